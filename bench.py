@@ -25,6 +25,8 @@ Output.  stdout carries ONE compact JSON line (< 6 KB, `compact_line()`: the con
 the full record (every leg with its notes and count tables) is written to bench_detail.json next to this file (--detail-out) and to stderr.
 The default run (`--legs core`) is the headline, the roofline legs, the precision legs `summary` is built from and the CPU baseline; `--legs all`
 adds the diagnostic / configs[4] legs (overlap_rec, ConvNextViT, ONNX recogniser, MtlTabNet / TableMaster).
+``--dump-outputs DIR`` also writes what the last timed step returned to its caller (boxes, texts, layout regions, table cells) as
+DIR/<name>.npy (`output_arrays()`); pages and weights are seeded, so the same arguments feed the same inputs on every run.
 
 Objects of the full record:
   roofline        the dominant kernel class (3x3 MFMA convolutions of all stages), HIP-event timed inside the timed region,
@@ -106,6 +108,9 @@ def parse_args(argv=None):
                          "reports it as tolerance_mode)")
     ap.add_argument("--stages", default=os.environ.get("PT_BENCH_STAGES", "layout,det,rec,tsr"),
                     help="comma list of stages in the timed step: layout (PicoDet), det (configs[1]), rec, tsr (Lore)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what predict_stream() returned for the last timed step's batch as DIR/<name>.npy "
+                         "(float64, at most 64 MB; rank 0's shard): the inputs are seeded, so two builds compare output for output")
     return ap.parse_args(argv)
 
 
@@ -522,6 +527,7 @@ class HipRunner:
         assert hi - lo == PAGES_PER_STEP
         made = [make_page(rank * DISTINCT + i, PAGE) for i in range(DISTINCT)]
         self.pages_np = np.stack([made[i % DISTINCT][0] for i in range(PAGES_PER_STEP)])
+        self.page_ids = [rank * DISTINCT + i % DISTINCT for i in range(PAGES_PER_STEP)]     # make_page() index of every page of a batch
         # ground truth of the generator: text-line rectangles (only with --gt-chain) and table rectangles.  The layout net
         # has random-init weights (its boxes are not tables), so the table-structure stage is fed the generator's own table
         # rectangles (1-2 per page) where the reference feeds it the layout boxes with label "table"
@@ -590,6 +596,7 @@ class HipRunner:
         # table regions: the layout stage's own (table_boxes=None: OcrTablePipeline._layout_table_boxes) unless --gt-tables / no fitted head
         tb = itertools.repeat(self.table_boxes, steps) if self.tsr is not None and not self.layout_chain else None
         c["tables"] = 0
+        res = None
         for res in self.pipe.predict_stream(itertools.repeat(self.pages if batch is None else batch, steps), table_boxes=tb):
             if count:
                 for r in res:
@@ -599,6 +606,7 @@ class HipRunner:
                     c["layout"] += len(r.layout_result or ())
                     c["cells"] += sum(len(t["polygons"]) for t in (r.table_structure_result or ()))
                     c["tables"] += len(r.table_structure_result or ())
+        self.last_results = res         # List[PageResult] of the last batch: what --dump-outputs writes
         if self.trace is not None:
             try:
                 hs = self.torch.cuda.host_memory_stats()
@@ -1278,6 +1286,57 @@ class HipRunner:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64 << 20  # bytes of --dump-outputs in all
+TABLE_KEYS = (("polygons", 8), ("logi", 4), ("logic_axis", 4), ("stacked_axis", 4), ("scores", 1))      # per table: TsrStage.collect()
+
+
+def output_arrays(results, page_ids):
+    """--dump-outputs: one batch's List[PageResult] (what predict_stream() hands its caller) as float64 arrays, pages concatenated in
+    order with their counts beside them, so that two runs compare array for array.  Texts are their Unicode code points.  When the
+    batch exceeds DUMP_LIMIT, whole pages of a seeded sample are kept; `page_ids` names the make_page() index of every page kept."""
+    def one(r):
+        boxes = np.asarray(r.det_result, np.float64).reshape(-1, 8)
+        ocr = r.ocr_result or []
+        a = {"det_boxes": boxes, "det_boxes_per_page": [len(boxes)],
+             "rec_bbox": np.asarray([o["bbox"] for o in ocr], np.float64).reshape(-1, 8), "rec_lines_per_page": [len(ocr)],
+             "rec_text_lengths": [len(o["text"]) for o in ocr], "rec_codepoints": [ord(ch) for o in ocr for ch in o["text"]]}
+        if r.layout_result is not None:
+            lay = r.layout_result
+            a.update(layout_bbox=np.asarray([d["bbox"] for d in lay], np.float64).reshape(-1, 4), layout_score=[d["score"] for d in lay],
+                     layout_category_id=[d["category_id"] for d in lay], layout_regions_per_page=[len(lay)])
+        if r.table_structure_result is not None:
+            tabs = r.table_structure_result
+            a["tables_per_page"] = [len(tabs)]
+            for key, width in TABLE_KEYS:
+                parts = [np.asarray(t[key], np.float64).reshape((-1, width) if width > 1 else (-1,)) for t in tabs]
+                a["table_" + key] = np.concatenate(parts) if parts else np.zeros((0, width) if width > 1 else (0,))
+                a[f"table_{key}_rows"] = [len(p) for p in parts]
+        return {k: np.asarray(v, np.float64) for k, v in a.items()}
+
+    per = [one(r) for r in results]
+    size = [sum(v.nbytes for v in p.values()) for p in per]
+    order = range(len(per)) if sum(size) <= DUMP_LIMIT else np.random.default_rng(0).permutation(len(per))
+    keep, total = [], 0
+    for i in order:
+        if total + size[i] <= DUMP_LIMIT:
+            keep.append(int(i))
+            total += size[i]
+    keep.sort()
+    assert keep, "no page's outputs fit DUMP_LIMIT"
+    out = {"page_ids": np.asarray(page_ids, np.float64)[keep]}
+    for k in per[0]:
+        out[k] = np.concatenate([per[i][k] for i in keep])
+    return out
+
+
+def dump_outputs(out_dir, results, page_ids):
+    arrays = output_arrays(results, page_ids)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": len(arrays), "bytes": sum(a.nbytes for a in arrays.values()), "pages": len(arrays["page_ids"])}
+
+
 LINE_LIMIT = 6000      # bytes of the ONE stdout line (VERDICT r05: the 20.8 KB line of round 5 was not parsed by the driver)
 
 
@@ -1412,10 +1471,17 @@ def main(argv=None):
             rccl_init_s = time.perf_counter() - t_init
 
     runner = StubRunner(args, rank, world) if stub else HipRunner(args, rank, local_rank, world, dist)
+    if args.dump_outputs and (stub or not runner.uses_pipeline()):
+        raise SystemExit("bench.py --dump-outputs: the timed path must be OcrTablePipeline.predict_stream() (no PT_BENCH_STUB, stages "
+                         "det and rec, no --private-loop / --gt-chain / --no-post / --overlap-rec)")
 
     def barrier():
         runner.sync()
-        if dist is not None:
+        if stub and dist is not None:
+            # gloo ranks without a device: dist.barrier() asks torch for the machine's accelerator first, which on a GPU host initialises
+            # HIP and opens the GPU in every rank (eight stub ranks = eight processes on the card); an all-reduce of a CPU tensor does not
+            dist.all_reduce(torch.zeros(1))
+        elif dist is not None:
             dist.barrier()
         runner.sync()
 
@@ -1458,6 +1524,9 @@ def main(argv=None):
                "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
                "config": runner.config(counts, args.steps)}
         out["config"]["spinup_steps_before_warmup"] = spin
+        if args.dump_outputs:       # outside the clock: host numpy over the last timed step's results
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, runner.last_results, runner.page_ids)
+            print(f"[bench] --dump-outputs: {out['dump_outputs']}", file=sys.stderr)
         if prof is not None:
             c3 = prof["conv3x3"]
             achieved = (c3["flop"] / (c3["ms"] * 1e-3)) / 1e12 if c3["ms"] > 0 else 0.0

@@ -5,7 +5,8 @@ Follows, function by function:
     /root/reference/src/pdftable/model/lore/dcnv2.py:71-86.  torchvision is not installed here; its algorithm is the
     DCNv2 im2col the reference vendors at lore/DCNv2_latest/src/cpu/dcn_v2_im2col_cpu.cpp:26-55 (bilinear rule) and
     :123-190 (sampling grid, zero outside (-1, H) x (-1, W), value * mask).  PINNED against that very source, compiled
-    from the reference tree into oracle/_ref/libdcnv2_ref.so (oracle/Makefile) -- tests/test_oracle_lore.py.
+    from the reference tree into oracle/_ref/libdcnv2_ref.so (oracle/Makefile), through the columns it produced for seeded
+    inputs (tests/golden/dcn_im2col.npz) -- tests/test_oracle_lore.py.
   * ``dla34_forward`` -- DLA.forward, center_net/modeling_centernet.py:382-402 with Tree.forward :259-271,
     Root.forward :167-175, BasicBlock.forward :58-72.
   * ``dlaseg_forward`` -- DLASeg.forward lore/lore_dla_34.py:184-196 with DLAUp.forward :128-134, IDAUp.forward :106-112,

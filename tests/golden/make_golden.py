@@ -54,18 +54,19 @@ def gen_db_resnet18():
     model = dbnet.DBModel().eval()
     sd = db_resnet18_state_dict(seed=11)
     model.load_state_dict(sd, strict=True)
+    model.double()          # float64 forward, outputs stored float32 (see gen_db_nas)
     rng = np.random.default_rng(101)
     out = {}
     for tag, (h, w) in {"a": (64, 96), "b": (128, 128)}.items():
         x = rng.standard_normal((1, 3, h, w)).astype(np.float32)
         with torch.no_grad():
-            xt = torch.from_numpy(x)
+            xt = torch.from_numpy(x).double()
             c2, c3, c4, c5 = model.backbone(xt)
             y = model(xt)
         out[f"x_{tag}"] = x
-        out[f"prob_{tag}"] = y.numpy()
-        out[f"c2_{tag}"] = c2.numpy()
-        out[f"c5_{tag}"] = c5.numpy()
+        out[f"prob_{tag}"] = y.float().numpy()
+        out[f"c2_{tag}"] = c2.float().numpy()
+        out[f"c5_{tag}"] = c5.float().numpy()
     out["seed"] = np.array(11)
     np.savez_compressed(os.path.join(HERE, "db_resnet18.npz"), **out)
     print("db_resnet18.npz", {k: v.shape for k, v in out.items()})
@@ -78,18 +79,22 @@ def gen_db_nas():
     model = dbnet.DBNasModel().eval()
     sd = db_nas_state_dict(seed=13)
     model.load_state_dict(sd, strict=True)
+    # float64 forward, outputs stored float32: a float32 forward pins one CPU's summation order (thread count, ISA), and the oracle on
+    # another CPU lands beyond the tests' bounds; the tests run the oracle in float64 against these (also gen_db_resnet18, gen_crnn,
+    # gen_lore_dla34, gen_lore_wireless)
+    model.double()
     rng = np.random.default_rng(113)
     out = {}
     for tag, (h, w) in {"a": (64, 96), "b": (160, 128)}.items():
         x = rng.standard_normal((1, 3, h, w)).astype(np.float32)
         with torch.no_grad():
-            xt = torch.from_numpy(x)
+            xt = torch.from_numpy(x).double()
             c2, c3, c4, c5 = model.backbone(xt)
             y = model(xt)
         out[f"x_{tag}"] = x
-        out[f"prob_{tag}"] = y.numpy()
-        out[f"c2_{tag}"] = c2.numpy()
-        out[f"c5_{tag}"] = c5.numpy()
+        out[f"prob_{tag}"] = y.float().numpy()
+        out[f"c2_{tag}"] = c2.float().numpy()
+        out[f"c5_{tag}"] = c5.float().numpy()
     out["seed"] = np.array(13)
     # the module's own parameter inventory: the synthetic checkpoint must have exactly these keys and shapes
     ref_sd = dbnet.DBNasModel().state_dict()
@@ -226,15 +231,16 @@ def gen_crnn():
     model = crnn.CRNN().eval()
     sd = crnn_state_dict(seed=12)
     model.load_state_dict(sd, strict=True)
+    model.double()          # float64 forward, outputs stored float32 (see gen_db_nas)
     rng = np.random.default_rng(102)
     x = rng.uniform(0, 1, (2, 3, 32, 96)).astype(np.float32)
     with torch.no_grad():
-        y = model(torch.from_numpy(x))
+        y = model(torch.from_numpy(x).double())
     # logits are [2, 24, 7644]; keep every 16th class column + argmax to stay small
     ynp = y.numpy()
     np.savez_compressed(os.path.join(HERE, "crnn.npz"), x=x, seed=np.array(12),
-                        logits_sub=ynp[:, :, ::16], argmax=ynp.argmax(-1).astype(np.int32),
-                        maxval=ynp.max(-1))
+                        logits_sub=ynp[:, :, ::16].astype(np.float32), argmax=ynp.argmax(-1).astype(np.int32),
+                        maxval=ynp.max(-1).astype(np.float32))
     print("crnn.npz logits", ynp.shape)
 
 
@@ -447,18 +453,38 @@ def gen_lore_dla34():
     model = m.get_dla_dcn(34, dict(LORE_HEADS), head_conv=256).eval()
     sd = lore_dla34_state_dict(seed=21)
     model.load_state_dict(sd, strict=True)
+    model.double()          # float64 forward, outputs stored float32 (see gen_db_nas)
     rng = np.random.default_rng(105)
     out = {"seed": np.array(21)}
     for tag, (h, w) in {"a": (128, 160), "b": (64, 64)}.items():
         x = rng.standard_normal((1, 3, h, w)).astype(np.float32)
         with torch.no_grad():
-            z = model(torch.from_numpy(x))[0]
+            z = model(torch.from_numpy(x).double())[0]
         out[f"x_{tag}"] = x
         for k, v in z.items():
-            v = v.numpy()
+            v = v.float().numpy()
             out[f"{k}_{tag}"] = v[:, ::8] if v.shape[1] == 256 else v     # every 8th channel of ax / cr
     np.savez_compressed(os.path.join(HERE, "lore_dla34.npz"), **out)
     print("lore_dla34.npz", {k: v.shape for k, v in out.items()})
+
+
+def gen_dcn_im2col():
+    """Columns of the reference's vendored modulated_deformable_im2col_cpu (DCNv2_latest/src/cpu/dcn_v2_im2col_cpu.cpp, compiled into
+    oracle/_ref/libdcnv2_ref.so by oracle/Makefile -- run __graft_entry__.build() first) for seeded inputs whose offsets leave the image
+    on every side; tests/test_oracle_lore.py holds the oracle's own columns to them bit for bit."""
+    from oracle import lore_net
+    out = {}
+    for i, (shape, scale) in enumerate([((2, 6, 13, 17), 1.5), ((1, 16, 32, 32), 4.0), ((1, 3, 5, 5), 8.0)]):
+        rng = np.random.default_rng(7)
+        B, C, H, W = shape
+        x = rng.standard_normal(shape).astype(np.float32)
+        off = (rng.standard_normal((B, 18, H, W)) * scale).astype(np.float32)
+        off[:, :, 0, 0] = np.round(off[:, :, 0, 0])                     # exact-integer positions too
+        m = rng.uniform(0, 1, (B, 9, H, W)).astype(np.float32)
+        out.update({f"case_{i}": np.array(list(shape) + [scale], np.float64), f"x_{i}": x, f"off_{i}": off, f"m_{i}": m,
+                    f"cols_{i}": lore_net.ref_dcn_im2col(x, off, m)})
+    np.savez_compressed(os.path.join(HERE, "dcn_im2col.npz"), **out)
+    print("dcn_im2col.npz", os.path.getsize(os.path.join(HERE, "dcn_im2col.npz")) // 1024, "KiB")
 
 
 def gen_lore_wireless():
@@ -469,15 +495,16 @@ def gen_lore_wireless():
     model = m.LoreDetectModel().eval()
     sd = lore_wireless_state_dict(seed=23)
     model.load_state_dict(sd, strict=True)
+    model.double()          # float64 forward, outputs stored float32 (see gen_db_nas)
     rng = np.random.default_rng(108)
     out = {"seed": np.array(23)}
     for tag, (h, w) in {"a": (128, 192), "b": (64, 128)}.items():   # sizes must be multiples of the total stride 64
         x = rng.standard_normal((1, 3, h, w)).astype(np.float32)
         with torch.no_grad():
-            z = model(torch.from_numpy(x))[0]
+            z = model(torch.from_numpy(x).double())[0]
         out[f"x_{tag}"] = x
         for k, v in z.items():
-            v = v.numpy()
+            v = v.float().numpy()
             out[f"{k}_{tag}"] = v[:, ::8] if v.shape[1] == 256 else v
     np.savez_compressed(os.path.join(HERE, "lore_wireless.npz"), **out)
     print("lore_wireless.npz", sum(p_.numel() for p_ in model.parameters()), "parameters")
@@ -1021,6 +1048,8 @@ if __name__ == "__main__":
         gen_lore_decode()
     if "lore_dla" in which:
         gen_lore_dla34()
+    if "dcn_im2col" in which or not sys.argv[1:]:
+        gen_dcn_im2col()
     if "lore_wireless" in which or not sys.argv[1:]:
         gen_lore_wireless()
     if "host" in which:
