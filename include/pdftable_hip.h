@@ -18,7 +18,10 @@
  *     its own activation arena and scratch inside the engine, so calls of DIFFERENT
  *     stages may be in flight on different streams at the same time (measured: +10 % pages/s with
  *     the recogniser on a second stream); two calls of the SAME stage -- and pt_cls_forward_lines
- *     with pt_rec_forward*, which share the crop buffers -- must be stream-ordered.
+ *     with pt_rec_forward*, which share the crop buffers -- must be stream-ordered.  The line classifier
+ *     pt_cls_forward_lines_direct owns its input buffer and activation arena: it may be in flight beside
+ *     pt_rec_forward* and the layout net (pt_layout_forward*, the other pt_cls_forward*) on other streams;
+ *     two calls of it must be stream-ordered.
  *     Distinct engines own all their state (weights,
  *     arena, scratch, the decode state between the steps of pt_tsr_forward_decode) and are
  *     independent, with ONE restriction per device: the bf16 recognition LSTM (pt_rec_forward*)
@@ -510,6 +513,14 @@ int pt_cls_forward(pt_engine* e, int slot, const uint8_t* d_base, const pt_cls_i
 int pt_cls_forward_lines(pt_engine* e, int slot, const uint8_t* d_pages_rgb, int n_pages, int h, int w,
                          const pt_rec_line* d_lines, const int64_t* h_crop_px, int n_lines, int max_crop_h, int max_crop_w,
                          int out_h, int out_w, int textline, float* d_logits, int* n_classes, pt_stream stream);
+/* The same logits as pt_cls_forward_lines (bit for bit), without h_crop_px and without the crop buffers it shares with
+ * pt_rec_forward*: one kernel samples every crop pixel from the pages while it resizes and normalises, into the call's
+ * own input buffer; the network runs in an activation arena of its own (see the concurrency rules at the top).
+ * Micro-batched like pt_cls_forward_lines (PT_CLS_MICROBATCH lines per network call).  A line whose crop_w or crop_h
+ * is <= 0 is read as a 1 x 1 crop sampled at its origin. */
+int pt_cls_forward_lines_direct(pt_engine* e, int slot, const uint8_t* d_pages_rgb, int n_pages, int h, int w,
+                                const pt_rec_line* d_lines, int n_lines, int max_crop_h, int max_crop_w, int out_h, int out_w,
+                                int textline, float* d_logits, int* n_classes, pt_stream stream);
 
 /* on = 1: every kernel launch of the forward calls is bracketed by hipEvents on `stream`; on = 2 + class: only the
  * launches of that kernel class (an event pair costs a few microseconds of idle GPU per launch, which adds up over the

@@ -79,6 +79,23 @@ class ClsStage:
         ok = scores > score_threshold
         return int(np.sum(ok & (ids == 0))) > int(np.sum(ok & (ids != 0)))
 
+    def page_votes(self, logits, counts: Sequence[int], score_threshold: float = 0.9) -> np.ndarray:
+        """orientation_vote() of every page at once from the host logits of all their lines (counts: lines per page, in order) -> bool [pages].
+        The same decision as the per-line dicts: the top-1 score is rounded in float64, as topk_postprocess rounds ``p[i].item()``
+        (top1() rounds the float32 array, which can land on the other side of the threshold)"""
+        counts = np.asarray(counts, dtype=np.int64)
+        x = np.ascontiguousarray(logits.numpy() if torch.is_tensor(logits) else logits, dtype=np.float32)
+        if not len(x):
+            return np.zeros(len(counts), dtype=bool)
+        p = torch.softmax(torch.from_numpy(x), dim=-1).numpy()
+        ids = np.argsort(p, axis=1)[:, -1]          # Topk's tie rule (the last of equal maxima in argsort order)
+        sc = np.around(p[np.arange(len(p)), ids].astype(np.float64), decimals=5)
+        ok = sc > score_threshold
+        page = np.repeat(np.arange(len(counts)), counts)
+        up = np.bincount(page[ok & (ids == 0)], minlength=len(counts))
+        down = np.bincount(page[ok & (ids != 0)], minlength=len(counts))
+        return up > down
+
     def images(self, images: Sequence[np.ndarray]) -> List[Dict]:
         """RGB uint8 host images of any sizes"""
         if not len(images):
@@ -94,6 +111,30 @@ class ClsStage:
         if not len(lines):
             return []
         return self.post(self.eng.cls_forward_lines(pages, lines, self.cfg["size"], self.slot, self.cfg["textline"]))
+
+    def lines_start(self, pages: torch.Tensor, lines: np.ndarray):
+        """asynchronous lines(): pt_cls_forward_lines_direct on the current stream (its own buffers: it may run beside the recogniser and the
+        layout net on other streams), then the logits on their way to pinned host memory behind an event.  -> (device logits, event, state);
+        lines_finish(state) waits for that copy only"""
+        n = len(lines)
+        if not n:
+            return None, None, (None, None, 0)
+        logits = self.eng.cls_forward_lines_direct(pages, lines, self.cfg["size"], self.slot, self.cfg["textline"])
+        ev = torch.cuda.Event()
+        ev.record()
+        host = torch.empty(tuple(logits.shape), dtype=torch.float32, pin_memory=True)
+        host.copy_(logits, non_blocking=True)       # the event is on this stream: the copy is queued behind it
+        done = torch.cuda.Event()
+        done.record()
+        return logits, ev, (host, done, n)
+
+    def lines_finish(self, state) -> List[Dict]:
+        """host half of lines_start(): the same per-line dicts as lines()"""
+        host, done, n = state
+        if not n:
+            return []
+        done.synchronize()
+        return self.post(host)
 
     def orientation_vote(self, results: List[Dict], score_threshold: float = 0.9) -> bool:
         """OcrSystemTask.text_line_orientation's decision (ocr_system_task.py:418-431): True = upright page"""

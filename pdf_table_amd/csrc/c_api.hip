@@ -103,6 +103,7 @@ void pt_engine_destroy(pt_engine* e) {
     if (e->rec_zero_ready[i]) (void)hipEventDestroy(e->rec_zero_ready[i]);
   if (e->rec_limits) (void)hipFree(e->rec_limits);
   if (e->cls_scratch) (void)hipFree(e->cls_scratch);
+  if (e->cls_direct_in) (void)hipFree(e->cls_direct_in);
   if (e->layout_scratch) (void)hipFree(e->layout_scratch);
   if (e->det_in) (void)hipFree(e->det_in);
   pt_mtl_release(e);
@@ -851,7 +852,7 @@ int pt_cls_forward_net(pt_engine* e, int slot, const uint16_t* d_input_bf16, int
   for (int i0 = 0; i0 < n; i0 += mb) {
     const int nb = (n - i0) < mb ? (n - i0) : mb;
     const int rc = pt_pplcnet_forward_net(e, slot, d_input_bf16 + (size_t)i0 * per, nb, in_h, in_w, textline,
-                                          d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s);
+                                          d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s, PT_ARENA_LAYOUT);
     if (rc != PT_OK) return rc;
   }
   return PT_OK;
@@ -875,7 +876,8 @@ int pt_cls_forward(pt_engine* e, int slot, const uint8_t* d_base, const pt_cls_i
       rc = pt_launch_cls_resize_norm(d_base, d_images + i0, nb, max_h, max_w, out_h, out_w, e->cls_lut, x3, xin, s);
       if (rc != PT_OK) return rc;
     }
-    rc = pt_pplcnet_forward_net(e, slot, xin, nb, out_h, out_w, textline, d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s);
+    rc = pt_pplcnet_forward_net(e, slot, xin, nb, out_h, out_w, textline, d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s,
+                                PT_ARENA_LAYOUT);
     if (rc != PT_OK) return rc;
   }
   return PT_OK;
@@ -917,7 +919,38 @@ int pt_cls_forward_lines(pt_engine* e, int slot, const uint8_t* d_pages_rgb, int
                                      out_w, e->cls_lut, x3, xin, s);
       if (rc != PT_OK) return rc;
     }
-    rc = pt_pplcnet_forward_net(e, slot, xin, nb, out_h, out_w, textline, d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s);
+    rc = pt_pplcnet_forward_net(e, slot, xin, nb, out_h, out_w, textline, d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s,
+                                PT_ARENA_LAYOUT);
+    if (rc != PT_OK) return rc;
+  }
+  return PT_OK;
+}
+
+// the line classifier without the recogniser's crop buffers: crop + resize + normalise in one kernel into its own input buffer (sized
+// once per micro-batch width, not by the lines' pixels), LCNet in PT_ARENA_CLS -- nothing shared with pt_rec_forward* or the layout net
+int pt_cls_forward_lines_direct(pt_engine* e, int slot, const uint8_t* d_pages_rgb, int n_pages, int h, int w, const pt_rec_line* d_lines,
+                                int n_lines, int max_crop_h, int max_crop_w, int out_h, int out_w, int textline, float* d_logits,
+                                int* n_classes, pt_stream stream) {
+  PT_REQUIRE(e && d_pages_rgb && d_lines && d_logits && n_lines > 0 && n_pages > 0 && h > 0 && w > 0,
+             "pt_cls_forward_lines_direct: bad arguments");
+  PT_HIP_CHECK(hipSetDevice(e->device));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  int rc;
+  if ((rc = cls_lut(e)) != PT_OK) return rc;
+  const int mb = cls_microbatch(), x3 = pt_split(e);
+  const size_t per = (size_t)out_h * out_w * (x3 ? 8 : 4);
+  const int cap = mb < n_lines ? mb : n_lines;
+  if ((rc = ensure(&e->cls_direct_in, &e->cls_direct_in_cap, (size_t)cap * per * sizeof(bf16_t))) != PT_OK) return rc;
+  bf16_t* xin = reinterpret_cast<bf16_t*>(e->cls_direct_in);
+  for (int i0 = 0; i0 < n_lines; i0 += mb) {
+    const int nb = (n_lines - i0) < mb ? (n_lines - i0) : mb;
+    {
+      PtProfScope ps(e, s, PT_PROF_OTHER, 0, "cls line resize+norm");
+      rc = pt_launch_cls_line_resize_norm(d_pages_rgb, h, w, d_lines + i0, nb, max_crop_h, max_crop_w, out_h, out_w, e->cls_lut, x3, xin, s);
+      if (rc != PT_OK) return rc;
+    }
+    rc = pt_pplcnet_forward_net(e, slot, xin, nb, out_h, out_w, textline, d_logits + (size_t)i0 * PT_CLS_MAX_CLASSES, n_classes, s,
+                                PT_ARENA_CLS);
     if (rc != PT_OK) return rc;
   }
   return PT_OK;

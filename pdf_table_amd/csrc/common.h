@@ -128,7 +128,8 @@ struct PtPinnedRing {
   }
 };
 
-enum { PT_ARENA_DET = 0, PT_ARENA_REC, PT_ARENA_TSR, PT_ARENA_TSRP, PT_ARENA_LAYOUT, PT_ARENA_COUNT };   // TSRP: the Lore processor
+enum { PT_ARENA_DET = 0, PT_ARENA_REC, PT_ARENA_TSR, PT_ARENA_TSRP, PT_ARENA_LAYOUT, PT_ARENA_CLS, PT_ARENA_COUNT };   // TSRP: the Lore processor;
+// CLS: the PP-LCNet of pt_cls_forward_lines_direct (in flight beside the layout net and the recogniser)
 
 struct PtProfile {
   int on = 0;         // 0 off, 1 every launch, 2 + class: only the launches of kernel class (on - 2)
@@ -155,7 +156,8 @@ struct pt_engine {
   int device = 0;
   int num_cu = 256;
   // one activation arena per stage, so that calls of DIFFERENT stages may be in flight on different streams (two calls of
-  // one stage share its arena and must be stream-ordered); layout and the PP-LCNet classifiers share PT_ARENA_LAYOUT
+  // one stage share its arena and must be stream-ordered); layout and the PP-LCNet classifiers share PT_ARENA_LAYOUT, except the line
+  // classifier pt_cls_forward_lines_direct, which owns PT_ARENA_CLS and cls_direct_in
   PtArena arenas[PT_ARENA_COUNT];
   std::map<int, PtModel> models;
   PtProfile prof;
@@ -172,6 +174,7 @@ struct pt_engine {
   void* layout_scratch = nullptr; size_t layout_scratch_cap = 0;   // layout input + head maps (pt_layout_forward)
   float* tsr_lut = nullptr;                                  // [3][256] normalisation table of the Lore pre-process
   float* cls_lut = nullptr;                                  // [3][256] ... of the PP-LCNet pre-process
+  void* cls_direct_in = nullptr; size_t cls_direct_in_cap = 0;   // network input of pt_cls_forward_lines_direct (one micro-batch)
   float* rec_pp_lut = nullptr;                               // [256] (v / 255 - 0.5) / 0.5 of the PP-OCR recognition pre-process
   void* cls_scratch = nullptr; size_t cls_scratch_cap = 0;   // network input + image descriptors of pt_cls_forward*
   alignas(8) unsigned char tsr_decode_state[128] = {};       // lore_decode.hip: DecodeState of the sparse-head decode in flight
@@ -200,6 +203,37 @@ struct pt_engine {
 
 // Everything below exists once per activation format (act16.h): the launchers and the model drivers of namespace pt_bf16 and of namespace pt_f16.
 namespace PT_FMT_NS {
+
+// ---- perspective sample of a text-line crop (rec_warp_kernel, cls_line_resize_norm_kernel) --------------------------------------------
+// cv2.warpPerspective(img, M, (w, h)) for 8-bit RGB, INTER_LINEAR, constant border 0, at destination pixel (x, y): (X, Y, W) = Minv * (x, y, 1)
+// in double; X*32/W, Y*32/W rounded to nearest give the source position in 1/32 pixel; the four neighbours are blended with 15-bit weights
+// (32-ay)(32-ax)*32 ... and the sum is rounded with +2^14 >> 15.  src: the line's page, uint8 [ph, pw, 3]; m: the line's pt_rec_line::minv.
+// Compiled with -ffp-contract=off like every caller: the products and sums round exactly as written.
+__device__ __forceinline__ void pt_warp_sample(const uint8_t* __restrict__ src, int ph, int pw, const double* m, int x, int y, int v[3]) {
+  const double X0 = m[0] * x + m[1] * y + m[2];
+  const double Y0 = m[3] * x + m[4] * y + m[5];
+  double W = m[6] * x + m[7] * y + m[8];
+  W = W != 0. ? 32. / W : 0.;
+  const double fX = fmax(-2147483648., fmin(2147483647., X0 * W));
+  const double fY = fmax(-2147483648., fmin(2147483647., Y0 * W));
+  const long long Xi = (long long)rint(fX), Yi = (long long)rint(fY);
+  const long long sx = Xi >> 5, sy = Yi >> 5;
+  const int ax = (int)(Xi & 31), ay = (int)(Yi & 31);
+  const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32, w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
+  int acc[3] = {0, 0, 0};
+  auto tap = [&](long long yy, long long xx, int wgt) {
+    if (wgt && yy >= 0 && yy < ph && xx >= 0 && xx < pw) {
+      const uint8_t* p = src + ((size_t)yy * pw + xx) * 3;
+      acc[0] += p[0] * wgt; acc[1] += p[1] * wgt; acc[2] += p[2] * wgt;
+    }
+  };
+  tap(sy, sx, w00); tap(sy, sx + 1, w01); tap(sy + 1, sx, w10); tap(sy + 1, sx + 1, w11);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int t = (acc[c] + (1 << 14)) >> 15;
+    v[c] = t < 0 ? 0 : (t > 255 ? 255 : t);
+  }
+}
 
 // ---- conv launcher (conv_igemm.hip) -----------------------------------------------------------------
 struct ConvDesc {
@@ -314,10 +348,12 @@ int pt_launch_se(const bf16_t* x, const float* w1, const float* b1, const float*
 int pt_launch_add(const bf16_t* a, const bf16_t* b, bf16_t* out, long long npix, int C, int split, hipStream_t s);
 int pt_launch_chan_mean(const bf16_t* x, int B, int HW, int C, int split, float* part, bf16_t* mean, int rows, hipStream_t s);
 int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H, int W, int textline, float* logits,
-                           int* n_classes, hipStream_t s);
+                           int* n_classes, hipStream_t s, int arena);
 int pt_launch_cls_resize_norm(const uint8_t* base, const pt_cls_image* images, int n, int max_h, int max_w, int OH, int OW,
                               const float* lut, int split, bf16_t* out, hipStream_t s);
 int pt_launch_cls_desc_from_lines(const pt_rec_line* lines, const long long* off, int n, pt_cls_image* images, hipStream_t s);
+int pt_launch_cls_line_resize_norm(const uint8_t* pages, int ph, int pw, const pt_rec_line* lines, int n, int max_h, int max_w, int OH,
+                                   int OW, const float* lut, int split, bf16_t* out, hipStream_t s);
 int pt_launch_dbnas_tail(const bf16_t* y, const float* tw, int B, int H4, int W4, int split, float* prob, float* logits,
                          hipStream_t s);
 int pt_dbnas_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* prob, float* logits, hipStream_t s);

@@ -38,11 +38,12 @@ struct Ctx {
   float* gate = nullptr;
   float* part = nullptr;      // PT_SE_CHUNKS * n * 512 floats: two-level average pool of the SE blocks (null: single-workgroup scan)
   const char* what = "PicoDet";
+  int arena = PT_ARENA_LAYOUT;  // activation arena of the net (PT_ARENA_CLS: the line classifier of pt_cls_forward_lines_direct)
 
   T alloc(int H, int W, int C) {
     T t;
     t.H = H; t.W = W; t.C = C;
-    t.p = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)n * H * W * C * mul * sizeof(bf16_t)));
+    t.p = reinterpret_cast<bf16_t*>(e->arenas[arena].take((size_t)n * H * W * C * mul * sizeof(bf16_t)));
     if (!t.p) ok = false;
     return t;
   }
@@ -297,9 +298,11 @@ int pt_picodet_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, f
 // mode); textline != 0: stride_list [2, [2,1], [2,1], [2,1], [2,1]] (textline_orientation / language_classification).
 // logits: fp32 [n, 16], the first *n_classes columns valid.  slot: which of the PT_CLS_SLOTS loaded classifiers
 // (model kind PT_MODEL_PPLCNET + slot) -- the reference keeps several alive at once (ocr_system_task.py:116-146).
+// arena: PT_ARENA_LAYOUT (shared with the layout net: stream-ordered with it) or PT_ARENA_CLS (pt_cls_forward_lines_direct).
 int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H, int W, int textline, float* logits,
-                           int* n_classes, hipStream_t s) {
-  PT_REQUIRE(x && logits && n > 0 && H > 0 && W > 0 && slot >= 0 && slot < PT_CLS_SLOTS, "PP-LCNet: bad arguments");
+                           int* n_classes, hipStream_t s, int arena) {
+  PT_REQUIRE(x && logits && n > 0 && H > 0 && W > 0 && slot >= 0 && slot < PT_CLS_SLOTS &&
+             (arena == PT_ARENA_LAYOUT || arena == PT_ARENA_CLS), "PP-LCNet: bad arguments");
   auto it = e->models.find(PT_MODEL_PPLCNET + slot);
   if (it == e->models.end()) {
     pt_set_error("PP-LCNet weights not loaded (pt_weights_load(PT_MODEL_PPLCNET + %d))", slot);
@@ -312,6 +315,8 @@ int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H
   c.mul = c.x3 ? 2 : 1;
   c.rc = PT_OK;
   c.what = "PP-LCNet";
+  c.arena = arena;
+  PtArena& A = e->arenas[arena];
   const PtTensor* nc = c.get("fc.nclass");
   if (!nc) return c.rc;
   if (n_classes) *n_classes = (int)nc->dims[0];
@@ -320,9 +325,9 @@ int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H
   for (int pass = 0; pass < 2; ++pass) {
     c.dry = pass == 0;
     c.ok = true;
-    e->arenas[PT_ARENA_LAYOUT].reset();
-    c.gate = reinterpret_cast<float*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)n * 512 * sizeof(float)));
-    float* part = reinterpret_cast<float*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float)));
+    A.reset();
+    c.gate = reinterpret_cast<float*>(A.take((size_t)n * 512 * sizeof(float)));
+    float* part = reinterpret_cast<float*>(A.take((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float)));
     c.part = part;
     if (!c.gate || !part) c.ok = false;
     T feats[3];
@@ -331,11 +336,11 @@ int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H
     const int keep = c.n;
     T mean;
     mean.H = rows / 32; mean.W = 32; mean.C = 512;
-    mean.p = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)rows * 512 * c.mul * sizeof(bf16_t)));
+    mean.p = reinterpret_cast<bf16_t*>(A.take((size_t)rows * 512 * c.mul * sizeof(bf16_t)));
     T hid;
     hid.H = rows / 32; hid.W = 32; hid.C = 1280;
-    hid.p = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)rows * 1280 * c.mul * sizeof(bf16_t)));
-    float* lg = reinterpret_cast<float*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)rows * 16 * sizeof(float)));
+    hid.p = reinterpret_cast<bf16_t*>(A.take((size_t)rows * 1280 * c.mul * sizeof(bf16_t)));
+    float* lg = reinterpret_cast<float*>(A.take((size_t)rows * 16 * sizeof(float)));
     if (!mean.p || !hid.p || !lg) c.ok = false;
     if (c.go()) {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "pplcnet avgpool");
@@ -351,11 +356,11 @@ int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H
     if (pass == 0) {
       if (c.ok) continue;
       PT_HIP_CHECK(hipDeviceSynchronize());
-      if (e->arenas[PT_ARENA_LAYOUT].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_LAYOUT].base));
-      e->arenas[PT_ARENA_LAYOUT].base = nullptr;
-      const size_t want = pt_arena_round(e->arenas[PT_ARENA_LAYOUT].high);
-      PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_LAYOUT].base), want));
-      e->arenas[PT_ARENA_LAYOUT].cap = want;
+      if (A.base) PT_HIP_CHECK(hipFree(A.base));
+      A.base = nullptr;
+      const size_t want = pt_arena_round(A.high);
+      PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&A.base), want));
+      A.cap = want;
       continue;
     }
     if (!c.ok) {

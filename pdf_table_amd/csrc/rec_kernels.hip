@@ -24,10 +24,8 @@ __device__ __forceinline__ float rbf2f(uint32_t bits16) { return a16_to_f32(bits
 __device__ __forceinline__ uint32_t rf2bf(float f) { return f32_to_a16(f); }
 
 // ---------------------------------------------------------------------------------------------------
-// Perspective crop.  cv2.warpPerspective(img, M, (w, h)) semantics for 8-bit, INTER_LINEAR, constant border 0:
-// destination (x, y) -> (X, Y, W) = Minv * (x, y, 1) in double; X*32/W, Y*32/W rounded to nearest integer give
-// the source position in 1/32 pixel; the four neighbours are blended with 15-bit weights
-// (32-ay)(32-ax)*32 ... and the sum is rounded with +2^14 >> 15.
+// Perspective crop.  cv2.warpPerspective(img, M, (w, h)) semantics for 8-bit, INTER_LINEAR, constant border 0, one
+// pt_warp_sample (common.h) per crop pixel; cls_line_resize_norm_kernel samples the same way without the crop buffer.
 // ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rec_warp_kernel(const uint8_t* __restrict__ pages, int ph, int pw,
                                                         const pt_rec_line* __restrict__ lines, int n_lines,
@@ -42,29 +40,10 @@ __global__ __launch_bounds__(256) void rec_warp_kernel(const uint8_t* __restrict
   const uint8_t* src = pages + (size_t)L.page * ph * pw * 3;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += (long long)gridDim.x * blockDim.x) {
     const int x = (int)(i % cw), y = (int)(i / cw);
-    const double X0 = L.minv[0] * x + L.minv[1] * y + L.minv[2];
-    const double Y0 = L.minv[3] * x + L.minv[4] * y + L.minv[5];
-    double W = L.minv[6] * x + L.minv[7] * y + L.minv[8];
-    W = W != 0. ? 32. / W : 0.;
-    const double fX = fmax(-2147483648., fmin(2147483647., X0 * W));
-    const double fY = fmax(-2147483648., fmin(2147483647., Y0 * W));
-    const long long Xi = (long long)rint(fX), Yi = (long long)rint(fY);
-    const long long sx = Xi >> 5, sy = Yi >> 5;
-    const int ax = (int)(Xi & 31), ay = (int)(Yi & 31);
-    const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32, w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
-    int acc[3] = {0, 0, 0};
-    auto tap = [&](long long yy, long long xx, int wgt) {
-      if (wgt && yy >= 0 && yy < ph && xx >= 0 && xx < pw) {
-        const uint8_t* p = src + ((size_t)yy * pw + xx) * 3;
-        acc[0] += p[0] * wgt; acc[1] += p[1] * wgt; acc[2] += p[2] * wgt;
-      }
-    };
-    tap(sy, sx, w00); tap(sy, sx + 1, w01); tap(sy + 1, sx, w10); tap(sy + 1, sx + 1, w11);
+    int v[3];
+    pt_warp_sample(src, ph, pw, L.minv, x, y, v);      // common.h
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      int v = (acc[c] + (1 << 14)) >> 15;
-      dst[i * 3 + c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-    }
+    for (int c = 0; c < 3; ++c) dst[i * 3 + c] = (uint8_t)v[c];
   }
 }
 

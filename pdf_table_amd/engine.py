@@ -399,6 +399,22 @@ class HipEngine:
                                                   self._stream()), "pt_cls_forward_lines")
         return logits[:, :nc.value] if nl else logits[:, :0]
 
+    def cls_forward_lines_direct(self, pages: torch.Tensor, lines: np.ndarray, out_hw, slot: int = 0, textline: bool = True):
+        """cls_forward_lines() without the recogniser's crop buffers (pt_cls_forward_lines_direct): bit-identical logits, and the call may be in
+        flight beside rec_forward*() and the layout net on other streams"""
+        self._chk(pages, torch.uint8, "pages")
+        n, h, w, _ = pages.shape
+        nl = len(lines)
+        logits = torch.empty((nl, L.PT_CLS_MAX_CLASSES), dtype=torch.float32, device=self._tdev)
+        nc = C.c_int(0)
+        if nl:
+            d, _ = self._lines_to_device(lines)
+            mh, mw = max(1, int(lines["crop_h"].max())), max(1, int(lines["crop_w"].max()))
+            L.check(self.lib.pt_cls_forward_lines_direct(self._h, slot, _ptr(pages), n, h, w, _ptr(d), nl, mh, mw, out_hw[0], out_hw[1],
+                                                         int(textline), _ptr(logits), C.byref(nc), self._stream()),
+                    "pt_cls_forward_lines_direct")
+        return logits[:, :nc.value] if nl else logits[:, :0]
+
     # ---- recognition ------------------------------------------------------------------------------
     def _lines_to_device(self, lines: np.ndarray):
         """structured array (REC_LINE_DTYPE) -> (uint8 device tensor holding the pt_rec_line records, host crop px)."""

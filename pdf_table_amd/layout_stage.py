@@ -102,10 +102,11 @@ class LayoutStage:
         self._pinned = [None, None]          # two host landing buffers: a forward() may be queued while the previous finish() still reads
         self._turn = 0
 
-    def forward(self, pages: torch.Tensor):
+    def forward(self, pages: torch.Tensor, landing=None):
         """device half (asynchronous): network + candidate compaction on the current stream, then the D2H of the
         records on a copy stream behind an event -- finish() waits for that copy only, not for whatever else has
-        been queued on the compute stream meanwhile"""
+        been queued on the compute stream meanwhile.  ``landing``: a key of its own host landing buffer, outside the two
+        that alternate (predict_stream's second layout pass over pages rotated by the orientation vote)"""
         cfg = self.config
         # the stage's precision is host state read when a call is QUEUED: the launches below carry it, later calls do not; the scope holds the
         # engine's lock, so no other host thread can queue a call in this stage's precision meanwhile
@@ -115,12 +116,18 @@ class LayoutStage:
         n = counts.shape[0]
         if self._copy_stream is None:
             self._copy_stream = shared_stream(counts.device, "layout_copy")
-        slot = self._turn
-        self._turn ^= 1
-        if self._pinned[slot] is None or self._pinned[slot][0].shape[0] < n:
-            self._pinned[slot] = (torch.empty((n,), dtype=torch.int32).pin_memory(),
-                                  torch.empty((n, self.max_cands, L.PT_LAYOUT_CAND_FLOATS), dtype=torch.float32).pin_memory())
-        host = self._pinned[slot]
+        if landing is None:
+            slot = self._turn
+            self._turn ^= 1
+            pinned = self._pinned
+        else:
+            slot = landing
+            pinned = self.__dict__.setdefault("_pinned_extra", {})
+        host = pinned.get(slot) if isinstance(pinned, dict) else pinned[slot]
+        if host is None or host[0].shape[0] < n:
+            host = (torch.empty((n,), dtype=torch.int32).pin_memory(),
+                    torch.empty((n, self.max_cands, L.PT_LAYOUT_CAND_FLOATS), dtype=torch.float32).pin_memory())
+            pinned[slot] = host
         ready = torch.cuda.Event()
         ready.record()
         with torch.cuda.stream(self._copy_stream):

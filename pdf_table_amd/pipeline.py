@@ -33,7 +33,7 @@ from .ocr_detection_task import OcrDetectionTask, _read_image
 from .layout_stage import layout_tables
 from .ocr_layout_task import OcrLayoutTask
 from .ocr_recognition_task import OcrRecognitionTask
-from .rec_stage import order_points
+from .rec_stage import build_lines, order_points
 from .trace_ranges import stage_range
 from .ocr_table_structure_task import OcrTableStructureTask
 
@@ -131,10 +131,12 @@ class OcrTablePipeline:
 
     @classmethod
     def from_engine(cls, engine: HipEngine, det_stage: DetStage, rec_stage, layout_stage=None, tsr_stage=None, table_html: bool = False,
-                    overlap_rec: bool = False, aux_layout: bool = False, tsr_on_aux: bool = False, lookahead: int = 1) -> "OcrTablePipeline":
+                    overlap_rec: bool = False, aux_layout: bool = False, tsr_on_aux: bool = False, lookahead: int = 1,
+                    orientation_stage=None) -> "OcrTablePipeline":
         """The façade over an engine whose weights are ALREADY loaded -- e.g. packed once on rank 0, broadcast over RCCL and loaded from
         device memory on every rank (dist_utils.broadcast_blob, ``bench.py --gpus N``) -- and over stage objects the caller built on it.
-        ``predict()`` / ``predict_stream()`` are the same code as after the ordinary constructor."""
+        ``predict()`` / ``predict_stream()`` are the same code as after the ordinary constructor.  ``orientation_stage``: a ClsStage of the
+        "textline_orientation" task on that engine: the text-line orientation vote (what ``text_orientation=True`` attaches)."""
         import types
         self = cls.__new__(cls)
         self.engine, self.overlap_rec, self.rotate_upside_down, self._rec_stream = engine, overlap_rec, True, None
@@ -145,6 +147,11 @@ class OcrTablePipeline:
         self.layout_task = None if layout_stage is None else types.SimpleNamespace(_stage=layout_stage, detect_pages=layout_stage)
         self.table_structure_task = None if tsr_stage is None else types.SimpleNamespace(
             _stage=tsr_stage, recognize_tables=lambda pages, boxes, page_frame=True: tsr_stage(pages, boxes, page_frame=page_frame))
+        if orientation_stage is not None:
+            def lines(pages, quads_per_page, st=orientation_stage):       # ClsImagePulcTask.lines
+                res = st.lines(pages, build_lines(quads_per_page))
+                return res, st.orientation_vote(res)
+            self.orientation_task = types.SimpleNamespace(_stage=orientation_stage, lines=lines)
         return self
 
     def predict(self, pages: Sequence, table_boxes: Optional[Sequence[np.ndarray]] = None, **kwargs) -> List[PageResult]:
@@ -325,7 +332,7 @@ class OcrTablePipeline:
             out.append(row)
         return out
 
-    def predict_stream(self, batches, table_boxes=None):
+    def predict_stream(self, batches, table_boxes=None, orientation_vote: bool = False):
         """``predict()`` over a stream of page batches, software-pipelined: a generator that takes an iterable of batches (each a
         sequence of equally sized RGB pages, or a uint8 tensor [n, h, w, 3] already on the device) and yields one
         ``List[PageResult]`` per batch, in order, with the results ``predict()`` gives for that batch.
@@ -344,10 +351,23 @@ class OcrTablePipeline:
         the generator drains at the end.  ``tsr_on_aux=True`` runs the processor on an auxiliary stream in the collect step
         instead (a = 1, two batches of latency, measured slower: concurrent small kernels beside the cluster LSTM and the large
         convolutions); ``aux_layout=True`` does the same for the layout network.
-        ``table_boxes``: optional iterable aligned with ``batches`` (per batch: per-page int [k, 4] regions).  The text-line
-        orientation vote needs a second, dependent detection pass per page and is not pipelined: use ``predict()`` for it."""
-        if self.orientation_task is not None:
-            raise ValueError("predict_stream() does not run the text-line orientation vote; use predict()")
+        ``table_boxes``: optional iterable aligned with ``batches`` (per batch: per-page int [k, 4] regions).
+
+        ``orientation_vote=True`` (needs ``text_orientation=True``; without it such a pipeline refuses to stream): the text-line orientation
+        vote of ``predict()`` as one more stage of the pipeline.  Right after the host halves of batch j produced its boxes, the line
+        classifier over all of them is queued on the main stream (pt_cls_forward_lines_direct: its own buffers, beside the recogniser and
+        the layout net).  One step later (orient): the host waits for that classifier only, votes per page like predict() (a page
+        without lines votes "not upright"), and -- with ``rotate_upside_down`` -- flips the pages voted upside-down in place and queues
+        detection (a slot of its own) and layout again over just those pages; their host halves replace those pages' boxes and layout
+        a step after that, and caller-given table boxes follow the rotation.  Everything after detection moves a lookahead later:
+        results arrive one batch later than without the vote at a = 1 (four batches behind the input), whether or not a page flips.
+        The fields ``rotated_180``, ``text_upright`` and ``text_line_orientation`` are filled as in predict()."""
+        vote = bool(orientation_vote)
+        if self.orientation_task is not None and not vote:
+            raise ValueError("predict_stream() runs the text-line orientation vote only when asked: predict_stream(..., orientation_vote=True) "
+                             "(one more batch of latency), or predict()")
+        if vote and self.orientation_task is None:
+            raise ValueError("orientation_vote=True needs the text-line orientation classifier (text_orientation=True)")
         if self.table_structure_task is not None and table_boxes is None and self.layout_task is None:
             raise ValueError("table_structure=True needs layout=True or predict_stream(table_boxes=...)")
         dev = self.engine._tdev
@@ -369,10 +389,14 @@ class OcrTablePipeline:
         t_start = time.time()
         total_lines = 0
         host = {"queue_first": 0.0, "queue_second": 0.0, "process_tables": 0.0, "collect": 0.0, "host_halves": 0.0}      # host seconds per phase (self.metric)
+        cls_stage = self.orientation_task._stage if vote else None
+        if vote:
+            host["orient"] = 0.0
 
         def queue_first(batch, k):
             """layout(k) + detection(k)"""
             up = torch.cuda.Event()
+            caller_owned = False
             if torch.is_tensor(batch) and batch.device.type == "cpu":
                 # host batch: H2D on a copy stream, queued NOW -- the enqueue thread runs ahead of the GPU, so the transfer overlaps the
                 # compute of the batches before it (asynchronous when the batch is pinned; a pageable batch is staged by the runtime)
@@ -386,6 +410,7 @@ class OcrTablePipeline:
             elif torch.is_tensor(batch):
                 pages_t = batch.to(dev)
                 up.record(main)
+                caller_owned = pages_t is batch
             else:
                 imgs = [_read_image(p) for p in batch]
                 if len({im.shape for im in imgs}) != 1:
@@ -395,11 +420,15 @@ class OcrTablePipeline:
             st = {"pages": pages_t, "shape": tuple(pages_t.shape[1:3]), "n": pages_t.shape[0],
                   "tb": [np.asarray(b).reshape(-1, 4) for b in next(tb_iter)] if tb_iter is not None else None}
             st["uploaded"] = up
+            st["k"], st["caller_owned"] = k, caller_owned
             if lay_stage is not None:
                 if getattr(self, "aux_layout", False):
                     with torch.cuda.stream(aux):
                         aux.wait_event(up)
                         st["lay"] = lay_stage.forward(pages_t)
+                        if vote:      # the orientation flip writes the pages: after this read
+                            st["lay_read"] = torch.cuda.Event()
+                            st["lay_read"].record(aux)
                     pages_t.record_stream(aux)
                 else:       # one compute stream: per-kernel durations are those of the kernel alone (what bench.py's roofline divides by)
                     with stage_range("layout"):
@@ -417,6 +446,75 @@ class OcrTablePipeline:
             st["layout"] = lay_stage.finish(st["lay"][0], st["lay"][1], st["shape"]) if lay_stage is not None else None
             host["halves.boxes"] = host.get("halves.boxes", 0.0) + t1 - t0
             host["halves.layout"] = host.get("halves.layout", 0.0) + time.perf_counter() - t1
+
+        def start_orientation(st):
+            """the line classifier over every line of the batch's first detection, queued on the main stream (end of host_halves)"""
+            t0 = time.perf_counter()
+            lines = build_lines(st["boxes"])
+            st["ori_counts"] = [len(b) for b in st["boxes"]]
+            st["cls"] = cls_stage.lines_start(st["pages"], lines)
+            host["halves.cls_start"] = host.get("halves.cls_start", 0.0) + time.perf_counter() - t0
+
+        def orient(st):
+            """the vote of the classifier queued one step ago (waits for it only); pages voted upside-down are flipped in place and detected
+            (and laid out) again -- on a detection slot and a layout landing buffer of their own"""
+            _, _, state = st["cls"]
+            host_logits, done, n_lines = state
+            if n_lines:
+                done.synchronize()
+                votes = cls_stage.page_votes(host_logits, st["ori_counts"])
+            else:
+                votes = np.zeros(st["n"], dtype=bool)
+            st["upright"] = [bool(v) for v in votes]
+            down = [k for k in range(st["n"]) if not votes[k]] if self.rotate_upside_down else []
+            st["down"] = down
+            if not down:
+                return
+            sel = torch.tensor(down, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+            if "lay_read" in st:
+                main.wait_event(st["lay_read"])
+            pages = st["pages"]
+            if st["caller_owned"]:       # never rotate the caller's own tensor
+                pages = pages.clone()
+                st["pages"] = pages
+            pages[sel] = torch.flip(pages[sel], dims=(1, 2))
+            sub = pages[sel]
+            flipped = torch.cuda.Event()
+            flipped.record(main)
+            st["uploaded"] = flipped        # what the recogniser / a table stream on other streams wait for from now on
+            ring = st["k"] % a_             # at most a_ second passes are in flight (issued at step j + a, finished at the end of j + 2a - 1)
+            with stage_range("text_detection"):
+                st["det2"] = det.forward(sub, slot=2 + ring, early_copy=True)
+            if lay_stage is not None:
+                if getattr(self, "aux_layout", False):
+                    with torch.cuda.stream(aux):
+                        aux.wait_event(flipped)
+                        st["lay2"] = lay_stage.forward(sub, landing=("orient", ring))
+                    sub.record_stream(aux)
+                else:
+                    with stage_range("layout"):
+                        st["lay2"] = lay_stage.forward(sub, landing=("orient", ring))
+            st["sub"] = sub
+
+        def orient_halves(st):
+            """host halves of the second detection / layout pass: those pages' boxes and layout replaced, given table boxes rotated"""
+            t0 = time.perf_counter()
+            down = st.get("down")
+            if down:
+                shape = st["shape"]
+                prob, bitmap, ev = st["det2"]
+                again = [sort_boxes_reading_order(b) for b in det.boxes(prob, bitmap, shape, ev)]
+                lay2 = lay_stage.finish(st["lay2"][0], st["lay2"][1], shape) if lay_stage is not None else None
+                for i, k in enumerate(down):
+                    st["boxes"][k] = again[i]
+                    if lay2 is not None:
+                        st["layout"][k] = lay2[i]
+                    if st["tb"] is not None and len(st["tb"][k]):     # boxes given for the page as handed in: follow its rotation
+                        x1, y1, x2, y2 = st["tb"][k].T
+                        st["tb"][k] = np.stack([shape[1] - x2, shape[0] - y2, shape[1] - x1, shape[0] - y1], 1)
+                del st["det2"]
+                st.pop("lay2", None)
+            host["halves.orient"] = host.get("halves.orient", 0.0) + time.perf_counter() - t0
 
         def queue_second(st):
             """recognition + table detector / decode on the boxes and regions host_halves() produced one step ago"""
@@ -505,6 +603,15 @@ class OcrTablePipeline:
             if tsr is not None and self.table_html:
                 self._attach_html(tsr, st["tb"], st["boxes"], texts)
             tsr = self._realign_tables(tsr, st.get("kept"))
+            ori = None
+            if vote:
+                t2 = time.perf_counter()
+                flat = cls_stage.lines_finish(st["cls"][2])
+                ori, o = [], 0
+                for c in st["ori_counts"]:
+                    ori.append(flat[o:o + c])
+                    o += c
+                host["collect.orientation"] = host.get("collect.orientation", 0.0) + time.perf_counter() - t2
             out = []
             for k in range(st["n"]):
                 boxes = st["boxes"][k]
@@ -512,7 +619,10 @@ class OcrTablePipeline:
                 ocr = [{"index": j + 1, "text": t, "bbox": pts[j]} for j, t in enumerate(texts[k])]
                 total_lines += len(ocr)
                 out.append(PageResult(det_result=boxes, ocr_result=ocr, layout_result=None if st["layout"] is None else st["layout"][k],
-                                      table_structure_result=None if tsr is None else tsr[k]))
+                                      table_structure_result=None if tsr is None else tsr[k],
+                                      text_upright=None if ori is None else st["upright"][k],
+                                      rotated_180=bool(ori is not None and k in st["down"]),
+                                      text_line_orientation=None if ori is None else ori[k]))
             return out
 
         gpu_marks = [] if os.environ.get("PT_PIPE_GPU_TRACE") else None      # diagnostics: (phase, begin event, end event) on the main stream
@@ -550,23 +660,36 @@ class OcrTablePipeline:
             a_ = 1
         flight: Dict[int, dict] = {}
         k = 0
+        # orientation_vote: orient(j) at step j + a, the second pass's host halves at the end of step j + 2a - 1; every later phase of the
+        # batch moves by a steps
+        s_ = a_ if vote else 0
 
         def step(j: int, cur):
             """one step of the schedule at stream position j (cur: the batch that arrived, or None while draining)"""
             if cur is not None:
                 flight[j] = cur
-            st = flight.get(j - a_)
+            if vote:
+                st = flight.get(j - a_)
+                if st is not None:
+                    timed("orient", orient, st)
+            st = flight.get(j - a_ - s_)
             if st is not None:
                 timed("queue_second", queue_second, st)
             if depth == 3:
-                st = flight.get(j - 2 * a_)
+                st = flight.get(j - 2 * a_ - s_)
                 if st is not None:
                     timed("process_tables", process_tables, st)
-            done = flight.pop(j - 2 * a_ - (1 if depth == 3 else 0), None)
+            done = flight.pop(j - 2 * a_ - s_ - (1 if depth == 3 else 0), None)
             res = timed("collect", collect, done) if done is not None else None
             st = flight.get(j - (a_ - 1))
             if st is not None and "boxes" not in st:
                 timed("host_halves", host_halves, st)
+                if vote:
+                    start_orientation(st)
+            if vote:
+                st = flight.get(j - (2 * a_ - 1))
+                if st is not None and "det2" in st:
+                    orient_halves(st)
             return res
 
         for batch in batches:

@@ -807,10 +807,13 @@ def db_nas_state_dict(seed: int = 0, with_thresh_branch: bool = True, head_bias:
     return g.sd
 
 
-def pplcnet_state_dict(seed: int = 0, class_num: int = 2, logit_gain: float = 4.0):
+def pplcnet_state_dict(seed: int = 0, class_num: int = 2, logit_gain: float = 4.0, textline_head: bool = False):
     """state_dict of ``PPLCNet(scale=1.0, class_num=...)`` (model/cls/cls_pp_lcnet.py:164-260): conv1, blocks2..6 (the
     LCNet x1.0 table LCNET_CONFIG == NET_CONFIG :54-66), last_conv (512 -> 1280, no bias), fc.  stride_list does not
-    change any shape."""
+    change any shape.
+    ``textline_head=True`` (seed 5, two classes: the text-line orientation classifier of OcrTablePipeline(synthetic_seed=0)): ``fc`` is replaced by
+    the weights of ``data/pplcnet_synth_textline_head.json``, fitted by ``tools/fit_textline_head.py`` on this very backbone's features of the
+    generator's lines, upright and rotated by 180 degrees -- a workload device that memorises those pages' lines, not an orientation classifier."""
     g = _Gen(seed)
 
     def conv_bn(p, cout, cin, k, groups=1, gain=2.0):
@@ -828,6 +831,20 @@ def pplcnet_state_dict(seed: int = 0, class_num: int = 2, logit_gain: float = 4.
             conv_bn(p + ".pw_conv", cout, cin, 1)
     g.conv("last_conv", 1280, 512, 1, 1)
     g.linear("fc", class_num, 1280, scale=logit_gain)
+    if textline_head:
+        import os
+        import torch
+        import json
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "pplcnet_synth_textline_head.json")) as f:
+            z = json.load(f)
+        if (seed, class_num) != (z["seed"], z["class_num"]):
+            raise ValueError(f"the fitted text-line head belongs to pplcnet_state_dict(seed={z['seed']}, class_num={z['class_num']})")
+        # two classes, logit difference d = l0 - l1: class 0 gets +d/2, class 1 -d/2 (float32 values stored exactly as decimal float64)
+        half = np.asarray(z["half"], dtype=np.float32)
+        if half.shape != tuple(g.sd["fc.weight"].shape[1:]):
+            raise ValueError(f"pplcnet_synth_textline_head.json: {half.shape[0]} weights per class, the checkpoint's fc has {g.sd['fc.weight'].shape[1]}")
+        g.sd["fc.weight"] = torch.from_numpy(np.stack([half, -half])).to(g.sd["fc.weight"].dtype)
+        g.sd["fc.bias"] = torch.from_numpy(np.array([z["bias0"], -z["bias0"]], dtype=np.float32)).to(g.sd["fc.bias"].dtype)
     return g.sd
 
 
