@@ -407,6 +407,13 @@ int pt_op_conv2d(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Ci
                  pt_stream stream);
 /* split=1 (BF16X3): d_in/d_res/d_out carry (hi | lo) channel groups, d_w_tiled is [N/64][3*Cin/32][ks*ks][64][32]
  * (K chunks: w_hi for x_hi, w_hi for x_lo, w_lo for x_hi), out_lo_off = channel distance hi -> lo in d_out. */
+/* 1x1 stride-1 bf16 convolution with the epilogues the network launchers use and pt_op_conv2d does not expose (parity tests of the 1x1
+ * kernels): d_out bf16 [B,H,W,out_cstride] or, when d_out_f32 is set, fp32 [B,H,W,out_cstride] (d_out unused); n_valid > 0: only
+ * channels [0, n_valid) are stored; d_res_f32: fp32 residual laid out like d_out_f32 (added before the activation); d_ylimit: device
+ * int, output rows >= *d_ylimit are not computed (the row-limited launches of the Lore patch mosaics). */
+int pt_op_conv1x1_ex(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Cin, const uint16_t* d_w_tiled, const float* d_bias,
+                     int N, uint16_t* d_out, float* d_out_f32, int out_cstride, int n_valid, const float* d_res_f32, int relu,
+                     const int32_t* d_ylimit, pt_stream stream);
 
 /* Fused modulated deformable 3x3 convolution (pad 1, stride 1, dilation 1, one deformable group) + bias (+ ReLU): the operator
  * DCN.forward (model/lore/dcnv2.py:71-86) hands to torchvision.ops.deform_conv2d, sampling rule of

@@ -969,6 +969,17 @@ int pt_op_conv2d(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Ci
   return pt_launch_conv(e, d, reinterpret_cast<hipStream_t>(stream));
 }
 
+int pt_op_conv1x1_ex(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Cin, const uint16_t* d_w_tiled, const float* d_bias,
+                     int N, uint16_t* d_out, float* d_out_f32, int out_cstride, int n_valid, const float* d_res_f32, int relu,
+                     const int32_t* d_ylimit, pt_stream stream) {
+  PT_REQUIRE(e != nullptr, "pt_op_conv1x1_ex: null engine");
+  ConvDesc d;
+  d.in = d_in; d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.w = d_w_tiled; d.bias = d_bias; d.N = N; d.ks = 1; d.stride = 1;
+  d.out = d_out_f32 ? nullptr : d_out; d.out_f32 = d_out_f32; d.out_cstride = out_cstride; d.n_valid = n_valid; d.res_f32 = d_res_f32;
+  d.relu = relu; d.ylimit = d_ylimit;
+  return pt_launch_conv(e, d, reinterpret_cast<hipStream_t>(stream));
+}
+
 int pt_op_stem7x7(pt_engine* e, const uint16_t* d_in, int B, int H, int W, const uint16_t* d_w, const float* d_bias,
                   uint16_t* d_out, int split, pt_stream stream) {
   PT_REQUIRE(e != nullptr, "pt_op_stem7x7: null engine");

@@ -793,10 +793,18 @@ __global__ __launch_bounds__(256, KS == 1 ? 4 : 2) void conv_igemm_kernel(ConvK 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// 1x1 stride-1 layers with a plain epilogue, K staged KG 32-channel chunks at a time.  conv_igemm_kernel<1, 1> hands its 4 x 32 x 64 tile one
+// 1x1 stride-1 layers, K staged KG 32-channel chunks at a time.  conv_igemm_kernel<1, 1> hands its 4 x 32 x 64 tile one
 // 32-channel chunk per barrier pair: 12 KB in flight per workgroup and four MFMAs per wave between two barriers -- a 128 -> 128 layer is four
 // load latencies in a row per tile and ran at 2.2 TB/s.  Here a stage is KG chunks (KG = 4: the whole K of a 128-channel layer is requested at
 // once, one barrier pair per tile); same tile, same chunk order inside the accumulators (bit-identical), same register epilogue.
+// Cin % (32 KG) != 0: the last stage's missing chunks are neither fetched nor multiplied (the products are exactly those of the chunk kernel).
+// GEN: the instance for row-limited or padded launches; the others keep the schedule of a single whole-stage tile (with the walk or the guarded
+// loop in the same instance hipcc sinks the stage's LDS reads to their MFMAs: isa_wait_audit 0.25 -> 0.97).
+// STAGED: the epilogues the register path does not have (fp32 residual, pixel shuffle, arg-max, fused head): the MFMA runs with the pixels as
+// its A operand and the tile leaves through LDS by epilogue_store, as in conv_igemm_kernel<1, 1, 0, 2, false>.
+// Row-limited launches (ConvK.ylimit, reps > 1): workgroup w takes tiles w, w + grid, w + 2 grid, ... and stops at the first one beyond the
+// limit.  The live tiles are the front of the tile order, so they spread over the whole grid (the chunk kernel walks reps CONSECUTIVE tiles:
+// a Lore head's few hundred live tiles went to ~20 workgroups, 16 tiles x 18 chunks each in a row, 141 us per launch).
 // ---------------------------------------------------------------------------------------------------
 template <int KG>
 struct Conv1WideCfg {
@@ -804,9 +812,10 @@ struct Conv1WideCfg {
   static constexpr int IN_BYTES = 128 * PIXB;
   static constexpr int W_BYTES = 64 * PIXB;
   static constexpr int SMEM = IN_BYTES + W_BYTES > 16384 ? IN_BYTES + W_BYTES : 16384;      // (16 KB: the xp_store tiles of the epilogue)
+  static constexpr int SMEM_STAGED = SMEM > 32768 ? SMEM : 32768;                            // (the fp32 [128 pixels][64] tile of epilogue_store)
 };
 
-template <int KG>
+template <int KG, bool STAGED = false, bool GEN = false>
 __global__ __launch_bounds__(256, KG == 4 ? 3 : 4) void conv1x1_wide_kernel(ConvK p) {
   a16_kernel_enter();
   using C = Conv1WideCfg<KG>;
@@ -816,24 +825,36 @@ __global__ __launch_bounds__(256, KG == 4 ? 3 : 4) void conv1x1_wide_kernel(Conv
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int lx = lane & 31, q = lane >> 5;
+  const int nch = p.Cin >> 5;
+  const int nstages = (nch + KG - 1) / KG;
+  const int reps = GEN && p.reps > 1 ? p.reps : 1;
+  for (int rep = 0; rep < reps; ++rep) {
   int L, nt;
-  L = xcd_remap(blockIdx.x, gridDim.x);
-  tile_order(L, p.n_tiles, p.n_group, nt, L);
+  if (reps == 1) {
+    L = xcd_remap(blockIdx.x, gridDim.x);
+    tile_order(L, p.n_tiles, p.n_group, nt, L);
+  } else {
+    L = rep * (int)gridDim.x + (int)blockIdx.x;
+    if (L >= p.total_tiles) break;
+    nt = L % p.n_tiles;
+    L /= p.n_tiles;
+    if (rep) __syncthreads();                      // the previous tile's epilogue has finished with the LDS image
+  }
   const int txi = L % p.tiles_x;
   L /= p.tiles_x;
   const int tyi = L % p.tiles_y;
   const int b = L / p.tiles_y;
   const int oy0 = tyi * 4, ox0 = txi * 32;
-  if (p.xlimit && ox0 >= p.xlimit[b]) return;
+  if (GEN && p.ylimit && oy0 >= *p.ylimit) break;  // uniform over the workgroup; later tiles of the walk are further down
+  if (p.xlimit && ox0 >= p.xlimit[b]) continue;
   if (p.xlimit_rows) {
     int mx = 0;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       if (oy0 + r < p.Ho) mx = max(mx, p.xlimit_rows[oy0 + r]);
-    if (ox0 >= mx) return;
+    if (ox0 >= mx) continue;
   }
-  const int nstages = (p.Cin >> 5) / KG;
-  const bf16_t* wt = p.w + (size_t)nt * (p.Cin >> 5) * (64 * 32);
+  const bf16_t* wt = p.w + (size_t)nt * nch * (64 * 32);
 
   u32x4 rin[2 * KG];
   u32x4 rw[KG];
@@ -847,10 +868,11 @@ __global__ __launch_bounds__(256, KG == 4 ? 3 : 4) void conv1x1_wide_kernel(Conv
   auto prefetch = [&](int stage) {
 #pragma unroll
     for (int g = 0; g < KG; ++g) {
+      const bool live = stage * KG + g < nch;      // uniform; false only in the last stage of a Cin % (32 KG) != 0 layer
       int cc = (stage * KG + g) << 5;
       const bf16_t* sp = p.in;
       int sc = p.Cin;
-      if (p.nseg > 1) {      // K over a concatenation of tensors: logical channel -> (segment, channel inside it); uniform over the workgroup
+      if (p.nseg > 1 && live) {      // K over a concatenation of tensors: logical channel -> (segment, channel inside it); uniform over the workgroup
         sc = p.segc0;
         if (cc >= sc) { cc -= sc; sp = p.in1; sc = p.segc1;
           if (cc >= sc) { cc -= sc; sp = p.in2; sc = p.segc2;
@@ -858,14 +880,18 @@ __global__ __launch_bounds__(256, KG == 4 ? 3 : 4) void conv1x1_wide_kernel(Conv
       }
       const bf16_t* src = sp + ((size_t)b * p.H * p.W) * sc + cc + part * 8;
       u32x4 v0 = {0u, 0u, 0u, 0u}, v1 = {0u, 0u, 0u, 0u};
-      if (in0) v0 = *reinterpret_cast<const u32x4*>(src + ((size_t)gy0 * p.W + gx) * sc);
-      if (in1) v1 = *reinterpret_cast<const u32x4*>(src + ((size_t)(gy0 + 2) * p.W + gx) * sc);
+      if (live && in0) v0 = *reinterpret_cast<const u32x4*>(src + ((size_t)gy0 * p.W + gx) * sc);
+      if (live && in1) v1 = *reinterpret_cast<const u32x4*>(src + ((size_t)(gy0 + 2) * p.W + gx) * sc);
       rin[2 * g] = v0;
       rin[2 * g + 1] = v1;
     }
     const bf16_t* wc = wt + (size_t)stage * KG * (64 * 32);
 #pragma unroll
-    for (int g = 0; g < KG; ++g) rw[g] = *reinterpret_cast<const u32x4*>(wc + (g * 256 + pix0 * 4 + part) * 8);
+    for (int g = 0; g < KG; ++g) {
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (stage * KG + g < nch) v = *reinterpret_cast<const u32x4*>(wc + (g * 256 + pix0 * 4 + part) * 8);
+      rw[g] = v;
+    }
   };
   auto commit = [&]() {
 #pragma unroll
@@ -890,14 +916,42 @@ __global__ __launch_bounds__(256, KG == 4 ? 3 : 4) void conv1x1_wide_kernel(Conv
     commit();
     __syncthreads();
     if (st + 1 < nstages) prefetch(st + 1);
-#pragma unroll
-    for (int k = 0; k < 2 * KG; ++k) {
+    auto kstep = [&](int k) {
       const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(b_base + k * 32);
       const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(b_base + 32 * C::PIXB + k * 32);
       const bf16x8 a = *reinterpret_cast<const bf16x8*>(a_base + k * 32);
-      acc[0] = mma16<false>(b0, a, acc[0]);      // D = [channel][pixel]
-      acc[1] = mma16<false>(b1, a, acc[1]);
+      if (STAGED) {
+        acc[0] = mma16<false>(a, b0, acc[0]);      // D = [pixel][channel]
+        acc[1] = mma16<false>(a, b1, acc[1]);
+      } else {
+        acc[0] = mma16<false>(b0, a, acc[0]);      // D = [channel][pixel]
+        acc[1] = mma16<false>(b1, a, acc[1]);
+      }
+    };
+    const int live = nch - st * KG;      // chunks of this stage that exist (>= KG but in the padded last stage)
+    if (!GEN || live >= KG) {
+#pragma unroll
+      for (int k = 0; k < 2 * KG; ++k) kstep(k);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 2 * KG; ++k)
+        if ((k >> 1) < live) kstep(k);      // uniform
     }
+  }
+  if (STAGED) {
+    // ---- epilogue through LDS (fp32 [pixel][64]), conv_igemm_kernel's ----
+    __syncthreads();
+    float* stage = reinterpret_cast<float*>(smem);
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int tx = (r & 3) + 8 * (r >> 2) + 4 * q;
+        stage[(wave * 32 + tx) * 64 + n * 32 + lx] = acc[n][r];
+      }
+    __syncthreads();
+    epilogue_store<4, 32>(p, stage, tid, b, oy0, ox0, nt * 64);
+    continue;
   }
   const DirectBias bs = direct_bias<2>(p, nt * 64, q);
   char* xp = nullptr;
@@ -906,6 +960,7 @@ __global__ __launch_bounds__(256, KG == 4 ? 3 : 4) void conv1x1_wide_kernel(Conv
     xp = smem + wave * 4096;
   }
   epilogue_direct_row<2>(p, acc, bs, b, oy0 + wave, ox0, lx, nt * 64, q, xp);
+  }   // rep
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3107,19 +3162,27 @@ static void launch_direct(const ConvK& k, unsigned nblk, hipStream_t s) {
   hipLaunchKernelGGL((conv_igemm_kernel<KS, STRIDE, 0, NHALF, true>), dim3(nblk), dim3(256), C::SMEM, s, k);
 }
 
-static bool conv1_wide() {      // PT_CONV1_WIDE=0: conv_igemm_kernel<1, 1> (one 32-channel chunk per stage) for every plain 1x1 layer (A/B switch, read per call)
+static bool conv1_wide() {      // PT_CONV1_WIDE=0: conv_igemm_kernel<1, 1> (one 32-channel chunk per stage) for every 1x1 stride-1 layer (A/B switch, read per call)
   const char* ev = getenv("PT_CONV1_WIDE");
   return !(ev && ev[0] == '0');
 }
-template <int KG>
-static void launch_wide1(const ConvK& k, unsigned nblk, hipStream_t s) {
+template <int KG, bool STAGED, bool GEN>
+static void launch_wide1_(const ConvK& k, unsigned nblk, hipStream_t s) {
   using C = Conv1WideCfg<KG>;
+  constexpr int smem = STAGED ? C::SMEM_STAGED : C::SMEM;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_wide_kernel<KG>), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_wide_kernel<KG, STAGED, GEN>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
     attr_done = true;
   }
-  hipLaunchKernelGGL((conv1x1_wide_kernel<KG>), dim3(nblk), dim3(256), C::SMEM, s, k);
+  hipLaunchKernelGGL((conv1x1_wide_kernel<KG, STAGED, GEN>), dim3(nblk), dim3(256), smem, s, k);
+}
+// KG = 4 where Cin is a multiple of 128, else 2 (zero-padded last stage where Cin is an odd number of 32-channel chunks)
+template <bool STAGED>
+static void launch_wide1(const ConvK& k, unsigned nblk, hipStream_t s) {
+  const bool kg4 = k.Cin % 128 == 0;
+  if (k.ylimit || k.Cin % 64 != 0) kg4 ? launch_wide1_<4, STAGED, true>(k, nblk, s) : launch_wide1_<2, STAGED, true>(k, nblk, s);
+  else kg4 ? launch_wide1_<4, STAGED, false>(k, nblk, s) : launch_wide1_<2, STAGED, false>(k, nblk, s);
 }
 
 template <int KS, int STRIDE, int GEOM = 0>
@@ -3159,14 +3222,15 @@ static int launch_cfg(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
     const bool plain = direct1 && GEOM == 0 && !k.split && !k.pool && !k.head_w && !k.argmax_part && !k.res_f32 && !k.shuffle_cout;
     const bool narrow = KS == 3 && STRIDE == 1 && GEOM == 0 && k.n_valid > 0 && k.n_valid <= 32 && k.N == 64 && !k.split && !k.pool &&
                         !k.head_w && !k.argmax_part;      // <= 32 real output channels: half-width variant
+    // (Cin = 32 stays on the chunk kernel: one chunk is one stage either way, and the padded 2-chunk stage measured slower, 0.31 -> 0.37 ms @256x256)
+    const bool wide1 = KS == 1 && STRIDE == 1 && GEOM == 0 && !k.split && !k.pool && k.Cin >= 64 && conv1_wide();
     if (narrow && plain)
       launch_direct<3, 1, 1>(k, (unsigned)nblk, s);
     else if (narrow)
       launch_half(k, (unsigned)nblk, s);
-    else if (plain && KS == 1 && STRIDE == 1 && !k.ylimit && k.Cin % 128 == 0 && conv1_wide())
-      launch_wide1<4>(k, (unsigned)nblk, s);
-    else if (plain && KS == 1 && STRIDE == 1 && !k.ylimit && k.Cin % 64 == 0 && conv1_wide())
-      launch_wide1<2>(k, (unsigned)nblk, s);
+    // every 1x1 stride-1 layer but the split / pooled ones: row-limited, Cin % 64 != 0 and the staged epilogues included
+    else if (wide1)
+      plain ? launch_wide1<false>(k, (unsigned)nblk, s) : launch_wide1<true>(k, (unsigned)nblk, s);
     else if (plain && KS == 1 && STRIDE == 1)
       launch_direct<1, 1, 2>(k, (unsigned)nblk, s);
     else if (plain && KS == 3 && STRIDE == 2)

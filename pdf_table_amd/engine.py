@@ -664,6 +664,21 @@ class HipEngine:
                                       int(relu), int(split), out.shape[-1] // 2, self._stream()), "pt_op_conv2d")      # relu: bool, or the epilogue's activation code (0 none, 1 ReLU, 2 hardswish)
         return out
 
+    def op_conv1x1_ex(self, x: torch.Tensor, w_tiled: torch.Tensor, bias: torch.Tensor, relu: int = 0, out_f32: bool = False,
+                      n_valid: int = 0, res_f32: Optional[torch.Tensor] = None, ylimit: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """1x1 stride-1 conv with the network launchers' extra epilogues (pt_op_conv1x1_ex): fp32 output, n_valid stored channels, fp32
+        residual, a device row limit (int32 [1]: output rows >= ylimit[0] are not computed and keep what `out` held, zeros here)."""
+        self._chk(x, self.act_dtype, "x")
+        self._chk(bias, torch.float32, "bias")
+        B, H, W, Cin = x.shape
+        N = bias.numel()
+        cs = n_valid or N
+        out = torch.zeros((B, H, W, cs), dtype=torch.float32 if out_f32 else self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_conv1x1_ex(self._h, _ptr(x), B, H, W, Cin, _ptr(w_tiled), _ptr(bias), N, None if out_f32 else _ptr(out),
+                                          _ptr(out) if out_f32 else None, cs, n_valid, _ptr(res_f32), int(relu), _ptr(ylimit),
+                                          self._stream()), "pt_op_conv1x1_ex")
+        return out
+
     def op_dcn(self, x: torch.Tensor, om: torch.Tensor, w_tiled: torch.Tensor, bias: torch.Tensor, relu: bool = True, split: int = 0) -> torch.Tensor:
         """Fused modulated deformable 3x3 convolution (lore/dcnv2.py:71-86) as a single operator.  x bf16 [B,H,W,C] ([hi | lo] when split),
         om fp32 [B,H,W,32] (18 offsets, 9 mask logits, 5 unused), w_tiled = the [N, 9C, 1, 1] weight tiled as a 1x1 conv, bias fp32 [N]."""
