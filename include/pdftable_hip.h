@@ -456,7 +456,7 @@ int pt_op_maxpool(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C
                   int split, pt_stream stream);
 /* AveragePool k x k, stride k, no padding (H and W divisible by k) */
 int pt_op_avgpool(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C, int k, uint16_t* d_out, int split, pt_stream stream);
-/* GlobalAveragePool: [B, HW, C] -> bf16 [B, C]; d_scratch: pt_op_chan_mean_scratch_floats(B, C) floats */
+/* GlobalAveragePool: [B, HW, C] -> bf16 [B, C] (B, HW > 0; C a multiple of 8, <= 2048); d_scratch: pt_op_chan_mean_scratch_floats(B, C) floats */
 int pt_op_chan_mean(pt_engine* e, const uint16_t* d_in, int B, int HW, int C, float* d_scratch, uint16_t* d_mean, int split, pt_stream stream);
 int pt_op_chan_mean_scratch_floats(int B, int C);
 /* x [B, HW, C] * gate [B, C] (the Mul of a squeeze-and-excitation block) */

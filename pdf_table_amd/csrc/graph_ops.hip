@@ -298,6 +298,9 @@ int pt_op_avgpool(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C
 
 int pt_op_chan_mean(pt_engine* e, const uint16_t* d_in, int B, int HW, int C, float* d_scratch, uint16_t* d_mean, int split, pt_stream stream) {
   PT_REQUIRE(e && d_in && d_scratch && d_mean, "pt_op_chan_mean: null pointer");
+  // an empty map has no mean: the second level would store 0 / 0 = NaN
+  PT_REQUIRE(B > 0 && HW > 0 && C > 0 && C % 8 == 0 && C <= 2048, "pt_op_chan_mean: B=%d HW=%d C=%d unsupported (B, HW > 0; C a multiple of 8, <= 2048)",
+             B, HW, C);
   return pt_launch_chan_mean(d_in, B, HW, C, split ? 1 : 0, d_scratch, d_mean, B, reinterpret_cast<hipStream_t>(stream));
 }
 
