@@ -589,6 +589,31 @@ int pt_tsr_mtl_structure(pt_engine* e, const float* d_f3, int n, int hw, float* 
 int pt_tsr_mtl_cells(pt_engine* e, int total, int32_t* d_cell_ids, float* d_cell_prob, float* d_cell_logits, int32_t* h_steps,
                      int force_redecode, pt_stream stream);
 
+
+/* ---- image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-491) ----------------
+ * Engine-free: these read and write uint8 RGB pages [n, h, w, 3] only (csrc/page_pre.hip, compiled once).
+ * pt_page_line_mask: the deskew's horizontal line mask of n same-shape pages in one launch -- 255 - gray (cv2's fixed-point
+ *   BGR2GRAY on the reference's BGR = the same weights on R, G, B here), adaptiveThreshold(GAUSSIAN_C, BINARY, 15, -2), then erode
+ *   and dilate with a (w / 40) x 1 rectangle.  d_bits uint64 [n, h, (w + 63) / 64]: bit b of word q = column 64 q + b (1 = line pixel),
+ *   bits past the page end 0.  w >= 40 (cv2 rejects a zero-width element).
+ * pt_page_line_angles (HOST): RETR_EXTERNAL contours of those masks; per page, get_line_angle of every contour wider than min_width
+ *   (the reference's diff_angle, 400), in cv2's contour order: h_angles double [n, cap], h_counts int32 [n].  n_threads in 1 .. 16.
+ * pt_page_warp_cubic: cv2.warpAffine(INTER_CUBIC, BORDER_REPLICATE) at the page's own size.  Output page j of d_out [m, h, w, 3] is page
+ *   d_idx[j] of d_pages warped by d_minv[j] (double [m, 6]: the INVERSE map, as warpAffine computes it); an index outside 0 .. n - 1
+ *   leaves output j unwritten.
+ * pt_page_quarter_turn: cv2.rotate with cv2's codes; d_out [n, w, h, 3] for the 90-degree turns, [n, h, w, 3] for ROTATE_180.
+ * pt_page_pre_tables: the host tables the kernels use (15 blur taps, sum 256; 1024 x 16 bicubic weights), for tests. */
+#define PT_ROTATE_90_CLOCKWISE 0
+#define PT_ROTATE_180 1
+#define PT_ROTATE_90_COUNTERCLOCKWISE 2
+int pt_page_line_mask(const uint8_t* d_pages, int n, int h, int w, uint64_t* d_bits, pt_stream stream);
+int pt_page_line_angles(const uint64_t* h_bits, int n, int h, int w, int min_width, int n_threads, double* h_angles, int cap,
+                        int32_t* h_counts);
+int pt_page_warp_cubic(const uint8_t* d_pages, int n, int h, int w, const double* d_minv, const int32_t* d_idx, int m, uint8_t* d_out,
+                       pt_stream stream);
+int pt_page_quarter_turn(const uint8_t* d_pages, int n, int h, int w, int code, uint8_t* d_out, pt_stream stream);
+int pt_page_pre_tables(int32_t* h_blur_taps, int16_t* h_cubic);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,9 @@ HIP_SOURCES = ["conv_igemm.hip", "det_kernels.hip", "db_model.hip", "rec_kernels
                "graph_ops.hip", "cvit_model.hip", "mtl_model.hip", "mtl_decoder.hip", "c_api.hip"]
 # compiled ONCE: host-only post-processing and the format-independent corner of the ABI
 CPP_SOURCES = ["db_post.cpp", "api_common.cpp"]
+# HIP compiled ONCE (as namespace pt_bf16): kernels on uint8 pages only, no activation format; their entry points take no engine, so the
+# generated dispatchers call pt_bf16::api only
+ONCE_HIP_SOURCES = ["page_pre.hip"]
 HEADERS = ["common.h", "act16.h", os.path.join("..", "..", "include", "pdftable_hip.h")]
 # Every HIP translation unit is compiled once per 16-bit activation format (csrc/act16.h): namespace pt_bf16, and namespace pt_f16 with -DPT_ACT_F16=1
 FORMATS = [("bf16", []), ("f16", ["-DPT_ACT_F16=1"])]
@@ -38,7 +41,7 @@ def _hipcc() -> str:
 
 
 def _sources():
-    return [s for s in HIP_SOURCES + CPP_SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    return [s for s in HIP_SOURCES + ONCE_HIP_SOURCES + CPP_SOURCES if os.path.exists(os.path.join(CSRC, s))]
 
 
 def _digest() -> str:
@@ -60,7 +63,7 @@ def lint_kernel_enter() -> None:
     language enforces it, so the build does: per translation unit, as many a16_kernel_enter() calls as __global__ definitions."""
     import re
     bad = []
-    for src in HIP_SOURCES:
+    for src in HIP_SOURCES + ONCE_HIP_SOURCES:
         path = os.path.join(CSRC, src)
         if not os.path.exists(path):
             continue
@@ -147,7 +150,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     jobs = []
     for src in _sources():
         hip = src.endswith(".hip")
-        for fmt, defs in (FORMATS if hip else [("", [])]):
+        for fmt, defs in (FORMATS if hip and src not in ONCE_HIP_SOURCES else [("", [])]):
             obj = os.path.join(objdir, os.path.splitext(src)[0] + ("_" + fmt if fmt else "") + ".o")
             jobs.append((src + (" [" + fmt + "]" if fmt else ""), [hipcc] + FLAGS + defs + (["-x", "hip"] if hip else []) + ["-c", os.path.join(CSRC, src), "-o", obj]))
             objs.append(obj)

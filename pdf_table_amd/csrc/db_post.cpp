@@ -646,3 +646,103 @@ int pt_hard_nms(const double* boxes, const int64_t* order, const int64_t* group_
 }
 
 }  // extern "C"
+
+// ---- page deskew: the horizontal-line angles of one page's opened line mask ---------------------------------------------------------
+// PdfImageProcessor.find_lines_angle (utils/table/image_processing.py:161-266) after the device opening (page_pre.hip): findContours
+// (RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), and for every contour whose boundingRect is wider than min_width, get_line_angle (:308-336).
+// RETR_EXTERNAL is OpenCV's scan mode 0: hole borders are never followed, and an outer border start is skipped when the last border pixel
+// met on the row (lnbd) is marked positive -- the component then lies inside a hole of an already traced one.  Only the horizontal pass is
+// built: the reference computes the vertical one as well but only logs its angle.
+namespace {
+
+static void find_external_contours(int8_t* img, int h, int w, std::vector<std::vector<Pt>>& contours) {
+  const int step = w + 2;
+  for (int y = 1; y <= h; ++y) {
+    int8_t* row = img + (size_t)y * step;
+    int prev = 0;
+    int lnbd = 0;                 // x of the last border pixel met on this row; the zero frame to begin with
+    for (int x = 1; x <= w; ++x) {
+      const int p = row[x];
+      if (p == prev) continue;
+      if (prev == 0 && p == 1) {  // outer border start
+        if (row[lnbd] <= 0) {
+          std::vector<Pt> c;
+          fetch_contour(img, step, x, y, false, c);
+          for (auto& q : c) { q.x -= 1; q.y -= 1; }
+          contours.push_back(std::move(c));
+          lnbd = x;
+        }
+      } else if (p == 0 && prev >= 1 && (prev & -2)) {  // hole border start: not followed; its left pixel is the last border met
+        lnbd = x - 1;
+      }
+      prev = row[x];
+      if (prev & -2) lnbd = x;
+    }
+  }
+  std::reverse(contours.begin(), contours.end());
+}
+
+// get_line_angle: the contour's points sorted (stable) by x when their extent is wider than tall, else by y; calculate_angle (:281-306)
+// of the first and the last: 90 if dx == 0, 0 if dy == 0, else arctan(dy / dx) * 57.29577
+static double line_angle(const std::vector<Pt>& c) {
+  int x0 = c[0].x, x1 = c[0].x, y0 = c[0].y, y1 = c[0].y;
+  for (const Pt& q : c) { x0 = std::min(x0, q.x); x1 = std::max(x1, q.x); y0 = std::min(y0, q.y); y1 = std::max(y1, q.y); }
+  std::vector<Pt> s(c);
+  if (x1 - x0 > y1 - y0) std::stable_sort(s.begin(), s.end(), [](const Pt& a, const Pt& b) { return a.x < b.x; });
+  else std::stable_sort(s.begin(), s.end(), [](const Pt& a, const Pt& b) { return a.y < b.y; });
+  const double dx = (double)s.back().x - s.front().x, dy = (double)s.back().y - s.front().y;
+  if (dx == 0) return 90.0;
+  if (dy == 0) return 0.0;
+  return atan(dy / dx) * 57.29577;
+}
+
+static int page_line_angles(const uint64_t* bits, int h, int w, int min_width, double* angles, int cap, int* count) {
+  const int nw = (w + 63) / 64, step = w + 2;
+  std::vector<int8_t> img((size_t)(h + 2) * step, 0);
+  for (int y = 0; y < h; ++y) {
+    int8_t* row = img.data() + (size_t)(y + 1) * step + 1;
+    for (int q = 0; q < nw; ++q) {
+      uint64_t b = bits[(size_t)y * nw + q];
+      while (b) {
+        const int x = q * 64 + __builtin_ctzll(b);
+        if (x < w) row[x] = 1;
+        b &= b - 1;
+      }
+    }
+  }
+  std::vector<std::vector<Pt>> contours;
+  find_external_contours(img.data(), h, w, contours);
+  int k = 0;
+  for (const auto& c : contours) {
+    int x0 = c[0].x, x1 = c[0].x;
+    for (const Pt& q : c) { x0 = std::min(x0, q.x); x1 = std::max(x1, q.x); }
+    if (x1 - x0 + 1 <= min_width) continue;   // boundingRect width > diff_angle
+    if (k >= cap) {
+      pt_set_error("pt_page_line_angles: more than cap = %d lines on a page", cap);
+      return PT_ERR_INVALID;
+    }
+    angles[k++] = line_angle(c);
+  }
+  *count = k;
+  return PT_OK;
+}
+
+}  // namespace
+
+// pt_page_line_angles (page_pre.hip) -- not extern "C": the exported symbol is the generated dispatcher
+int page_line_angles_batch(const uint64_t* h_bits, int n, int h, int w, int min_width, int n_threads, double* h_angles, int cap,
+                           int32_t* h_counts) {
+  if (!h_bits || !h_angles || !h_counts || n <= 0 || h <= 0 || w <= 0 || cap <= 0 || min_width < 0 || n_threads < 1 || n_threads > 16) {
+    pt_set_error("pt_page_line_angles: bad arguments");
+    return PT_ERR_INVALID;
+  }
+  const size_t words = (size_t)h * ((w + 63) / 64);
+  std::atomic<int> bad(0);
+  parallel_pages(n, n_threads, [&](int i) {
+    int cnt = 0;
+    const int rc = page_line_angles(h_bits + (size_t)i * words, h, w, min_width, h_angles + (size_t)i * cap, cap, &cnt);
+    h_counts[i] = cnt;
+    if (rc != PT_OK) bad.store(rc);
+  });
+  return bad.load();
+}

@@ -325,6 +325,40 @@ class HipEngine:
                                                self._stream()), "pt_det_box_scores")
         return scores
 
+    # ---- image-page straightening (csrc/page_pre.hip) ---------------------------------------------
+    def page_line_mask(self, pages: torch.Tensor) -> torch.Tensor:
+        """uint8 RGB [n, h, w, 3] -> the deskew's opened horizontal-line mask, bit-packed: int64 [n, h, (w + 63) // 64] (bit b of word q =
+        column 64 q + b)"""
+        self._chk(pages, torch.uint8, "pages")
+        n, h, w, _ = pages.shape
+        bits = torch.empty((n, h, (w + 63) // 64), dtype=torch.int64, device=self._tdev)
+        L.check(self.lib.pt_page_line_mask(_ptr(pages), n, h, w, _ptr(bits), self._stream()), "pt_page_line_mask")
+        return bits
+
+    def page_warp_cubic(self, pages: torch.Tensor, minv: np.ndarray, idx: Sequence[int]) -> torch.Tensor:
+        """cv2.warpAffine(INTER_CUBIC, BORDER_REPLICATE) of pages[idx[j]] by the INVERSE map minv[j] (float64 [m, 6]) -> uint8 [m, h, w, 3]"""
+        self._chk(pages, torch.uint8, "pages")
+        n, h, w, _ = pages.shape
+        mi = np.ascontiguousarray(minv, dtype=np.float64).reshape(-1, 6)
+        ix = np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+        assert len(mi) == len(ix) and len(ix) and ((ix >= 0) & (ix < n)).all(), "page_warp_cubic: bad page indices"
+        out = torch.empty((len(ix), h, w, 3), dtype=torch.uint8, device=self._tdev)
+        d_m, d_i = _upload(mi, self._tdev), _upload(ix, self._tdev)
+        L.check(self.lib.pt_page_warp_cubic(_ptr(pages), n, h, w, _ptr(d_m), _ptr(d_i), len(ix), _ptr(out), self._stream()),
+                "pt_page_warp_cubic")
+        d_m.record_stream(torch.cuda.current_stream(self._tdev))
+        d_i.record_stream(torch.cuda.current_stream(self._tdev))
+        return out
+
+    def page_quarter_turn(self, pages: torch.Tensor, code: int) -> torch.Tensor:
+        """cv2.rotate(page, code) of every page: L.PT_ROTATE_90_CLOCKWISE / _180 / _90_COUNTERCLOCKWISE"""
+        self._chk(pages, torch.uint8, "pages")
+        n, h, w, _ = pages.shape
+        shape = (n, h, w, 3) if code == L.PT_ROTATE_180 else (n, w, h, 3)
+        out = torch.empty(shape, dtype=torch.uint8, device=self._tdev)
+        L.check(self.lib.pt_page_quarter_turn(_ptr(pages), n, h, w, int(code), _ptr(out), self._stream()), "pt_page_quarter_turn")
+        return out
+
     # ---- image classification (PP-LCNet) ------------------------------------------------------------
     def _cls_batch(self, images: Sequence[np.ndarray]):
         """RGB uint8 images of any sizes -> (flat device bytes, device pt_cls_image records, max_h, max_w)"""
@@ -956,3 +990,28 @@ def db_finalize(boxes: np.ndarray, scores: np.ndarray, net_hw, dest_hw, box_thre
                                int(dest_hw[0]), int(dest_hw[1]), int(post_flavour), out.ctypes.data_as(C.c_void_p),
                                osc.ctypes.data_as(C.c_void_p), max(nb, 1), C.byref(n)), "pt_db_finalize")
     return out[:n.value].copy(), osc[:n.value].copy()
+
+
+def page_line_angles(bits: np.ndarray, w: int, min_width: int = 400, n_threads: int = 16) -> list:
+    """bit-packed line masks int64 / uint64 [n, h, (w + 63) // 64] (HipEngine.page_line_mask) -> per page a float64 array of the
+    get_line_angle values of every RETR_EXTERNAL contour wider than min_width, in cv2's contour order; pages run on n_threads (<= 16)"""
+    lib = L.load()
+    b = np.ascontiguousarray(bits).view(np.uint64)
+    n, h, nw = b.shape
+    assert nw == (w + 63) // 64
+    # external contours are disjoint: at most one per two rows in every 401-column span wider than min_width
+    cap = ((h + 1) // 2) * (w // (min_width + 1) + 1) + 1
+    angles = np.empty((n, cap), dtype=np.float64)
+    counts = np.zeros((n,), dtype=np.int32)
+    L.check(lib.pt_page_line_angles(b.ctypes.data_as(C.c_void_p), n, h, w, int(min_width), max(1, min(16, int(n_threads))),
+                                    angles.ctypes.data_as(C.c_void_p), cap, counts.ctypes.data_as(C.c_void_p)), "pt_page_line_angles")
+    return [angles[i, :counts[i]].copy() for i in range(n)]
+
+
+def page_pre_tables():
+    """(the 15 fixed-point blur taps int32, the bicubic weight table int16 [1024, 16]) the page kernels use"""
+    lib = L.load()
+    taps = np.zeros((15,), dtype=np.int32)
+    cub = np.zeros((1024, 16), dtype=np.int16)
+    L.check(lib.pt_page_pre_tables(taps.ctypes.data_as(C.c_void_p), cub.ctypes.data_as(C.c_void_p)), "pt_page_pre_tables")
+    return taps, cub

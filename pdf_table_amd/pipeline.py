@@ -28,6 +28,7 @@ import torch
 from .streams import shared_stream
 
 from .det_stage import DetConfig, DetStage, sort_boxes_reading_order
+from . import lib as L
 from .engine import HipEngine
 from .ocr_detection_task import OcrDetectionTask, _read_image
 from .layout_stage import layout_tables
@@ -52,6 +53,11 @@ class PageResult:
     text_upright: Optional[bool] = None          # text_line_orientation's vote (ocr_system_task.py:395-439); None = not run
     rotated_180: bool = False                    # the page was voted upside-down and rotated before the stages ran (:471-478)
     text_line_orientation: Optional[list] = None  # per detected line: {"class_ids", "scores", "label_names"}
+    skew_angle: Optional[float] = None           # deskew=True: the measured small angle (metric["rotate_small"]; 0 = no line), None = not run
+    rotated_90: bool = False                     # sideways_check=True: the page was turned by ROTATE_90_COUNTERCLOCKWISE and detected again
+    image_shape: Optional[tuple] = None          # the shape of the page every result refers to (after straightening)
+    page_orientation: Optional[dict] = None      # page_orientation=True: rotate_image_v2's metric {"angle", "score"[, "angle2", "score2"]}
+    table_attribute: Optional[dict] = None       # table_attribute=True: {"attributes", "output"} of the page (first orientation pass)
 
 
 class OcrTablePipeline:
@@ -63,8 +69,21 @@ class OcrTablePipeline:
                  layout_task_path: Optional[str] = None, text_orientation: bool = False,
                  orientation_task_path: Optional[str] = None, table_html: bool = False, overlap_rec: bool = True,
                  rotate_upside_down: bool = True, aux_layout: bool = False, tsr_on_aux: bool = False, lookahead: int = 1,
-                 precision: str = "bf16", layout_precision: Optional[str] = None, **kwargs):
+                 precision: str = "bf16", layout_precision: Optional[str] = None, deskew: bool = False,
+                 sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
+                 table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
+                 **kwargs):
         self.engine = HipEngine(device)
+        # image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-468; page_pre_stage.py):
+        # deskew=True warps a page back by the angle of its long horizontal rules; page_orientation=True classifies the page with
+        # text_image_orientation (PP-LCNet, slot 1) and turns it by 90 / 180 / 270 degrees (table_attribute=True: slot 2 on the same
+        # pass, reported only); sideways_check=True turns a page whose detected boxes
+        # are, in sum, taller than wide by 90 degrees counter-clockwise and detects it again.  page_preprocess=True switches on both.
+        # Every result is then in the straightened page's pixels, as in the reference
+        self.deskew = bool(deskew or page_preprocess)
+        self.sideways_check = bool(sideways_check or page_preprocess)
+        self.page_orientation_task = self.table_attribute_task = None
+        self._page_pre = None
         # arithmetic of every stage on this engine: "bf16" (BASELINE.json's), "fp16" (the reference's own default precision,
         # base_infer_task.py:56-57: the engine's single-pass IEEE-half mode, same speed, 8x finer rounding) or "fp32" (three-pass pair mode)
         _p = str(precision).lower()
@@ -119,6 +138,19 @@ class OcrTablePipeline:
             if orientation_task_path:
                 ok["task_path"] = orientation_task_path
             self.orientation_task = ClsImagePulcTask(task_type="textline_orientation", engine=self.engine, slot=0, **ok)
+        if page_orientation or page_preprocess or table_attribute:
+            from .cls_image_pulc_task import ClsImagePulcTask
+            for on, task, slot, seed, path, attr in ((page_orientation or page_preprocess, "text_image_orientation", 1, 6,
+                                                      page_orientation_task_path, "page_orientation_task"),
+                                                     (table_attribute, "table_attribute", 2, 7, table_attribute_task_path, "table_attribute_task")):
+                if not on:
+                    continue
+                ck = dict(kwargs)
+                if synthetic_seed is not None:
+                    ck["synthetic_seed"] = synthetic_seed + seed
+                if path:
+                    ck["task_path"] = path
+                setattr(self, attr, ClsImagePulcTask(task_type=task, engine=self.engine, slot=slot, **ck))
         self.table_structure_task = None
         if table_structure:
             tk = dict(kwargs)
@@ -142,6 +174,8 @@ class OcrTablePipeline:
         self.engine, self.overlap_rec, self.rotate_upside_down, self._rec_stream = engine, overlap_rec, True, None
         self.table_html, self.orientation_task, self.aux_layout, self.tsr_on_aux = table_html, None, aux_layout, tsr_on_aux
         self.lookahead = lookahead
+        self.deskew, self.sideways_check, self._page_pre = False, False, None
+        self.page_orientation_task = self.table_attribute_task = None
         self.text_detector = types.SimpleNamespace(_stage=det_stage)
         self.text_recognizer = types.SimpleNamespace(_stage=rec_stage)
         self.layout_task = None if layout_stage is None else types.SimpleNamespace(_stage=layout_stage, detect_pages=layout_stage)
@@ -159,12 +193,25 @@ class OcrTablePipeline:
         layout stage would deliver).  Returns one PageResult per page, plus ``self.metric``."""
         if self.table_structure_task is not None and table_boxes is None and self.layout_task is None:
             raise ValueError("table_structure=True needs layout=True or predict(table_boxes=...)")
+        straighten = self._straightening()
+        if straighten and table_boxes is not None:
+            raise ValueError("predict(table_boxes=...) cannot follow a deskew or a quarter turn of the page: build the pipeline without "
+                             "deskew / page_orientation / table_attribute / sideways_check / page_preprocess, or let the layout stage "
+                             "find the tables")
         t0 = time.time()
         imgs = [_read_image(p) for p in pages]
         results: List[Optional[PageResult]] = [None] * len(imgs)
+        skew = [None] * len(imgs)
+        turned = [False] * len(imgs)
+        pre_boxes: Dict[int, np.ndarray] = {}
+        dev_pages = None
+        page_ori = page_attr = [None] * len(imgs)
+        if straighten:
+            # device pages from here on: uploaded once per input shape, regrouped on the device
+            dev_pages, skew, page_ori, page_attr, turned, pre_boxes = self._straighten_pages(imgs)
         groups: Dict[tuple, List[int]] = {}
-        for i, im in enumerate(imgs):
-            groups.setdefault(im.shape, []).append(i)
+        for i, im in enumerate(imgs if dev_pages is None else dev_pages):
+            groups.setdefault(tuple(im.shape), []).append(i)
         t_det = t_rec = t_tsr = 0.0
         # opt-in (PT_PREDICT_CHUNK=n or self.predict_chunk = n; default 0 = off): a group of >= 2 n equally sized pages goes through
         # predict_stream() in chunks of n, so that the host halves of one chunk (contours, unclip, NMS, CTC collapse, result shaping) run
@@ -174,7 +221,7 @@ class OcrTablePipeline:
         # eat what the overlap gives, which is why it is off by default and predict_stream() is the throughput API.
         chunk = int(os.environ.get("PT_PREDICT_CHUNK", str(getattr(self, "predict_chunk", 0))))
         streamed = {}
-        if chunk > 0 and self.orientation_task is None:
+        if chunk > 0 and self.orientation_task is None and not straighten:
             for shape, idxs in groups.items():
                 if len(idxs) < 2 * chunk:
                     continue
@@ -189,7 +236,10 @@ class OcrTablePipeline:
         for shape, idxs in groups.items():
             if shape in streamed:
                 continue
-            batch = torch.from_numpy(np.stack([imgs[i] for i in idxs])).to(self.engine._tdev)
+            if dev_pages is None:
+                batch = torch.from_numpy(np.stack([imgs[i] for i in idxs])).to(self.engine._tdev)
+            else:
+                batch = torch.stack([dev_pages[i] for i in idxs])
             a = time.time()
             stage: DetStage = self.text_detector._stage
 
@@ -198,7 +248,8 @@ class OcrTablePipeline:
                 return [sort_boxes_reading_order(b) for b in stage.boxes(prob, bitmap, shape[:2], ev)]
 
             with stage_range("text_detection"):
-                boxes = detect(batch)
+                # pages the sideways check detected already (detection looks at one page at a time: same boxes in any batch)
+                boxes = [pre_boxes[i] for i in idxs] if all(i in pre_boxes for i in idxs) else detect(batch)
             ori = None
             rotated = [False] * len(idxs)
             if self.orientation_task is not None:
@@ -273,7 +324,8 @@ class OcrTablePipeline:
                 # bbox = OcrCommonUtils.order_point(det_result[j]) (ocr_system_task.py:311-320), what OcrCell.parse consumes
                 pts = order_points(boxes[k]) if len(boxes[k]) else np.zeros((0, 4, 2), np.float32)
                 ocr = [{"index": j + 1, "text": t, "bbox": pts[j]} for j, t in enumerate(texts[k])]
-                results[i] = PageResult(rotated_180=rotated[k],
+                results[i] = PageResult(rotated_180=rotated[k], skew_angle=skew[i], rotated_90=turned[i], image_shape=tuple(shape),
+                                        page_orientation=page_ori[i], table_attribute=page_attr[i],
                                         det_result=boxes[k], ocr_result=ocr, layout_result=None if lay is None else lay[k],
                                         table_structure_result=None if tsr is None else tsr[k],
                                         text_upright=None if ori is None else ori[k][1],
@@ -284,6 +336,50 @@ class OcrTablePipeline:
         return results
 
     # ------------------------------------------------------------------------------------------------------------------
+    def _straightening(self) -> bool:
+        return bool(getattr(self, "deskew", False) or getattr(self, "sideways_check", False)
+                    or getattr(self, "page_orientation_task", None) is not None or getattr(self, "table_attribute_task", None) is not None)
+
+    def _detect_boxes(self, batch: torch.Tensor) -> List[np.ndarray]:
+        stage: DetStage = self.text_detector._stage
+        prob, bitmap, ev = stage.forward(batch)
+        return [sort_boxes_reading_order(b) for b in stage.boxes(prob, bitmap, tuple(batch.shape[1:3]), ev)]
+
+    def _straighten_pages(self, imgs: List[np.ndarray]):
+        """steps 1 to 3 of OcrSystemTask.image_pre_process (ocr_system_task.py:441-468; the orientation pass of
+        OcrTablePreprocessTask.rotate_image_v2) on host pages of any shapes -> (device pages [h, w, 3], skew angles, orientation metrics,
+        table attributes, turned flags, the boxes of the pages the sideways check detected and did not turn)"""
+        from .page_pre_stage import PagePreStage
+        if self._page_pre is None:
+            self._page_pre = PagePreStage(self.engine)
+        st = self._page_pre
+        ori = self.page_orientation_task._stage if self.page_orientation_task is not None else None
+        att = self.table_attribute_task._stage if self.table_attribute_task is not None else None
+        if att is not None and ori is None:
+            raise ValueError("table_attribute=True runs on the page-orientation pass: it needs page_orientation=True")
+        with stage_range("page_pre"):
+            dev, skew, metrics, attrs = st.straighten(imgs, deskew=self.deskew, orientation=ori, attribute=att)
+        turned = [False] * len(imgs)
+        pre_boxes: Dict[int, np.ndarray] = {}
+        if self.sideways_check:
+            groups: Dict[tuple, List[int]] = {}
+            for i, t in enumerate(dev):
+                groups.setdefault(tuple(t.shape), []).append(i)
+            for shape, idxs in groups.items():
+                batch = torch.stack([dev[i] for i in idxs])
+                with stage_range("text_detection"):
+                    boxes = self._detect_boxes(batch)
+                side = st.sideways(boxes)
+                for k, i in enumerate(idxs):
+                    if not side[k]:
+                        pre_boxes[i] = boxes[k]
+                if side.any():
+                    sel = np.nonzero(side)[0]
+                    t = st.turn(batch[torch.tensor(sel, device=batch.device)].contiguous(), L.PT_ROTATE_90_COUNTERCLOCKWISE)
+                    for k, s_ in enumerate(sel):
+                        dev[idxs[s_]], turned[idxs[s_]] = t[k], True
+        return dev, skew, metrics, attrs, turned, pre_boxes
+
     def _layout_table_boxes(self, lay_pages) -> List[np.ndarray]:
         """layout regions labelled "table", score >= 0.2, top to bottom, at rounded coordinates
         (ocr_system_task.py:184-198, crop_image_by_box utils/ocr/ocr_common_utils.py:279-280)"""
@@ -363,6 +459,9 @@ class OcrTablePipeline:
         results arrive one batch later than without the vote at a = 1 (four batches behind the input), whether or not a page flips.
         The fields ``rotated_180``, ``text_upright`` and ``text_line_orientation`` are filled as in predict()."""
         vote = bool(orientation_vote)
+        if self._straightening():
+            raise ValueError("predict_stream() does not straighten pages (deskew / page_orientation / table_attribute / sideways_check / "
+                             "page_preprocess): use predict()")
         if self.orientation_task is not None and not vote:
             raise ValueError("predict_stream() runs the text-line orientation vote only when asked: predict_stream(..., orientation_vote=True) "
                              "(one more batch of latency), or predict()")
@@ -622,7 +721,7 @@ class OcrTablePipeline:
                                       table_structure_result=None if tsr is None else tsr[k],
                                       text_upright=None if ori is None else st["upright"][k],
                                       rotated_180=bool(ori is not None and k in st["down"]),
-                                      text_line_orientation=None if ori is None else ori[k]))
+                                      text_line_orientation=None if ori is None else ori[k], image_shape=tuple(st["shape"]) + (3,)))
             return out
 
         gpu_marks = [] if os.environ.get("PT_PIPE_GPU_TRACE") else None      # diagnostics: (phase, begin event, end event) on the main stream
