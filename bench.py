@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- pages/s of the hot path on N MI355X (one process per GPU, RCCL only for the weight broadcast).
 
-    python bench.py [--gpus N] [--steps 10] [--warmup 3]
+    python bench.py [--gpus N] [--steps 10] [--warmup 3] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -23,19 +23,21 @@ detector), and the table-structure stage crops the regions the layout stage labe
 
 Output.  stdout carries ONE compact JSON line (< 6 KB, `compact_line()`: the contract keys, `roofline`, `cpu_baseline`, `summary` -- numbers only);
 the full record (every leg with its notes and count tables) is written to bench_detail.json next to this file (--detail-out) and to stderr.
-The default run (`--legs core`) is the headline, the roofline legs, the precision legs `summary` is built from and the CPU baseline; `--legs all`
-adds the diagnostic / configs[4] legs (overlap_rec, ConvNextViT, ONNX recogniser, MtlTabNet / TableMaster).
+A plain run is the headline alone: set-up, spin-up, warm-up, the timed steps (with the roofline's HIP events inside them), the dump, the line.
+``--full`` (`--legs core`) adds what runs after the timed region: the roofline legs, the precision legs `summary` is built from, host_pages /
+one_eighth_host and the CPU baseline; ``--full --legs all`` also the diagnostic / configs[4] legs (overlap_rec, ConvNextViT, ONNX recogniser,
+MtlTabNet / TableMaster).
 ``--dump-outputs DIR`` also writes what the last timed step returned to its caller (boxes, texts, layout regions, table cells) as
 DIR/<name>.npy (`output_arrays()`); pages and weights are seeded, so the same arguments feed the same inputs on every run.
 
 Objects of the full record:
   roofline        the dominant kernel class (3x3 MFMA convolutions of all stages), HIP-event timed inside the timed region,
                   FLOP counted from real channel counts and the rows row-limited launches really computed;
-                  ``det_backbone``: BASELINE.md section 5's figure, 111.71 GFLOP x det-only pages/s / peak, from a det-only
+                  ``det_backbone`` (--full): BASELINE.md section 5's figure, 111.71 GFLOP x det-only pages/s / peak, from a det-only
                   leg of the same run
-  tolerance_mode  the same step in PT_PRECISION_BF16X3 -- the arithmetic whose GPU tests assert the north-star tolerance
+  tolerance_mode  (--full) the same step in PT_PRECISION_BF16X3 -- the arithmetic whose GPU tests assert the north-star tolerance
                   (1e-3 on logits, ids exact outside the oracle's own ties) -- timed over a few steps
-  cpu_baseline    the oracle restatement of the same stages on the host cores (bounded sample, rank 0 at N = 1 only),
+  cpu_baseline    (--full) the oracle restatement of the same stages on the host cores (bounded sample, rank 0 at N = 1 only),
                   plus BASELINE.json configs[0] (one 640x640 page, det + rec) on CPU and on the GPU
 """
 from __future__ import annotations
@@ -70,16 +72,19 @@ def parse_args(argv=None):
     ap.add_argument("--warmup", type=int, default=8,
                     help="untimed steps; the default covers the software pipeline's depth (3 batches) and the clock ramp of a GPU that idled "
                          "while the process imported and packed weights (a first process on a fresh box read 554 pages/s at 3, 605 afterwards)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs the headline does not need: the roofline legs (det-only, by-class), the precision "
+                         "legs the summary is built from (BF16X3, f16, end-to-end agreement), host_pages / one_eighth_host and the CPU baseline.  "
+                         "Without it a run sets up, warms up, times the steps, dumps (--dump-outputs) and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--legs", default="core", choices=["core", "all"],
-                    help="core (default): the headline, the roofline legs (det-only, by-class), the precision legs the summary is built from (BF16X3, "
-                         "f16, end-to-end agreement), host_pages / one_eighth_host and the CPU baseline.  all: also the diagnostic and configs[4] legs "
+                    help="which legs --full runs -- core (default): those its help names.  all: also the diagnostic and configs[4] legs "
                          "(overlap_rec, ConvNextViT, ONNX recogniser, MtlTabNet / TableMaster).  Either way stdout carries ONE compact JSON line "
                          "(< 6 KB); the full record goes to bench_detail.json next to this file and to stderr")
     ap.add_argument("--detail-out", default=os.environ.get("PT_BENCH_DETAIL", os.path.join(REPO, "bench_detail.json")),
                     help="where the full record (every leg, notes, count tables) is written")
     ap.add_argument("--by-class-only", action="store_true", help="diagnostic: the timed region, then only the roofline.by_class leg")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the det-only and BF16X3 legs (diagnostic runs)")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the legs after the timed region except the CPU baseline")
     ap.add_argument("--det-backbone", default="resnet18", choices=["resnet18", "proxylessnas"],
                     help="DB detector network: DBModel (BASELINE.json's configuration) or DBNasModel (diagnostic variant)")
     ap.add_argument("--no-post", action="store_true", help="device half only (diagnostic; not a valid headline)")
@@ -87,7 +92,7 @@ def parse_args(argv=None):
                     help="also run the host_pages leg (pinned host batches, H2D inside the timed region) when --no-extra-legs is given; "
                          "the one_eighth_host child uses it")
     ap.add_argument("--host-share", type=int, default=0,
-                    help="(leg of the default run) re-run the timed region in a child process pinned with sched_setaffinity to 1/N of "
+                    help="(leg of a --full run) re-run the timed region in a child process pinned with sched_setaffinity to 1/N of "
                          "the host's cores: what every rank of an N-GPU node gets")
     ap.add_argument("--private-loop", action="store_true",
                     help="time bench.py's own software-pipelined loop (HipRunner.run_private) instead of OcrTablePipeline.predict_stream() "
@@ -104,14 +109,17 @@ def parse_args(argv=None):
                     help="diagnostic: feed the table-structure stage the generator's table rectangles (grown by 8 px) instead of the "
                          "layout stage's own 'table' regions (rounds 1-2 behaviour)")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "bf16x3", "f16x2"],
-                    help="arithmetic mode of the TIMED region (bf16x3: the tolerance mode as the headline; the default line "
+                    help="arithmetic mode of the TIMED region (bf16x3: the tolerance mode as the headline; a --full line "
                          "reports it as tolerance_mode)")
     ap.add_argument("--stages", default=os.environ.get("PT_BENCH_STAGES", "layout,det,rec,tsr"),
                     help="comma list of stages in the timed step: layout (PicoDet), det (configs[1]), rec, tsr (Lore)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what predict_stream() returned for the last timed step's batch as DIR/<name>.npy "
                          "(float64, at most 64 MB; rank 0's shard): the inputs are seeded, so two builds compare output for output")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.legs == "all" and not args.full:
+        ap.error("--legs all names legs of a --full run: add --full")
+    return args
 
 
 def self_launch(args, argv):
@@ -445,7 +453,8 @@ class HipRunner:
         self.dev = dev = torch.device("cuda", local_rank)
         self.stages = stages = [x for x in args.stages.split(",") if x]
         assert set(stages) <= {"layout", "det", "rec", "tsr", "cls"} and stages
-        # the (hi, lo) weight tiles are only packed / broadcast when a BF16X3 leg will run (extra legs: one rank only)
+        # the (hi, lo) weight tiles are only packed / broadcast when a BF16X3 leg may run (extra legs: one rank only).  A plain run packs them too: its
+        # timed steps then run on the device memory layout of a --full run's (without them, five alternated pairs read 780 vs 786 pages/s)
         self.x3_leg = ((not args.no_extra_legs and world == 1) or args.precision != "bf16") and args.det_backbone == "resnet18"
         x3 = self.x3_leg            # blobs then also carry the (hi, lo) weight tiles of PT_PRECISION_BF16X3
         self.eng = eng = HipEngine(local_rank)
@@ -875,8 +884,8 @@ class HipRunner:
 
     def x3_leg_run(self, steps=8, warm=2):
         """the same step in PT_PRECISION_BF16X3 (the mode whose tests assert 1e-3 / id-exact parity); eight timed steps: the software pipeline's fill
-        and drain are one step's worth of a three-step run (the bf16 region reads 3 % lower at 10 steps than at 20 for the same reason); the default
-        bench passes the headline's K"""
+        and drain are one step's worth of a three-step run (the bf16 region reads 3 % lower at 10 steps than at 20 for the same reason); --full
+        passes the headline's K"""
         L = self.L
         self.eng.set_precision(L.PT_PRECISION_BF16X3)
         try:
@@ -1419,7 +1428,7 @@ def compact_line(out):
             s[name] = {m: v[rate] for m, v in leg.items() if isinstance(v, dict) and rate in v} or _pick(leg, "error")
     if isinstance(out.get("overlap_rec"), dict):
         s["overlap_rec_pages_per_s"] = out["overlap_rec"].get("pages_per_s")
-    s["detail"] = "bench_detail.json (every leg, notes, count tables); side legs: --legs all"
+    s["detail"] = "bench_detail.json (every leg, notes, count tables); legs: --full, side legs: --full --legs all"
     line["summary"] = s
     line = _r(line)
     for k in ("value", "ms_per_step"):      # the contract's own numbers keep every digit (value == pages / time to the last bit)
@@ -1560,7 +1569,9 @@ def main(argv=None):
                 roof["all_kernel_classes_ms"] = {k: v["ms"] for k, v in prof.items()}
                 roof["all_kernel_classes_flop"] = {k: v["flop"] for k, v in prof.items()}
             out["roofline"] = roof
-    if not stub and world == 1 and (args.host_pages_leg or not (args.no_extra_legs or args.by_class_only)) and not args.no_post:
+    # everything below is outside what the headline needs: a plain run reports the timed region and stops; --full runs the legs and the CPU baseline
+    extra = args.full and not args.no_extra_legs and not args.by_class_only
+    if not stub and world == 1 and (args.host_pages_leg or extra) and not args.no_post:
         try:
             # as many timed steps as the headline region: a 10-step leg reads ~3 % lower than a 20-step one on the SAME resident input (one pipeline fill + drain
             # in half the time), which is most of the 0.96 the round-4 driver line showed for this ratio
@@ -1590,7 +1601,7 @@ def main(argv=None):
         leg = guarded(runner.by_class_leg)
         if rank == 0 and leg is not None:
             out["roofline"]["by_class"] = leg
-    if not stub and not args.no_extra_legs and not args.by_class_only and world == 1:
+    if not stub and extra and world == 1:
         if "det" in runner.stages and not runner.nas:
             leg = guarded(runner.det_only_leg)
             if rank == 0:
@@ -1638,13 +1649,13 @@ def main(argv=None):
             if rank == 0 and leg is not None:
                 out["mtl_tabnet"] = leg
     if rank == 0:
-        if not stub and world == 1 and not args.no_cpu_baseline and "det" in runner.stages:
+        if not stub and world == 1 and args.full and not args.no_cpu_baseline and "det" in runner.stages:
             r = runner
             gpu = r.parity_sample()
             out["cpu_baseline"] = cpu_baseline(r.sd, r.pages_np[:2], r.cfg, r.csd if r.rec is not None else None,
                                                tsr=(r.lsd, r.psd, r.table_boxes, r.tables_per_page) if r.tsr is not None else None,
                                                layout=r.ysd if r.layout is not None else None, gpu=gpu)
-        if not stub and not args.no_extra_legs and not args.by_class_only and world == 1 and len(runner.stages) > 1 and not args.no_post:
+        if not stub and extra and world == 1 and len(runner.stages) > 1 and not args.no_post:
             # last: the child needs the GPU's memory, so this process gives its engine (activation arenas, weights) and torch's cache back first
             try:
                 runner.eng.close()

@@ -105,3 +105,15 @@ def test_stub_refuses_dump_outputs(tmp_path):
                         "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, env=env, timeout=300)
     assert p.returncode != 0 and "--dump-outputs" in p.stderr
     assert not (tmp_path / "out").exists()
+
+
+def test_legs_all_needs_full(tmp_path):
+    """the side legs are legs of a --full run: `--legs all` alone is refused, `--full --legs all` runs (stub runner: no legs to run)"""
+    env = dict(os.environ, PT_BENCH_STUB="1")
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "0", "--detail-out", str(tmp_path / "d.json"), "--legs", "all"]
+    p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode != 0 and "--full" in p.stderr and not p.stdout.strip()
+    p = subprocess.run(cmd + ["--full"], capture_output=True, text=True, env=env, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and json.loads(lines[0])["steps"] == 1

@@ -36,3 +36,22 @@ def test_bench_dump_outputs(tmp_path):
     assert got["layout_regions_per_page"].sum() == len(got["layout_bbox"]) == len(got["layout_score"])
     assert got["tables_per_page"].sum() == len(got["table_polygons_rows"]) > 0
     assert got["table_polygons_rows"].sum() == len(got["table_polygons"]) and got["table_scores_rows"].sum() == len(got["table_scores"]) > 0
+
+
+def test_bench_plain_run_stops_after_the_timed_steps(tmp_path):
+    """without --full nothing runs after the timed steps: the record holds the headline and the timed region's roofline, no leg and no CPU baseline"""
+    env = dict(os.environ, PT_BENCH_PAGES="4", PT_BENCH_SPINUP="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "PT_BENCH_STUB", "PT_BENCH_DISTINCT"):
+        env.pop(k, None)
+    detail = tmp_path / "detail.json"
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--detail-out", str(detail)],
+                       cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0, p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
+    full = json.loads(detail.read_text())
+    assert full["roofline"]["launches"] > 0
+    assert not {"det_backbone", "by_class"} & set(full["roofline"])
+    assert not {"host_pages", "tolerance_mode", "cpu_baseline", "one_eighth_host"} & set(full)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/profile_round.sh <tag>: the measurement set committed under profiles/<round>/ (run on the GPU box through gpurun).
-#   1. bench.py default (compact line + bench_detail.json)                          -> gpurun_out/<tag>/bench_line.json, bench_detail.json
+#   1. bench.py --full (compact line + bench_detail.json)                           -> bench_line.json, bench_detail.json of the tag
 #   2. bench.py --stages det (BASELINE.json configs[1])                             -> gpurun_out/<tag>/bench_det.json
 #   3. rocprofv3 --kernel-trace --stats of the default bench (timed legs only)      -> gpurun_out/<tag>/kernel_stats.csv, gaps.txt
 #   4. separate PMC passes: FETCH_SIZE, WRITE_SIZE (-> pmc_summary.json), MFMA busy (-> mfma_busy.json)
@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python $R/bench.py --steps 20 --warmup 8 --detail-out $O/bench_detail.json 2>$O/bench_full.err | tail -1 > $O/bench_line.json
+timeout 900 python $R/bench.py --full --steps 20 --warmup 8 --detail-out $O/bench_detail.json 2>$O/bench_full.err | tail -1 > $O/bench_line.json
 timeout 300 python $R/bench.py --stages det --no-cpu-baseline --no-extra-legs --steps 20 --warmup 5 --detail-out $O/bench_det_detail.json 2>/dev/null | tail -1 > $O/bench_det.json
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extra-legs --detail-out /tmp/d1.json > $O/stats.log 2>&1
 KS=$(find $O/stats -name "*kernel_stats.csv" | head -1); [ -n "$KS" ] && cp $KS $O/kernel_stats.csv
