@@ -26,7 +26,7 @@ CPP_SOURCES = ["db_post.cpp", "api_common.cpp"]
 # HIP compiled ONCE (as namespace pt_bf16): kernels on uint8 pages only, no activation format; their entry points take no engine, so the
 # generated dispatchers call pt_bf16::api only
 ONCE_HIP_SOURCES = ["page_pre.hip"]
-HEADERS = ["common.h", "act16.h", "dla_net.h", os.path.join("..", "..", "include", "pdftable_hip.h")]
+HEADERS = ["common.h", "act16.h", "dla_net.h", "net_ctx.h", os.path.join("..", "..", "include", "pdftable_hip.h")]
 # Every HIP translation unit is compiled once per 16-bit activation format (csrc/act16.h): namespace pt_bf16, and namespace pt_f16 with -DPT_ACT_F16=1
 FORMATS = [("bf16", []), ("f16", ["-DPT_ACT_F16=1"])]
 

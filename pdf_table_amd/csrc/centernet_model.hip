@@ -55,7 +55,7 @@ struct CCtx : DlaCtx {
   Slice half(const T& cat, int which) const { return Slice{cat.p ? cat.p + which * (cat.C / 2) : nullptr, cat.C * mul, cat.C}; }
 
   void copy(const T& like, const Slice& from, const Slice& to) {
-    if (rc != PT_OK || dry || !ok) return;
+    if (!go()) return;
     const long long npix = (long long)n * like.H * like.W;
     e->prof.next_bytes = (double)npix * like.C * 2.0 * mul * 2.0;
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "centernet concat copy");
@@ -68,16 +68,11 @@ struct CCtx : DlaCtx {
   }
   // conv + folded bias (+ ReLU) into a slice of a wider map
   void conv_into(const T& in, const std::string& q, int N, int ks, const Slice& out, int relu) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK || dry || !ok) return;
     ConvDesc c;
-    c.in = in.p; c.B = n; c.H = in.H; c.W = in.W; c.Cin = in.C;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = ks; c.stride = 1; c.relu = relu; c.split = x3; c.alg_scale = alg_scale;
+    if (!conv_desc(c, in, q, N, ks, 1, relu)) return;
+    c.alg_scale = alg_scale;
     c.out = out.p; c.out_cstride = out.cs; c.out_lo_off = out.lo;
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
   // IDAUp.forward on layers[startp .. endp); keep_dense: the node outputs are projected by the next IDAUp
   void ida(const std::string& q, std::vector<T>& layers, int startp, int endp, int o, bool keep_dense) {
@@ -92,13 +87,13 @@ struct CCtx : DlaCtx {
         conv(layers[i], q + ".proj_" + js, o, 1, 1, p, 1);
       }
       const PtTensor* wu = get(q + ".up_" + js + ".wf32");
-      if (rc == PT_OK && !dry && ok) {
+      if (go()) {
         e->prof.next_bytes = (double)n * p.H * p.W * o * 2.0 * mul * 5.0;      // in once, out at 2 x 2 the pixels
         char label[48];
         snprintf(label, sizeof(label), "dw convT up %d @%dx%d", o, p.H * 2, p.W * 2);
         PtProfScope ps(e, s, PT_PROF_OTHER, 0, label);
         const Slice u = half(cat, 1);
-        const int r = pt_launch_dwconvt_up2_slice(p.p, reinterpret_cast<const float*>(wu->d_ptr), cat.p, u.cs, o, u.lo, n, p.H, p.W, o, x3, s);
+        const int r = pt_launch_dwconvt_up2_slice(p.p, F(wu), cat.p, u.cs, o, u.lo, n, p.H, p.W, o, x3, s);
         if (r != PT_OK) rc = r;
       }
       const bool last = i + 1 == endp;
@@ -129,25 +124,14 @@ struct CCtx : DlaCtx {
 int pt_centernet_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* hm, float* v2c, float* c2v, float* reg, hipStream_t s) {
   PT_REQUIRE(H % 32 == 0 && W % 32 == 0 && H > 0 && W > 0, "CenterNet net: input %dx%d must be multiples of 32", H, W);
   PT_REQUIRE(x && n > 0 && hm && v2c && c2v && reg, "CenterNet net: null pointer");
-  auto it = e->models.find(PT_MODEL_CENTERNET_DLA34);
-  if (it == e->models.end()) {
-    pt_set_error("CenterNet DLA-34 weights not loaded (pt_weights_load(PT_MODEL_CENTERNET_DLA34))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_CENTERNET_DLA34")) return PT_ERR_STATE;
+  const PtModel* m = pt_find_model(e, PT_MODEL_CENTERNET_DLA34, "CenterNet DLA-34", "PT_MODEL_CENTERNET_DLA34");
+  if (!m) return PT_ERR_STATE;
   CCtx c;
-  c.e = e; c.m = &it->second; c.s = s; c.n = n;
-  c.what = "CenterNet DLA-34";
-  c.x3 = pt_split(e) ? 1 : 0;
-  c.mul = c.x3 ? 2 : 1;
-  c.rc = PT_OK;
+  c.init(e, m, "CenterNet DLA-34", s, n, PT_ARENA_TSR);
   float* heads[4] = {hm, v2c, c2v, reg};
   const char* hname[4] = {"hm", "v2c", "c2v", "reg"};
   const int hreal[4] = {2, 8, 8, 2};
-  for (int pass = 0; pass < 2; ++pass) {
-    c.dry = pass == 0;     // pass 0 plans the arena (and grows it if needed), pass 1 launches
-    c.ok = true;
-    e->arenas[PT_ARENA_TSR].reset();
+  return pt_plan_then_launch(c, "CenterNet net", [&] {
     std::vector<T> layers = dla34_base(c, x, H, W);
     // DLAUp.forward: ida_0 on [4,6), ida_1 on [3,6), ida_2 on [2,6); each replaces layers[startp + 1 ..] by its node outputs
     c.ida("dla_up.ida_0", layers, 4, 6, 256, true);
@@ -159,19 +143,8 @@ int pt_centernet_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* 
       c.conv(feat, std::string(hname[h]) + ".0", 256, 3, 1, hid, 1);
       c.conv(hid, std::string(hname[h]) + ".2", 64, 1, 1, T(), 0, nullptr, 8, heads[h], 8, 0, hreal[h]);
     }
-    if (c.rc != PT_OK) return c.rc;
-    if (pass == 0) {
-      if (c.ok) continue;
-      const int r = dla_arena_grow(e);
-      if (r != PT_OK) return r;
-      continue;
-    }
-    if (!c.ok) {
-      pt_set_error("CenterNet net: activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-  }
-  return PT_OK;
+    return c.rc;
+  });
 }
 
 }  // namespace PT_FMT_NS

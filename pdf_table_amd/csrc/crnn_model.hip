@@ -17,7 +17,7 @@
 // 32 time steps (no empty MFMA rows).
 #include <stdlib.h>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -37,9 +37,6 @@ int getw(const PtModel& m, const std::string& base, bool x3, ConvW& out) {
   return PT_OK;
 }
 
-inline const bf16_t* W(const PtTensor* t) { return reinterpret_cast<const bf16_t*>(t->d_ptr); }
-inline const float* Bv(const PtTensor* t) { return reinterpret_cast<const float*>(t->d_ptr); }
-
 }  // namespace
 
 // element offsets (per channel multiplier m) of the single-line tensors inside pt_engine::rec_zero[precision]
@@ -54,13 +51,9 @@ struct ZeroLine {
 int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, float* maxlogit, hipStream_t s,
                         const pt_rec_line* d_lines) {
   PT_REQUIRE(e && gray && ids && n > 0, "crnn: bad arguments");
-  auto it = e->models.find(PT_MODEL_CRNN);
-  if (it == e->models.end()) {
-    pt_set_error("CRNN weights not loaded (pt_weights_load(PT_MODEL_CRNN))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_CRNN")) return PT_ERR_STATE;
-  const PtModel& M = it->second;
+  const PtModel* pm = pt_find_model(e, PT_MODEL_CRNN, "CRNN", "PT_MODEL_CRNN");
+  if (!pm) return PT_ERR_STATE;
+  const PtModel& M = *pm;
   const int x3 = pt_split(e) ? 1 : 0;
   const int m = x3 ? 2 : 1;
   int rc;
@@ -83,14 +76,8 @@ int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, f
     bf16_t *a0, *a1, *p1, *c2a, *c2b, *p2, *c3a, *c3b, *p3, *f, *gx, *h, *e1, *e2;
     float* part;
   } bf;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    e->arenas[PT_ARENA_REC].reset();
-    bool ok = true;
-    auto take = [&](size_t elems) {
-      void* p = e->arenas[PT_ARENA_REC].take(elems * m * sizeof(bf16_t));
-      if (!p) ok = false;
-      return reinterpret_cast<bf16_t*>(p);
-    };
+  rc = pt_arena_plan(e, PT_ARENA_REC, "crnn", [&](auto&& take_bytes) {
+    auto take = [&](size_t elems) { return reinterpret_cast<bf16_t*>(take_bytes(elems * m * sizeof(bf16_t))); };
     const size_t N = (size_t)n;
     bf.a0 = take(N * 16 * 320 * 64);
     bf.a1 = take(N * 16 * 320 * 128);
@@ -106,26 +93,14 @@ int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, f
     bf.h = take(N * T * 512);
     bf.e1 = take(N * T * 256);
     bf.e2 = take(N * T * 512);
-    void* pp = e->arenas[PT_ARENA_REC].take(N * T * NT * 2 * sizeof(float));
-    if (!pp) ok = false;
-    bf.part = reinterpret_cast<float*>(pp);
-    if (ok) break;
-    if (attempt == 1) {
-      pt_set_error("activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-    PT_HIP_CHECK(hipDeviceSynchronize());
-    if (e->arenas[PT_ARENA_REC].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_REC].base));
-    e->arenas[PT_ARENA_REC].base = nullptr;
-    const size_t want = pt_arena_round(e->arenas[PT_ARENA_REC].high);
-    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_REC].base), want));
-    e->arenas[PT_ARENA_REC].cap = want;
-  }
+    bf.part = reinterpret_cast<float*>(take_bytes(N * T * NT * 2 * sizeof(float)));
+  });
+  if (rc != PT_OK) return rc;
 
 #define RUN(call) do { if ((rc = (call)) != PT_OK) return rc; } while (0)
   auto conv = [&](const bf16_t* in, int B, int hh, int ww, int cin, const ConvW& cw, int N, int ks, bf16_t* out, int relu) {
     ConvDesc c;
-    c.in = in; c.B = B; c.H = hh; c.W = ww; c.Cin = cin; c.w = W(cw.w); c.bias = Bv(cw.b); c.N = N; c.ks = ks;
+    c.in = in; c.B = B; c.H = hh; c.W = ww; c.Cin = cin; c.w = W(cw.w); c.bias = F(cw.b); c.N = N; c.ks = ks;
     c.stride = 1; c.out = out; c.out_cstride = N * m; c.relu = relu; c.split = x3; c.out_lo_off = N;
     return c;
   };
@@ -148,13 +123,13 @@ int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, f
   auto rows_gemm = [&](const bf16_t* in, int cin, const ConvW& cw, int N, bf16_t* out, int relu, const char* label) -> int {
     if (!x3 && fused && (cin == 256 || (cin == 512 && !gemm_pipe()))) {      // (K = 256 stays on the streaming kernel: pt_launch_conv's rule)
       PtProfScope ps(e, s, PT_PROF_CONV1X1, 2.0 * n * T * (double)cin * N, label);
-      return pt_launch_gemm_rows(in, (long long)n * T, cin, W(cw.w), Bv(cw.b), N, out, relu, s);
+      return pt_launch_gemm_rows(in, (long long)n * T, cin, W(cw.w), F(cw.b), N, out, relu, s);
     }
     if (rows_x3() && (cin == 512 || cin == 256)) {
       char lb[48];
       snprintf(lb, sizeof(lb), "%s x3", label);
       PtProfScope ps(e, s, PT_PROF_CONV1X1, 2.0 * n * T * (double)cin * N, lb);
-      return pt_launch_gemm_rows_x3(in, (long long)n * T, cin, W(cw.w), Bv(cw.b), N, out, relu, s);
+      return pt_launch_gemm_rows_x3(in, (long long)n * T, cin, W(cw.w), F(cw.b), N, out, relu, s);
     }
     return pt_launch_conv(e, conv(in, 1, n, T, cin, cw, N, 1, out, relu), s);
   };
@@ -189,11 +164,11 @@ int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, f
     const char* ev01 = getenv("PT_CONV01");
     const bool conv01 = pool_fused && !x3 && !(ev01 && atoi(ev01) == 0);
     if (conv01) {
-      RUN(pt_launch_crnn_conv01(e, g, nn, Bv(c0w), Bv(c0b), W(c1.w), Bv(c1.b), p1, lim ? lim->lim[0] : nullptr, lim ? lim->cols + 0 : nullptr, s));
+      RUN(pt_launch_crnn_conv01(e, g, nn, F(c0w), F(c0b), W(c1.w), F(c1.b), p1, lim ? lim->lim[0] : nullptr, lim ? lim->cols + 0 : nullptr, s));
       RUN(fill(p1, ZeroLine::P1, 0, 32, 2, 8, 160, 128, 1, 32));
     } else {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "crnn conv0+pool");
-      RUN(pt_launch_crnn_conv0_pool(g, nn, PT_REC_H, PT_REC_W, Bv(c0w), Bv(c0b), x3, a0, s, lim ? lim->lim[5] : nullptr));
+      RUN(pt_launch_crnn_conv0_pool(g, nn, PT_REC_H, PT_REC_W, F(c0w), F(c0b), x3, a0, s, lim ? lim->lim[5] : nullptr));
     }
     // conv1 + pool(2,2) and conv2.3 + pool((2,1)): pooling in the conv epilogue (PT_POOL_FUSED=0: separate pool kernels,
     // which need the full maps: no column limits then)
@@ -240,8 +215,8 @@ int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, f
       int lim_slot = -1;
       {
         PtProfScope ps(e, s, PT_PROF_CONV1X1, 2.0 * nn * T * 512.0 * 2048, x3 ? "rows gemm 512->2048 x3" : "rows gemm 512->2048");
-        if (x3) RUN(pt_launch_gemm_rows_x3(f_o, (long long)nn * T, 512, W(xp1.w), Bv(xp1.b), 2048, gx_o, 0, s, lim ? lim->glist : nullptr));
-        else RUN(pt_launch_gemm_rows(f_o, (long long)nn * T, 512, W(xp1.w), Bv(xp1.b), 2048, gx_o, 0, s, lim ? lim->glist : nullptr));
+        if (x3) RUN(pt_launch_gemm_rows_x3(f_o, (long long)nn * T, 512, W(xp1.w), F(xp1.b), 2048, gx_o, 0, s, lim ? lim->glist : nullptr));
+        else RUN(pt_launch_gemm_rows(f_o, (long long)nn * T, 512, W(xp1.w), F(xp1.b), 2048, gx_o, 0, s, lim ? lim->glist : nullptr));
         if (lim && ps.idx >= 0 && e->prof.h_lims && e->prof.n_lims < PtProfile::MAX_LIMS) {      // credit the executed row groups, like the limited convs
           auto& pd = e->prof.pending[ps.idx];
           pd.lim_slot = lim_slot = e->prof.n_lims++;
@@ -325,12 +300,12 @@ int pt_crnn_forward_net(pt_engine* e, const bf16_t* gray, int n, int32_t* ids, f
   const bool cls_pipe = gemm_pipe() && cp_ev && cp_ev[0] == '1';
   if (!x3 && fused && !cls_pipe) {
     PtProfScope ps(e, s, PT_PROF_CONV1X1, 2.0 * n * T * 512.0 * 7680.0, "classifier gemm+argmax");
-    RUN(pt_launch_gemm_argmax(bf.e2, (long long)n * T, 512, W(cls.w), Bv(cls.b), 7680, ids, maxlogit, s));
+    RUN(pt_launch_gemm_argmax(bf.e2, (long long)n * T, 512, W(cls.w), F(cls.b), 7680, ids, maxlogit, s));
   } else if (x3 && fused && !pt_f16x2(e) && !(getenv("PT_CLS_X3_REFINE") && atoi(getenv("PT_CLS_X3_REFINE")) == 0)) {
     // hi/lo mode: two single-pass sweeps (maximum, then the classes within the rounding bound of it) + exact logits of those
     // candidates (rec_kernels.hip: gemm_cand_kernel / cand_eval_kernel); PT_CLS_X3_REFINE=0: the tiled three-pass GEMM (A/B switch)
     PtProfScope ps(e, s, PT_PROF_CONV1X1, 2.0 * n * T * 512.0 * 7680.0, "classifier bound+refine x3");
-    RUN(pt_launch_gemm_argmax_x3(bf.e2, (long long)n * T, 512, W(cls.w), Bv(cls.b), 7680, 7680, ids, maxlogit, bf.part, s));
+    RUN(pt_launch_gemm_argmax_x3(bf.e2, (long long)n * T, 512, W(cls.w), F(cls.b), 7680, 7680, ids, maxlogit, bf.part, s));
   } else {
     {
       ConvDesc c = conv(bf.e2, 1, n, T, 512, cls, 7680, 1, nullptr, 0);

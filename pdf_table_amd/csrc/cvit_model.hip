@@ -36,7 +36,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -591,43 +591,27 @@ int launch_mlp(const bf16_t* xb, const bf16_t* w1, const float* b1, const bf16_t
   return PT_OK;
 }
 
-struct Net {
-  pt_engine* e;
-  const PtModel* m;
-  hipStream_t s;
-  int x3, mul, rc;
-  const PtTensor* get(const std::string& n) {
-    const PtTensor* t = m->find(n);
-    if (!t && rc == PT_OK) {
-      pt_set_error("ConvNextViT weight blob lacks tensor '%s'", n.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  }
+struct Net : NetCtx {
   const float* f32(const std::string& n) {
     const PtTensor* t = get(n);
-    return t ? reinterpret_cast<const float*>(t->d_ptr) : nullptr;
+    return t ? F(t) : nullptr;
   }
   // y = x W^T + b over `rows` (padded to 128) rows: x bf16 [rows, cin] -> bf16 [rows, N] (act: 0 none, 4 GELU), or the fp32
   // stream [rows, f32_cs] (+ fp32 residual `res`, in place when res == out_f32); nv: real output channels when N is padded
   void gemm(const bf16_t* x, long long rows, int cin, const std::string& q, int N, int act, bf16_t* out, float* out_f32 = nullptr,
             int f32_cs = 0, const float* res = nullptr, int nv = 0, float* argmax_part = nullptr) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK) return;
     ConvDesc c;
-    c.in = x; c.B = 1; c.H = (int)(rows / 32); c.W = 32; c.Cin = cin;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = 1; c.stride = 1; c.relu = act; c.split = x3; c.n_valid = nv;
+    if (!conv_desc(c, rows_map(x, rows, cin), q, N, 1, 1, act)) return;
+    c.n_valid = nv;
     if (argmax_part) {
       c.argmax_part = argmax_part;
     } else if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = f32_cs; c.res_f32 = res;
+      to_f32(c, out_f32, f32_cs);
+      c.res_f32 = res;
     } else {
-      c.out = out; c.out_cstride = N * mul; c.out_coff = 0; c.out_lo_off = N;
+      to_map(c, rows_map(out, rows, N));
     }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
 };
 
@@ -646,8 +630,7 @@ void mlp(Net& p, const bf16_t* xb, bf16_t* hb, float* x, long long rows_pad, int
     const float *b1 = p.f32(q + "." + n1 + ".b"), *b2 = p.f32(q + "." + n2 + ".b");
     if (p.rc != PT_OK) return;
     PtProfScope ps(p.e, p.s, PT_PROF_CONV1X1, 16.0 * rows_pad * (double)C * C, "cvit fused mlp");
-    const bf16_t* W1 = reinterpret_cast<const bf16_t*>(w1->d_ptr);
-    const bf16_t* W2 = reinterpret_cast<const bf16_t*>(w2->d_ptr);
+    const bf16_t *W1 = W(w1), *W2 = W(w2);
     // 128-row workgroups (NW = 4), two per CU; 256-row ones (NW = 8, one per CU, half the weight DMA per row) measured equal at
     // C = 256 and 5-10 % slower at C = 96 / 192
     int r;
@@ -664,8 +647,7 @@ void mlp(Net& p, const bf16_t* xb, bf16_t* hb, float* x, long long rows_pad, int
     const PtTensor *w = p.get(q + "." + n1 + ".w"), *b = p.get(q + "." + n1 + ".b");
     if (p.rc != PT_OK) return;
     PtProfScope ps(p.e, p.s, PT_PROF_CONV1X1, 2.0 * rows_pad * (double)C * 4 * C, "cvit rows gemm + gelu");
-    const int r = pt_launch_gemm_rows(xb, rows_pad, C, reinterpret_cast<const bf16_t*>(w->d_ptr), reinterpret_cast<const float*>(b->d_ptr),
-                                      4 * C, hb, 4, p.s);
+    const int r = pt_launch_gemm_rows(xb, rows_pad, C, W(w), F(b), 4 * C, hb, 4, p.s);
     if (r != PT_OK) p.rc = r;
   } else {
     p.gemm(xb, rows_pad, C, q + "." + n1, 4 * C, 4, hb);
@@ -677,9 +659,7 @@ void mlp(Net& p, const bf16_t* xb, bf16_t* hb, float* x, long long rows_pad, int
 int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, long long jstride, long long lstride, int n, int32_t* ids,
                   float* maxlogit, hipStream_t s, const int* h_tw) {
   Net p;
-  p.e = e; p.m = &M; p.s = s; p.rc = PT_OK;
-  p.x3 = pt_split(e) ? 1 : 0;
-  p.mul = p.x3 ? 2 : 1;
+  p.init(e, &M, "ConvNextViT", s, 1, PT_ARENA_REC);      // n = 1: every GEMM sees its rows as one [rows / 32, 32] map
   const int x3 = p.x3, mul = p.mul, NT = 7680 / 64;
   // h_tw != null: the lines' text widths after the keep-ratio resize are known.  Chunk j of a line is columns [252 j, 252 j +
   // 300): with a text width <= 252 j it is all padding, and every all-padding chunk yields the same 75 tokens -- the CNN and
@@ -718,11 +698,7 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
   bf16_t *xb = nullptr, *hb = nullptr, *qkv = nullptr, *att = nullptr, *feat = nullptr;
   float* part = nullptr;
   int *d_cmap = nullptr, *d_csrc = nullptr;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    PtArena& A = e->arenas[PT_ARENA_REC];
-    A.reset();
-    bool ok = true;
-    auto take = [&](size_t bytes) { void* q = A.take(bytes); if (!q) ok = false; return q; };
+  const int prc = pt_arena_plan(e, PT_ARENA_REC, "ConvNextViT", [&](auto&& take) {
     x = reinterpret_cast<float*>(take((size_t)(xel + 128) * sizeof(float)));      // + 128: the padded-N epilogue reads up to 32 floats
     xb = reinterpret_cast<bf16_t*>(take((size_t)xel * mul * sizeof(bf16_t)));      //   past the last 96-wide row
     hb = reinterpret_cast<bf16_t*>(take((size_t)xel * 4 * mul * sizeof(bf16_t)));
@@ -734,18 +710,8 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
       d_cmap = reinterpret_cast<int*>(take(cmap.size() * sizeof(int)));
       d_csrc = reinterpret_cast<int*>(take(csrc.size() * sizeof(int)));
     }
-    if (ok) break;
-    if (attempt == 1) {
-      pt_set_error("activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-    PT_HIP_CHECK(hipDeviceSynchronize());
-    if (A.base) PT_HIP_CHECK(hipFree(A.base));
-    A.base = nullptr;
-    const size_t want = pt_arena_round(A.high);
-    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&A.base), want));
-    A.cap = want;
-  }
+  });
+  if (prc != PT_OK) return prc;
   if (h_tw) {
     // sources of asynchronous copies: a pinned slot of the engine's staging ring, re-used only after the event recorded behind these
     // copies has completed (a pageable vector in a fixed-depth ring could be rewritten by a host that runs far ahead of the GPU)
@@ -841,8 +807,7 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
     const PtTensor *w = p.get("cls.w"), *b = p.get("cls.b");
     if (p.rc != PT_OK) return p.rc;
     PtProfScope ps(e, s, PT_PROF_CONV1X1, 2.0 * n * 201 * 192.0 * 7680.0, "cvit classifier gemm+argmax");
-    return pt_launch_gemm_argmax(feat, (long long)n * 201, 192, reinterpret_cast<const bf16_t*>(w->d_ptr), reinterpret_cast<const float*>(b->d_ptr),
-                                 7680, ids, maxlogit, s);
+    return pt_launch_gemm_argmax(feat, (long long)n * 201, 192, W(w), F(b), 7680, ids, maxlogit, s);
   }
   p.gemm(feat, rows_cls, 192, "cls", 7680, 0, nullptr, nullptr, 0, nullptr, 0, part);
   if (p.rc != PT_OK) return p.rc;
@@ -857,12 +822,8 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
 // pre-processor cuts the chunks from: chunk j = columns [252 j, 252 j + 300))
 int pt_cvit_forward_net(pt_engine* e, const float* gray, int layout, int n, int32_t* ids, float* maxlogit, hipStream_t s, const int* h_text_w) {
   PT_REQUIRE(e && gray && ids && n > 0 && (layout == 0 || layout == 1), "convnext-vit: bad arguments");
-  auto it = e->models.find(PT_MODEL_CONVNEXT_VIT);
-  if (it == e->models.end()) {
-    pt_set_error("ConvNextViT weights not loaded (pt_weights_load(PT_MODEL_CONVNEXT_VIT))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_CONVNEXT_VIT")) return PT_ERR_STATE;
+  const PtModel* M = pt_find_model(e, PT_MODEL_CONVNEXT_VIT, "ConvNextViT", "PT_MODEL_CONVNEXT_VIT");
+  if (!M) return PT_ERR_STATE;
   static int mb = -1, skip = -1;
   if (mb < 0) {
     const char* ev = getenv("PT_CVIT_MICROBATCH");
@@ -885,7 +846,7 @@ int pt_cvit_forward_net(pt_engine* e, const float* gray, int layout, int n, int3
       chunks += c;
       ++nb;
     }
-    const int rc = forward_batch(e, it->second, gray + (long long)i0 * lstride, pitch, jstride, lstride, nb, ids + (size_t)i0 * PT_CVIT_T,
+    const int rc = forward_batch(e, *M, gray + (long long)i0 * lstride, pitch, jstride, lstride, nb, ids + (size_t)i0 * PT_CVIT_T,
                                  maxlogit ? maxlogit + (size_t)i0 * PT_CVIT_T : nullptr, s, h_text_w ? h_text_w + i0 : nullptr);
     if (rc != PT_OK) return rc;
     i0 += nb;

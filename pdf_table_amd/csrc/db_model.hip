@@ -16,7 +16,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -37,7 +37,7 @@ struct DbWeights {
 int get(const PtModel& m, const std::string& name, const PtTensor** out, bool optional = false) {
   *out = m.find(name);
   if (!*out && !optional) {
-    pt_set_error("weight blob lacks tensor '%s'", name.c_str());
+    pt_set_error("DB-ResNet18 weight blob lacks tensor '%s'", name.c_str());
     return PT_ERR_FORMAT;
   }
   return PT_OK;
@@ -78,9 +78,6 @@ int bind(const PtModel& m, DbWeights& w, bool x3, bool f16) {
   return PT_OK;
 }
 
-inline const bf16_t* W(const PtTensor* t) { return reinterpret_cast<const bf16_t*>(t->d_ptr); }
-inline const float* Bv(const PtTensor* t) { return reinterpret_cast<const float*>(t->d_ptr); }
-
 struct Bufs {
   bf16_t *s, *p, *t[4], *a[4], *c[4], *d[4], *in5, *o4, *o3, *o2, *fuse, *y0, *y1, *f8, *p2, *yb;
 };
@@ -91,16 +88,12 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float
                       int* bitmap_done) {
   if (bitmap_done) *bitmap_done = 0;
   PT_REQUIRE(H % 32 == 0 && W_ % 32 == 0 && H > 0 && W_ > 0, "det net: input %dx%d must be multiples of 32", H, W_);
-  auto it = e->models.find(PT_MODEL_DB_RESNET18);
-  if (it == e->models.end()) {
-    pt_set_error("DB-ResNet18 weights not loaded (pt_weights_load(PT_MODEL_DB_RESNET18))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_DB_RESNET18")) return PT_ERR_STATE;
+  const PtModel* M = pt_find_model(e, PT_MODEL_DB_RESNET18, "DB-ResNet18", "PT_MODEL_DB_RESNET18");
+  if (!M) return PT_ERR_STATE;
   const int x3 = pt_split(e) ? 1 : 0;
   const int m = x3 ? 2 : 1;  // channel-group multiplier of every activation buffer
   DbWeights w;
-  const int f16 = pt_f16x2(e) && it->second.find("bin0.wh") ? 1 : 0;      // blobs packed without the fp16 tiles run as BF16X3
+  const int f16 = pt_f16x2(e) && M->find("bin0.wh") ? 1 : 0;      // blobs packed without the fp16 tiles run as BF16X3
   if (pt_f16x2(e) && !f16) {
     static bool said = false;      // once per process: the caller asked for F16X2 and gets BF16X3 numbers and speed
     if (!said) {
@@ -109,7 +102,7 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float
                       "(pack with x3=True to get them)\n");
     }
   }
-  int rc = bind(it->second, w, x3 != 0, f16 != 0);
+  int rc = bind(*M, w, x3 != 0, f16 != 0);
   if (rc != PT_OK) return rc;
 
   const int ch[4] = {64, 128, 256, 512};
@@ -124,14 +117,8 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float
   const char* fb_env = getenv("PT_DB_FUSE_BIN0");
   const bool fused0 = fused2 && !(fb_env && atoi(fb_env) == 0) && w.bin0p_w && w.bin0p_b && w.bin0c_w && w.bin0c_b;
   Bufs bf;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    e->arenas[PT_ARENA_DET].reset();
-    bool ok = true;
-    auto take = [&](size_t elems) {
-      void* p = e->arenas[PT_ARENA_DET].take(elems * m * sizeof(bf16_t));
-      if (!p) ok = false;
-      return reinterpret_cast<bf16_t*>(p);
-    };
+  rc = pt_arena_plan(e, PT_ARENA_DET, "det net", [&](auto&& take_bytes) {
+    auto take = [&](size_t elems) { return reinterpret_cast<bf16_t*>(take_bytes(elems * m * sizeof(bf16_t))); };
     const size_t px2 = (size_t)n * (H / 2) * (W_ / 2), px4 = px2 / 4;
     bf.s = take(px2 * 64);
     bf.p = take(px4 * 64);
@@ -148,25 +135,15 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float
     bf.y1 = take(px2 * 64);
     bf.f8 = bf.p2 = bf.yb = nullptr;
     if (fused0) { bf.f8 = take(px4 / 4 * 192); bf.p2 = take(px4 * 64); bf.yb = take(px4 * 64); }
-    if (ok) break;
-    if (attempt == 1) {
-      pt_set_error("activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-    PT_HIP_CHECK(hipDeviceSynchronize());
-    if (e->arenas[PT_ARENA_DET].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_DET].base));
-    e->arenas[PT_ARENA_DET].base = nullptr;
-    const size_t want = pt_arena_round(e->arenas[PT_ARENA_DET].high);
-    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_DET].base), want));
-    e->arenas[PT_ARENA_DET].cap = want;
-  }
+  });
+  if (rc != PT_OK) return rc;
 
 #define RUN(call) do { if ((rc = (call)) != PT_OK) return rc; } while (0)
   // every conv below: out buffer of C channels is laid out [hi(C) | lo(C)] in x3 mode
   auto conv = [&](const bf16_t* in, int hh, int ww, int cin, const PtTensor* wt, const PtTensor* bs, int N, int ks,
                   int stride, bf16_t* out, int out_c, int relu) {
     ConvDesc c;
-    c.in = in; c.B = n; c.H = hh; c.W = ww; c.Cin = cin; c.w = W(wt); c.bias = Bv(bs); c.N = N; c.ks = ks;
+    c.in = in; c.B = n; c.H = hh; c.W = ww; c.Cin = cin; c.w = W(wt); c.bias = F(bs); c.N = N; c.ks = ks;
     c.stride = stride; c.out = out; c.out_cstride = out_c * m; c.relu = relu; c.split = f16 ? 2 : x3; c.out_lo_off = out_c;
     c.xp_store = 1;      // full-line stores where the launch takes the register epilogue (conv_igemm.hip: +0.9 % det-only)
     return c;
@@ -175,9 +152,9 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float
   // PT_STEM_POOL=0 (read per call) keeps the two launches
   const char* sp_env = getenv("PT_STEM_POOL");
   if (!x3 && !(sp_env && atoi(sp_env) == 0)) {
-    RUN(pt_launch_stem7x7_pool(e, x, n, H, W_, W(w.stem_w), Bv(w.stem_b), bf.p, s));
+    RUN(pt_launch_stem7x7_pool(e, x, n, H, W_, W(w.stem_w), F(w.stem_b), bf.p, s));
   } else {
-    RUN(pt_launch_stem7x7(e, x, n, H, W_, W(w.stem_w), Bv(w.stem_b), bf.s, x3, s));
+    RUN(pt_launch_stem7x7(e, x, n, H, W_, W(w.stem_w), F(w.stem_b), bf.s, x3, s));
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "maxpool");
     RUN(pt_launch_maxpool3x3s2(bf.s, n, H / 2, W_ / 2, 64, bf.p, x3, s));
   }
@@ -268,13 +245,13 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float
       fuse_bm = ev ? atoi(ev) : 1;
     }
     uint32_t* bm = (fuse_bm && bitmap && bitmap_done && prob) ? bitmap : nullptr;
-    RUN(pt_launch_db_head_mfma(bf.y0, n, H / 4, W_ / 4, W(w.bin3_w), Bv(w.bin3_b), W(w.bin6_w), Bv(w.bin6_b), prob, logits, s, bm, thresh));
+    RUN(pt_launch_db_head_mfma(bf.y0, n, H / 4, W_ / 4, W(w.bin3_w), F(w.bin3_b), W(w.bin6_w), F(w.bin6_b), prob, logits, s, bm, thresh));
     if (bm) *bitmap_done = 1;
   } else {
     // ConvTranspose2d(64,64,2,2)+BN+ReLU with the final ConvTranspose2d(64,1,2,2)+Sigmoid fused into its epilogue
     ConvDesc c = conv(bf.y0, H / 4, W_ / 4, 64, w.bin3_w, w.bin3_b, 256, 1, 1, bf.y1, 64, 1);
     c.shuffle_cout = 64;
-    c.head_w = w.bin6_w->d_ptr; c.head_b = Bv(w.bin6_b); c.head_prob = prob; c.head_logits = logits;
+    c.head_w = w.bin6_w->d_ptr; c.head_b = F(w.bin6_b); c.head_prob = prob; c.head_logits = logits;
     RUN(pt_launch_conv(e, c, s));
   }
 #undef RUN

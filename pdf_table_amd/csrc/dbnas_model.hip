@@ -16,16 +16,11 @@
 // the GEMM's own channel stride; PReLU(0) = 0 and x * gate keep the padding zero.
 #include <string>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
 namespace {
-
-struct T {
-  bf16_t* p = nullptr;
-  int H = 0, W = 0, C = 0;
-};
 
 // kind (0 conv block, 1 SE), cin, cout, expand ratio, depthwise kernel after folding, stride, SE squeeze factor
 // proxyless.py:107-127: conv_candidates[conv_op_ids[i]] per block; '135'/'35' RepConv fold to k = 5
@@ -42,47 +37,17 @@ const Blk kBlocks[24] = {
 
 inline int pad64(int c) { return (c + 63) / 64 * 64; }
 
-struct Ctx {
-  pt_engine* e;
-  const PtModel* m;
-  hipStream_t s;
-  int n, x3, mul;
-  bool dry, ok;
-  int rc;
-
-  T alloc(int H, int W, int C) {
-    T t;
-    t.H = H; t.W = W; t.C = C;
-    t.p = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_DET].take((size_t)n * H * W * C * mul * sizeof(bf16_t)));
-    if (!t.p) ok = false;
-    return t;
-  }
-  const PtTensor* get(const std::string& name) {
-    const PtTensor* t = m->find(name);
-    if (!t && rc == PT_OK) {
-      pt_set_error("DB-NAS weight blob lacks tensor '%s'", name.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  }
-  bool go() const { return rc == PT_OK && !dry && ok; }
-  const float* F(const PtTensor* t) { return reinterpret_cast<const float*>(t->d_ptr); }
-
+struct Ctx : NetCtx {
   // 1x1 conv (+ folded BN); act 0 none / 1 ReLU / 3 PReLU(slope tensor q.slope); res_mode 1: + res, 2: + nearest-x2(res)
   void pw(const T& in, const std::string& q, int N, const T& out, int act, const T* res = nullptr, int res_mode = 1, int nv = 0) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
     const PtTensor* sl = act == 3 ? get(q + ".slope") : nullptr;
-    if (!go()) return;
     ConvDesc c;
-    c.in = in.p; c.B = n; c.H = in.H; c.W = in.W; c.Cin = in.C;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = F(b);
-    c.N = N; c.ks = 1; c.stride = 1; c.relu = act; c.split = x3; c.n_valid = nv;
+    if (!conv_desc(c, in, q, N, 1, 1, act)) return;
+    c.n_valid = nv;
     if (sl) c.slope = F(sl);
-    c.out = out.p; c.out_cstride = out.C * mul; c.out_lo_off = out.C;
+    to_map(c, out);
     if (res) { c.res = res->p; c.res_mode = res_mode; }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
   T dw(const T& in, const std::string& q, int k, int stride, int act) {
     const int pad = k / 2;
@@ -105,24 +70,13 @@ struct Ctx {
 int pt_dbnas_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* prob, float* logits, hipStream_t s) {
   PT_REQUIRE(x && (prob || logits) && n > 0, "DB-NAS net: null pointer");
   PT_REQUIRE(H % 32 == 0 && W % 32 == 0 && H > 0 && W > 0, "DB-NAS net: input %dx%d must be multiples of 32", H, W);
-  auto it = e->models.find(PT_MODEL_DB_NAS);
-  if (it == e->models.end()) {
-    pt_set_error("DB-NAS weights not loaded (pt_weights_load(PT_MODEL_DB_NAS))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_DB_NAS")) return PT_ERR_STATE;
+  const PtModel* m = pt_find_model(e, PT_MODEL_DB_NAS, "DB-NAS", "PT_MODEL_DB_NAS");
+  if (!m) return PT_ERR_STATE;
   Ctx c;
-  c.e = e; c.m = &it->second; c.s = s; c.n = n;
-  c.x3 = pt_split(e) ? 1 : 0;
-  c.mul = c.x3 ? 2 : 1;
-  c.rc = PT_OK;
-  for (int pass = 0; pass < 2; ++pass) {
-    c.dry = pass == 0;
-    c.ok = true;
-    e->arenas[PT_ARENA_DET].reset();
-    float* gate = reinterpret_cast<float*>(e->arenas[PT_ARENA_DET].take((size_t)n * 512 * sizeof(float)));
-    float* part = reinterpret_cast<float*>(e->arenas[PT_ARENA_DET].take((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float)));
-    if (!gate || !part) c.ok = false;
+  c.init(e, m, "DB-NAS", s, n, PT_ARENA_DET);
+  return pt_plan_then_launch(c, "DB-NAS net", [&]() -> int {
+    float* gate = c.take<float>((size_t)n * 512 * sizeof(float));
+    float* part = c.take<float>((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float));
     T t = c.alloc(H / 2, W / 2, 64);
     {
       const PtTensor* w = c.get("stem.wf32");
@@ -180,23 +134,8 @@ int pt_dbnas_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, flo
         if (r != PT_OK) c.rc = r;
       }
     }
-    if (c.rc != PT_OK) return c.rc;
-    if (pass == 0) {
-      if (c.ok) continue;
-      PT_HIP_CHECK(hipDeviceSynchronize());
-      if (e->arenas[PT_ARENA_DET].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_DET].base));
-      e->arenas[PT_ARENA_DET].base = nullptr;
-      const size_t want = pt_arena_round(e->arenas[PT_ARENA_DET].high);
-      PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_DET].base), want));
-      e->arenas[PT_ARENA_DET].cap = want;
-      continue;
-    }
-    if (!c.ok) {
-      pt_set_error("DB-NAS net: activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-  }
-  return PT_OK;
+    return c.rc;
+  });
 }
 
 }  // namespace PT_FMT_NS

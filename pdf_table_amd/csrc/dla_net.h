@@ -9,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -20,65 +20,29 @@ int pt_launch_dla_thin_chain(pt_engine* e, const bf16_t* in, int B, int H, int W
 
 namespace {
 
-struct T {
-  bf16_t* p = nullptr;
-  int H = 0, W = 0, C = 0;
-};
-
-struct DlaCtx {
-  pt_engine* e;
-  const PtModel* m;
-  const char* what = "Lore DLA-34";   // the model named in a missing-tensor error
-  hipStream_t s;
-  int n, x3, mul;
-  bool dry;      // planning pass: only arena accounting, no launches
-  bool ok;       // arena had room for everything so far
-  int rc;
+struct DlaCtx : NetCtx {
   bf16_t* cols = nullptr;   // shared DCN column scratch (largest site)
   float* om = nullptr;      // shared offset/mask scratch, fp32 [pixel][32]
   const int* ylimit = nullptr;   // when set: convs skip output tiles at rows >= *ylimit (sparse-head mosaics)
   double alg_scale = 1.0;        // roofline accounting: fraction of a launch's output pixels the algorithm needs
 
-  T alloc(int H, int W, int C) {
-    T t;
-    t.H = H; t.W = W; t.C = C;
-    t.p = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_TSR].take((size_t)n * H * W * C * mul * sizeof(bf16_t)));
-    if (!t.p) ok = false;
-    return t;
-  }
-  const PtTensor* get(const std::string& name) {
-    const PtTensor* t = m->find(name);
-    if (!t && rc == PT_OK) {
-      pt_set_error("%s weight blob lacks tensor '%s'", what, name.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  }
   // conv with folded bias; q = weight name prefix; N = GEMM width (multiple of 64), nv = channels stored (0 = N)
   void conv(const T& in, const std::string& q, int N, int ks, int stride, const T& out, int relu, const T* res = nullptr,
             int nv = 0, float* out_f32 = nullptr, int f32_cs = 0, int cin_override = 0, int alg_n = 0) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK || dry || !ok) return;
     ConvDesc c;
-    c.in = in.p; c.B = n; c.H = in.H; c.W = in.W; c.Cin = cin_override ? cin_override : in.C;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = ks; c.stride = stride; c.relu = relu; c.split = x3; c.n_valid = nv; c.ylimit = ylimit;
-    c.alg_n = alg_n; c.alg_scale = alg_scale;
-    if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = f32_cs;
-    } else {
-      c.out = out.p; c.out_cstride = out.C * mul; c.out_lo_off = out.C;
-    }
+    if (!conv_desc(c, in, q, N, ks, stride, relu)) return;
+    if (cin_override) c.Cin = cin_override;
+    c.n_valid = nv; c.ylimit = ylimit; c.alg_n = alg_n; c.alg_scale = alg_scale;
+    if (out_f32) to_f32(c, out_f32, f32_cs);
+    else to_map(c, out);
     if (res) { c.res = res->p; c.res_mode = 1; }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
   // 1x1 conv over the channel concatenation of `ins` (never materialised): one GEMM whose K walks the tensors
   void conv_cat(const std::vector<T>& ins, const std::string& q, int N, const T& out, int relu) {
     const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
     const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK || dry || !ok) return;
+    if (!go()) return;
     ConvDesc c;
     c.in = ins[0].p; c.B = n; c.H = ins[0].H; c.W = ins[0].W;
     c.nseg = (int)ins.size();
@@ -88,15 +52,14 @@ struct DlaCtx {
       c.Cin += ins[i].C;
       if (i) c.in_more[i - 1] = ins[i].p;
     }
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
+    c.w = W(w); c.bias = F(b);
     c.N = N; c.ks = 1; c.stride = 1; c.relu = relu; c.split = x3; c.alg_scale = alg_scale;
-    c.out = out.p; c.out_cstride = out.C * mul; c.out_lo_off = out.C;
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    to_map(c, out);
+    launch(c);
   }
   T maxpool2(const T& x) {
     T o = alloc(x.H / 2, x.W / 2, x.C);
-    if (rc == PT_OK && !dry && ok) {
+    if (go()) {
       e->prof.next_bytes = (double)n * x.H * x.W * x.C * 2.0 * mul * 1.25;
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "maxpool2x2");
       const int r = pt_launch_maxpool_kxk(x.p, n, x.H, x.W, x.C, 2, 2, 0, x3, o.p, s);
@@ -151,22 +114,17 @@ static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
     layers[1] = c.alloc(H / 2, W / 2, 32);
     const PtTensor *ws = c.get("base_layer.w"), *bs = c.get("base_layer.b"), *w0 = c.get("level0.wt"), *b0 = c.get("level0.bt"),
                    *w1 = c.get("level1.wt"), *b1 = c.get("level1.bt");
-    if (c.rc == PT_OK && !c.dry && c.ok) {
-      const int r = pt_launch_dla_thin_chain(e, x, n, H, W, reinterpret_cast<const bf16_t*>(ws->d_ptr), reinterpret_cast<const float*>(bs->d_ptr),
-                                             reinterpret_cast<const bf16_t*>(w0->d_ptr), reinterpret_cast<const float*>(b0->d_ptr),
-                                             reinterpret_cast<const bf16_t*>(w1->d_ptr), reinterpret_cast<const float*>(b1->d_ptr), layers[1].p, s);
+    if (c.go()) {
+      const int r = pt_launch_dla_thin_chain(e, x, n, H, W, c.W(ws), c.F(bs), c.W(w0), c.F(b0), c.W(w1), c.F(b1), layers[1].p, s);
       if (r != PT_OK) c.rc = r;
     }
   } else {
     T t0 = c.alloc(H, W, 16);
-    if (!c.dry && c.ok) {
-      const PtTensor* w = c.get(c.x3 ? "base_layer.w3" : "base_layer.w");
-      const PtTensor* b = c.get("base_layer.b");
-      if (c.rc == PT_OK) {
-        const int r = pt_launch_stem7x7(e, x, n, H, W, reinterpret_cast<const bf16_t*>(w->d_ptr),
-                                        reinterpret_cast<const float*>(b->d_ptr), t0.p, c.x3, s, 1, 16);
-        if (r != PT_OK) c.rc = r;
-      }
+    const PtTensor* w = c.get(c.x3 ? "base_layer.w3" : "base_layer.w");
+    const PtTensor* b = c.get("base_layer.b");
+    if (c.go()) {
+      const int r = pt_launch_stem7x7(e, x, n, H, W, c.W(w), c.F(b), t0.p, c.x3, s, 1, 16);
+      if (r != PT_OK) c.rc = r;
     }
     layers[0] = c.alloc(H, W, 16);
     layers[1] = c.alloc(H / 2, W / 2, 32);
@@ -174,9 +132,8 @@ static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
       const std::string q = lv1 ? "level1" : "level0";
       const PtTensor* w = c.get(q + (c.x3 ? ".wt3" : ".wt"));
       const PtTensor* b = c.get(q + ".bt");
-      if (c.rc == PT_OK && !c.dry && c.ok) {
-        const int r = pt_launch_conv3x3_c16(e, lv1 ? layers[0].p : t0.p, reinterpret_cast<const bf16_t*>(w->d_ptr),
-                                            reinterpret_cast<const float*>(b->d_ptr), layers[lv1].p, n, H, W, lv1 ? 32 : 16,
+      if (c.go()) {
+        const int r = pt_launch_conv3x3_c16(e, lv1 ? layers[0].p : t0.p, c.W(w), c.F(b), layers[lv1].p, n, H, W, lv1 ? 32 : 16,
                                             lv1 ? 2 : 1, c.x3, s);
         if (r != PT_OK) c.rc = r;
       }
@@ -185,17 +142,6 @@ static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
   for (int l = 2; l < 6; ++l)
     layers[l] = c.tree("level" + std::to_string(l), lv[l], layers[l - 1], ch[l - 1], ch[l], 2, l > 2, {});
   return layers;
-}
-
-// end of the arena planning pass (pass 0): if everything fitted, go on; otherwise grow PT_ARENA_TSR to the high-water mark
-static int dla_arena_grow(pt_engine* e) {
-  PT_HIP_CHECK(hipDeviceSynchronize());
-  if (e->arenas[PT_ARENA_TSR].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_TSR].base));
-  e->arenas[PT_ARENA_TSR].base = nullptr;
-  const size_t want = pt_arena_round(e->arenas[PT_ARENA_TSR].high);
-  PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_TSR].base), want));
-  e->arenas[PT_ARENA_TSR].cap = want;
-  return PT_OK;
 }
 
 }  // namespace

@@ -17,66 +17,27 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
 namespace {
 
-struct T {
-  bf16_t* p = nullptr;
-  int H = 0, W = 0, C = 0;
-};
-
-struct Ctx {
-  pt_engine* e;
-  const PtModel* m;
-  hipStream_t s;
-  int n, x3, mul;
-  bool dry, ok;
-  int rc;
+struct Ctx : NetCtx {
   float* gate = nullptr;
   float* part = nullptr;      // PT_SE_CHUNKS * n * 512 floats: two-level average pool of the SE blocks (null: single-workgroup scan)
-  const char* what = "PicoDet";
-  int arena = PT_ARENA_LAYOUT;  // activation arena of the net (PT_ARENA_CLS: the line classifier of pt_cls_forward_lines_direct)
-
-  T alloc(int H, int W, int C) {
-    T t;
-    t.H = H; t.W = W; t.C = C;
-    t.p = reinterpret_cast<bf16_t*>(e->arenas[arena].take((size_t)n * H * W * C * mul * sizeof(bf16_t)));
-    if (!t.p) ok = false;
-    return t;
-  }
-  const PtTensor* get(const std::string& name) {
-    const PtTensor* t = m->find(name);
-    if (!t && rc == PT_OK) {
-      pt_set_error("%s weight blob lacks tensor '%s'", what, name.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  }
-  bool go() const { return rc == PT_OK && !dry && ok; }
-  const float* F(const PtTensor* t) { return reinterpret_cast<const float*>(t->d_ptr); }
 
   // 1x1 conv (+ folded BN) with activation act (0 none, 2 hardswish); rep: nearest replicate factor of the stores;
   // res: added before the activation; nv: stored channels; out_f32: fp32 [.., f32_cs] output
   void pw(const T& in, const std::string& q, int N, const T& out, int act, const T* res = nullptr, int rep = 1, int nv = 0,
           float* out_f32 = nullptr, int f32_cs = 0) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (!go()) return;
     ConvDesc c;
-    c.in = in.p; c.B = n; c.H = in.H; c.W = in.W; c.Cin = in.C;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = F(b);
-    c.N = N; c.ks = 1; c.stride = 1; c.relu = act; c.split = x3; c.n_valid = nv; c.rep = rep;
-    if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = f32_cs;
-    } else {
-      c.out = out.p; c.out_cstride = out.C * mul; c.out_lo_off = out.C;
-    }
+    if (!conv_desc(c, in, q, N, 1, 1, act)) return;
+    c.n_valid = nv; c.rep = rep;
+    if (out_f32) to_f32(c, out_f32, f32_cs);
+    else to_map(c, out);
     if (res) { c.res = res->p; c.res_mode = 1; }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
   T dw(const T& in, const std::string& q, int k, int stride, int act) {     // stride: s or (sy << 8) | sx
     const int pad = k / 2, sy = stride > 255 ? stride >> 8 : stride, sx = stride > 255 ? stride & 255 : stride;
@@ -111,7 +72,7 @@ struct Ctx {
     if (!go()) return true;
     ConvDesc c;
     c.B = n; c.H = in.H; c.W = in.W; c.Cin = in.C;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = F(b);
+    c.w = W(w); c.bias = F(b);
     c.N = N; c.ks = 1; c.stride = 1; c.relu = act_pw; c.n_valid = nv;
     c.out = out.p; c.out_cstride = out.C; c.out_lo_off = out.C;
     const int r = pt_launch_dwpw(e, in.p, n, in.H, in.W, in.C, F(dww), F(dwb), k, 1, act_dw, c, s);
@@ -216,26 +177,15 @@ int pt_picodet_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, f
                           hipStream_t s) {
   PT_REQUIRE(x && h0 && h1 && h2 && h3 && n > 0, "layout net: null pointer");
   PT_REQUIRE(H % 32 == 0 && W % 32 == 0 && H > 0 && W > 0, "layout net: input %dx%d must be multiples of 32", H, W);
-  auto it = e->models.find(PT_MODEL_PICODET);
-  if (it == e->models.end()) {
-    pt_set_error("PicoDet weights not loaded (pt_weights_load(PT_MODEL_PICODET))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_PICODET")) return PT_ERR_STATE;
+  const PtModel* m = pt_find_model(e, PT_MODEL_PICODET, "PicoDet", "PT_MODEL_PICODET");
+  if (!m) return PT_ERR_STATE;
   Ctx c;
-  c.e = e; c.m = &it->second; c.s = s; c.n = n;
-  c.x3 = pt_split(e) ? 1 : 0;
-  c.mul = c.x3 ? 2 : 1;
-  c.rc = PT_OK;
+  c.init(e, m, "PicoDet", s, n, PT_ARENA_LAYOUT);
   float* heads[4] = {h0, h1, h2, h3};
   static const int st22[4] = {2, 2, 2, 2};
-  for (int pass = 0; pass < 2; ++pass) {
-    c.dry = pass == 0;
-    c.ok = true;
-    e->arenas[PT_ARENA_LAYOUT].reset();
-    c.gate = reinterpret_cast<float*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)n * 512 * sizeof(float)));
-    c.part = reinterpret_cast<float*>(e->arenas[PT_ARENA_LAYOUT].take((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float)));
-    if (!c.gate || !c.part) c.ok = false;
+  return pt_plan_then_launch(c, "layout net", [&]() -> int {
+    c.gate = c.take<float>((size_t)n * 512 * sizeof(float));
+    c.part = c.take<float>((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float));
     T feats[3];
     lcnet_backbone(c, x, H, W, st22, feats);
     // ---- CSP-PAN (csp_pan.py:305-345)
@@ -275,23 +225,8 @@ int pt_picodet_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, f
       }
       c.pw(f, "head." + std::to_string(l) + ".out", 64, T(), 0, nullptr, 1, 40, heads[l], 40);
     }
-    if (c.rc != PT_OK) return c.rc;
-    if (pass == 0) {
-      if (c.ok) continue;
-      PT_HIP_CHECK(hipDeviceSynchronize());
-      if (e->arenas[PT_ARENA_LAYOUT].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_LAYOUT].base));
-      e->arenas[PT_ARENA_LAYOUT].base = nullptr;
-      const size_t want = pt_arena_round(e->arenas[PT_ARENA_LAYOUT].high);
-      PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_LAYOUT].base), want));
-      e->arenas[PT_ARENA_LAYOUT].cap = want;
-      continue;
-    }
-    if (!c.ok) {
-      pt_set_error("layout net: activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-  }
-  return PT_OK;
+    return c.rc;
+  });
 }
 
 // PP-LCNet classifier (`PPLCNet.forward`, cls_pp_lcnet.py:262-283).  x: NHWC4 bf16 [n, H, W, 4] (8 channels in BF16X3
@@ -303,48 +238,32 @@ int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H
                            int* n_classes, hipStream_t s, int arena) {
   PT_REQUIRE(x && logits && n > 0 && H > 0 && W > 0 && slot >= 0 && slot < PT_CLS_SLOTS &&
              (arena == PT_ARENA_LAYOUT || arena == PT_ARENA_CLS), "PP-LCNet: bad arguments");
-  auto it = e->models.find(PT_MODEL_PPLCNET + slot);
-  if (it == e->models.end()) {
-    pt_set_error("PP-LCNet weights not loaded (pt_weights_load(PT_MODEL_PPLCNET + %d))", slot);
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_PPLCNET")) return PT_ERR_STATE;
+  const PtModel* m = pt_find_model(e, PT_MODEL_PPLCNET + slot, "PP-LCNet", "PT_MODEL_PPLCNET", slot);
+  if (!m) return PT_ERR_STATE;
   Ctx c;
-  c.e = e; c.m = &it->second; c.s = s; c.n = n;
-  c.x3 = pt_split(e) ? 1 : 0;
-  c.mul = c.x3 ? 2 : 1;
-  c.rc = PT_OK;
-  c.what = "PP-LCNet";
-  c.arena = arena;
-  PtArena& A = e->arenas[arena];
+  c.init(e, m, "PP-LCNet", s, n, arena);
   const PtTensor* nc = c.get("fc.nclass");
   if (!nc) return c.rc;
   if (n_classes) *n_classes = (int)nc->dims[0];
   const int st22[4] = {2, 2, 2, 2}, st21[4] = {(2 << 8) | 1, (2 << 8) | 1, (2 << 8) | 1, (2 << 8) | 1};
   const int rows = (n + 31) / 32 * 32;
-  for (int pass = 0; pass < 2; ++pass) {
-    c.dry = pass == 0;
-    c.ok = true;
-    A.reset();
-    c.gate = reinterpret_cast<float*>(A.take((size_t)n * 512 * sizeof(float)));
-    float* part = reinterpret_cast<float*>(A.take((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float)));
-    c.part = part;
-    if (!c.gate || !part) c.ok = false;
+  return pt_plan_then_launch(c, "PP-LCNet", [&]() -> int {
+    c.gate = c.take<float>((size_t)n * 512 * sizeof(float));
+    c.part = c.take<float>((size_t)n * PT_SE_CHUNKS * 512 * sizeof(float));
     T feats[3];
     T t = lcnet_backbone(c, x, H, W, textline ? st21 : st22, feats);
     // avg_pool -> last_conv (1x1, no bias) + hardswish -> fc: the pooled vectors form a [rows/32, 32] "image" of 512 channels
     const int keep = c.n;
     T mean;
     mean.H = rows / 32; mean.W = 32; mean.C = 512;
-    mean.p = reinterpret_cast<bf16_t*>(A.take((size_t)rows * 512 * c.mul * sizeof(bf16_t)));
+    mean.p = c.take<bf16_t>((size_t)rows * 512 * c.mul * sizeof(bf16_t));
     T hid;
     hid.H = rows / 32; hid.W = 32; hid.C = 1280;
-    hid.p = reinterpret_cast<bf16_t*>(A.take((size_t)rows * 1280 * c.mul * sizeof(bf16_t)));
-    float* lg = reinterpret_cast<float*>(A.take((size_t)rows * 16 * sizeof(float)));
-    if (!mean.p || !hid.p || !lg) c.ok = false;
+    hid.p = c.take<bf16_t>((size_t)rows * 1280 * c.mul * sizeof(bf16_t));
+    float* lg = c.take<float>((size_t)rows * 16 * sizeof(float));
     if (c.go()) {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "pplcnet avgpool");
-      const int r = pt_launch_chan_mean(t.p, n, t.H * t.W, 512, c.x3, part, mean.p, rows, s);
+      const int r = pt_launch_chan_mean(t.p, n, t.H * t.W, 512, c.x3, c.part, mean.p, rows, s);
       if (r != PT_OK) c.rc = r;
     }
     c.n = 1;     // the two head GEMMs see one [rows/32, 32] map
@@ -352,23 +271,8 @@ int pt_pplcnet_forward_net(pt_engine* e, int slot, const bf16_t* x, int n, int H
     c.pw(hid, "fc", 64, T(), 0, nullptr, 1, 16, lg, 16);
     c.n = keep;
     if (c.go()) PT_HIP_CHECK(hipMemcpyAsync(logits, lg, (size_t)n * 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (c.rc != PT_OK) return c.rc;
-    if (pass == 0) {
-      if (c.ok) continue;
-      PT_HIP_CHECK(hipDeviceSynchronize());
-      if (A.base) PT_HIP_CHECK(hipFree(A.base));
-      A.base = nullptr;
-      const size_t want = pt_arena_round(A.high);
-      PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&A.base), want));
-      A.cap = want;
-      continue;
-    }
-    if (!c.ok) {
-      pt_set_error("PP-LCNet: activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-  }
-  return PT_OK;
+    return c.rc;
+  });
 }
 
 }  // namespace PT_FMT_NS

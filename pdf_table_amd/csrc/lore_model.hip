@@ -36,16 +36,14 @@ struct Ctx : DlaCtx {
       const PtTensor* b = get(q + ".dcn.b");
       const PtTensor* ow = om_inside ? get(q + (x3 ? ".om.w3" : ".om.w")) : nullptr;
       const PtTensor* ob = om_inside ? get(q + ".om.b") : nullptr;
-      if (rc == PT_OK && !dry && ok) {
-        const int r = pt_launch_dcn_fused(e, x.p, om, reinterpret_cast<const bf16_t*>(w->d_ptr),
-                                          reinterpret_cast<const float*>(b->d_ptr), o.p, n, x.H, x.W, x.C, cout, x3, 1, s,
-                                          ow ? reinterpret_cast<const bf16_t*>(ow->d_ptr) : nullptr, ob ? reinterpret_cast<const float*>(ob->d_ptr) : nullptr);
+      if (go()) {
+        const int r = pt_launch_dcn_fused(e, x.p, om, W(w), F(b), o.p, n, x.H, x.W, x.C, cout, x3, 1, s, ow ? W(ow) : nullptr, ob ? F(ob) : nullptr);
         if (r != PT_OK) rc = r;
       }
       return o;
     }
     // two-kernel form (PT_DCN_FUSED=0): columns through HBM, then a 1x1 GEMM
-    if (rc == PT_OK && !dry && ok) {
+    if (go()) {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "dcn im2col");
       const int r = pt_launch_dcn_im2col(x.p, om, cols, n, x.H, x.W, x.C, x3, s);
       if (r != PT_OK) rc = r;
@@ -64,13 +62,12 @@ struct Ctx : DlaCtx {
       const int f = up_f[j];
       T u = alloc(p.H * f, p.W * f, o_ch);
       const PtTensor* wu = get(q + ".up_" + js + ".wf32");
-      if (rc == PT_OK && !dry && ok) {
+      if (go()) {
         e->prof.next_bytes = (double)n * p.H * p.W * o_ch * 2.0 * mul * (1.0 + 2.0 * f * f);      // in once, skip + out at f x f the pixels
         char label[48];
         snprintf(label, sizeof(label), "dw convT up + add %d @%dx%d", o_ch, p.H * f, p.W * f);
         PtProfScope ps(e, s, PT_PROF_OTHER, 0, label);
-        const int r = pt_launch_dwconvt_up_add(p.p, reinterpret_cast<const float*>(wu->d_ptr), layers[i - 1].p, u.p, n,
-                                               p.H, p.W, o_ch, f, x3, s);
+        const int r = pt_launch_dwconvt_up_add(p.p, F(wu), layers[i - 1].p, u.p, n, p.H, p.W, o_ch, f, x3, s);
         if (r != PT_OK) rc = r;
       }
       layers[i] = dcn(q + ".node_" + js, u, o_ch);
@@ -93,31 +90,20 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
                         float* cr, float* reg, const SparseArgs* sp, hipStream_t s) {
   PT_REQUIRE(H % 32 == 0 && W % 32 == 0 && H > 0 && W > 0, "Lore net: input %dx%d must be multiples of 32", H, W);
   PT_REQUIRE(x && n > 0 && (sp || (hm && st && wh && ax && cr && reg)), "Lore net: null pointer");
-  auto it = e->models.find(PT_MODEL_LORE_DLA34);
-  if (it == e->models.end()) {
-    pt_set_error("Lore DLA-34 weights not loaded (pt_weights_load(PT_MODEL_LORE_DLA34))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_LORE_DLA34")) return PT_ERR_STATE;
+  const PtModel* m = pt_find_model(e, PT_MODEL_LORE_DLA34, "Lore DLA-34", "PT_MODEL_LORE_DLA34");
+  if (!m) return PT_ERR_STATE;
   Ctx c;
-  c.e = e; c.m = &it->second; c.s = s; c.n = n;
-  c.x3 = pt_split(e) ? 1 : 0;
-  c.mul = c.x3 ? 2 : 1;
-  c.rc = PT_OK;
+  c.init(e, m, "Lore DLA-34", s, n, PT_ARENA_TSR);
   float* heads[6] = {hm, st, wh, ax, cr, reg};
   const char* hname[6] = {"hm", "st", "wh", "ax", "cr", "reg"};
   const int hcs[6] = {8, 8, 8, 256, 256, 8};
   const int hreal[6] = {2, 8, 8, 256, 256, 2};     // the heads' real channel counts (roofline accounting)
 
-  for (int pass = 0; pass < 2; ++pass) {
-    c.dry = pass == 0;     // pass 0 only plans the arena (and grows it if needed), pass 1 launches
-    c.ok = true;
-    e->arenas[PT_ARENA_TSR].reset();
+  return pt_plan_then_launch(c, "Lore net", [&]() -> int {
     // shared DCN scratch: the largest site is 64 channels at H/4 x W/4 (9*64 columns); 128 ch at H/8 is half of it
     const size_t px4 = (size_t)n * (H / 4) * (W / 4);
-    c.cols = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_TSR].take(px4 * 576 * c.mul * sizeof(bf16_t)));
-    c.om = reinterpret_cast<float*>(e->arenas[PT_ARENA_TSR].take(px4 * 32 * sizeof(float)));
-    if (!c.cols || !c.om) c.ok = false;
+    c.cols = c.take<bf16_t>(px4 * 576 * c.mul * sizeof(bf16_t));
+    c.om = c.take<float>(px4 * 32 * sizeof(float));
 
     std::vector<T> layers = dla34_base(c, x, H, W);
 
@@ -136,10 +122,8 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
     c.ida("ida_up", y, 0, 3, 64, f24);
     const T feat = y[2];
     T hid = c.alloc(feat.H, feat.W, 256);
-    if (sp) {      // only `hm` is needed everywhere: the other five heads run on patch mosaics (lore_decode.hip)
-      heads[0] = reinterpret_cast<float*>(e->arenas[PT_ARENA_TSR].take((size_t)n * feat.H * feat.W * 8 * sizeof(float)));
-      if (!heads[0]) c.ok = false;
-    }
+    // only `hm` is needed everywhere: the other five heads run on patch mosaics (lore_decode.hip)
+    if (sp) heads[0] = c.take<float>((size_t)n * feat.H * feat.W * 8 * sizeof(float));
     for (int h = 0; h < 6; ++h) {
       if (sp && h != 0) continue;
       c.conv(feat, std::string(hname[h]) + ".0", 256, 3, 1, hid, 1);
@@ -149,22 +133,21 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
       int rows_ax = 0, rows_cr = 0, rows_cell = 0, rows_corner = 0;
       pt_lore_mosaic_rows(n, &rows_ax, &rows_cr, &rows_cell, &rows_corner);
       const int MW = 32;          // patches per row of the patch image (lore_decode.hip: MOS_PW); a patch = one row of 9 * 64 values
-      auto take = [&](size_t bytes) { void* p_ = e->arenas[PT_ARENA_TSR].take(bytes); if (!p_) c.ok = false; return p_; };
       auto mosaic = [&](int rows, int C) {
         T t;
         t.H = rows; t.W = MW; t.C = C;
-        t.p = reinterpret_cast<bf16_t*>(take(((size_t)rows * MW * C * c.mul + 64) * sizeof(bf16_t)));
+        t.p = c.take<bf16_t>(((size_t)rows * MW * C * c.mul + 64) * sizeof(bf16_t));
         return t;
       };
       T mcell = mosaic(rows_cell, 9 * 64), mcorner = mosaic(rows_corner, 9 * 64), max_ = mosaic(rows_ax, 9 * 64), mcr_ = mosaic(rows_cr, 9 * 64);
       T mhid = mosaic(rows_cr, 256);                 // hidden layer of whichever head is running (rows_cr is the largest)
-      float* o_wh = reinterpret_cast<float*>(take((size_t)rows_cell * MW * 8 * sizeof(float)));
-      float* o_regc = reinterpret_cast<float*>(take((size_t)rows_cell * MW * 8 * sizeof(float)));
-      float* o_st = reinterpret_cast<float*>(take((size_t)rows_corner * MW * 8 * sizeof(float)));
-      float* o_regk = reinterpret_cast<float*>(take((size_t)rows_corner * MW * 8 * sizeof(float)));
-      float* oax = reinterpret_cast<float*>(take((size_t)rows_ax * MW * 256 * sizeof(float)));
-      float* ocr = reinterpret_cast<float*>(take((size_t)rows_cr * MW * 256 * sizeof(float)));
-      if (c.rc == PT_OK && !c.dry && c.ok) {
+      float* o_wh = c.take<float>((size_t)rows_cell * MW * 8 * sizeof(float));
+      float* o_regc = c.take<float>((size_t)rows_cell * MW * 8 * sizeof(float));
+      float* o_st = c.take<float>((size_t)rows_corner * MW * 8 * sizeof(float));
+      float* o_regk = c.take<float>((size_t)rows_corner * MW * 8 * sizeof(float));
+      float* oax = c.take<float>((size_t)rows_ax * MW * 256 * sizeof(float));
+      float* ocr = c.take<float>((size_t)rows_cr * MW * 256 * sizeof(float));
+      if (c.go()) {
         const int keep = c.n;
         // one head on one mosaic: 3x3 (64 -> 256) + ReLU, then 1x1 to nc channels, fp32 out; tiles below `lim` rows exit
         auto head = [&](const T& mos, int rows, const char* name, int nc, float* outp, const int* lim, int real_nc) {
@@ -199,20 +182,8 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
         if (r != PT_OK) return r;
       }
     }
-    if (c.rc != PT_OK) return c.rc;
-    if (pass == 0) {
-      if (c.ok) continue;      // everything fits: next pass launches
-      const int r = dla_arena_grow(e);
-      if (r != PT_OK) return r;
-      continue;
-    }
-    if (!c.ok) {
-      pt_set_error("Lore net: activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-    break;
-  }
-  return PT_OK;
+    return c.rc;
+  });
 }
 
 
@@ -238,46 +209,17 @@ int pt_lore_forward_decode(pt_engine* e, const bf16_t* x, int n, int H, int W, i
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
 
-struct WCtx {
-  pt_engine* e;
-  const PtModel* m;
-  hipStream_t s;
-  int n, x3, mul;
-  bool dry, ok;
-  int rc;
-  T alloc(int H, int W, int C) {
-    T t;
-    t.H = H; t.W = W; t.C = C;
-    t.p = reinterpret_cast<bf16_t*>(e->arenas[PT_ARENA_TSR].take((size_t)n * H * W * C * mul * sizeof(bf16_t)));
-    if (!t.p) ok = false;
-    return t;
-  }
-  const PtTensor* get(const std::string& name) {
-    const PtTensor* t = m->find(name);
-    if (!t && rc == PT_OK) {
-      pt_set_error("Lore wireless weight blob lacks tensor '%s'", name.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  }
+struct WCtx : NetCtx {
   void conv(const T& in, const std::string& q, int N, int ks, int stride, const T& out, int relu, const T* res = nullptr,
             int shuffle = 0, int nv = 0, float* out_f32 = nullptr, int f32_cs = 0) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK || dry || !ok) return;
     ConvDesc c;
-    c.in = in.p; c.B = n; c.H = in.H; c.W = in.W; c.Cin = in.C;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = ks; c.stride = stride; c.relu = relu; c.split = x3; c.n_valid = nv; c.shuffle_cout = shuffle;
+    if (!conv_desc(c, in, q, N, ks, stride, relu)) return;
+    c.n_valid = nv; c.shuffle_cout = shuffle;
     if (shuffle && ks == 3) c.alg_scale = 16.0 / 36.0;   // ConvTranspose2d(k=4,s=2) has 16 taps per (input pixel, Cout); the 3x3 x 4-phase GEMM spends 36
-    if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = f32_cs;
-    } else {
-      c.out = out.p; c.out_cstride = out.C * mul; c.out_lo_off = out.C;
-    }
+    if (out_f32) to_f32(c, out_f32, f32_cs);
+    else to_map(c, out);
     if (res) { c.res = res->p; c.res_mode = 1; }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
 };
 
@@ -287,37 +229,24 @@ int pt_lore_wireless_forward_net(pt_engine* e, const bf16_t* x, int n, int H, in
                                  float* ax, float* cr, float* reg, hipStream_t s) {
   PT_REQUIRE(H % 64 == 0 && W % 64 == 0 && H > 0 && W > 0, "Lore wireless net: input %dx%d must be multiples of 64", H, W);
   PT_REQUIRE(x && hm && st && wh && ax && cr && reg && n > 0, "Lore wireless net: null pointer");
-  auto it = e->models.find(PT_MODEL_LORE_RESNET18);
-  if (it == e->models.end()) {
-    pt_set_error("Lore wireless weights not loaded (pt_weights_load(PT_MODEL_LORE_RESNET18))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_LORE_RESNET18")) return PT_ERR_STATE;
+  const PtModel* m = pt_find_model(e, PT_MODEL_LORE_RESNET18, "Lore wireless", "PT_MODEL_LORE_RESNET18");
+  if (!m) return PT_ERR_STATE;
   WCtx c;
-  c.e = e; c.m = &it->second; c.s = s; c.n = n;
-  c.x3 = pt_split(e) ? 1 : 0;
-  c.mul = c.x3 ? 2 : 1;
-  c.rc = PT_OK;
+  c.init(e, m, "Lore wireless", s, n, PT_ARENA_TSR);
   float* heads[6] = {hm, st, wh, ax, cr, reg};
   const char* hname[6] = {"hm", "st", "wh", "ax", "cr", "reg"};
   const int hcs[6] = {8, 8, 8, 256, 256, 8};
   const int planes[4] = {64, 128, 256, 256};
-  for (int pass = 0; pass < 2; ++pass) {
-    c.dry = pass == 0;
-    c.ok = true;
-    e->arenas[PT_ARENA_TSR].reset();
+  return pt_plan_then_launch(c, "Lore wireless net", [&] {
     T s0 = c.alloc(H / 2, W / 2, 64);
-    if (!c.dry && c.ok) {
-      const PtTensor* w = c.get(c.x3 ? "stem.w3" : "stem.w");
-      const PtTensor* b = c.get("stem.b");
-      if (c.rc == PT_OK) {
-        const int r = pt_launch_stem7x7(e, x, n, H, W, reinterpret_cast<const bf16_t*>(w->d_ptr),
-                                        reinterpret_cast<const float*>(b->d_ptr), s0.p, c.x3, s, 2, 0);
-        if (r != PT_OK) c.rc = r;
-      }
+    const PtTensor* w = c.get(c.x3 ? "stem.w3" : "stem.w");
+    const PtTensor* b = c.get("stem.b");
+    if (c.go()) {
+      const int r = pt_launch_stem7x7(e, x, n, H, W, c.W(w), c.F(b), s0.p, c.x3, s, 2, 0);
+      if (r != PT_OK) c.rc = r;
     }
     T x0 = c.alloc(H / 4, W / 4, 64);
-    if (c.rc == PT_OK && !c.dry && c.ok) {
+    if (c.go()) {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "maxpool");
       const int r = pt_launch_maxpool3x3s2(s0.p, n, H / 2, W / 2, 64, x0.p, c.x3, s);
       if (r != PT_OK) c.rc = r;
@@ -365,23 +294,8 @@ int pt_lore_wireless_forward_net(pt_engine* e, const bf16_t* x, int n, int H, in
       }
       c.conv(*in, std::string(hname[h]) + ".out", hcs[h] < 64 ? 64 : hcs[h], 1, 1, T(), 0, nullptr, 0, hcs[h], heads[h], hcs[h]);
     }
-    if (c.rc != PT_OK) return c.rc;
-    if (pass == 0) {
-      if (c.ok) continue;
-      PT_HIP_CHECK(hipDeviceSynchronize());
-      if (e->arenas[PT_ARENA_TSR].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_TSR].base));
-      e->arenas[PT_ARENA_TSR].base = nullptr;
-      const size_t want = pt_arena_round(e->arenas[PT_ARENA_TSR].high);
-      PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_TSR].base), want));
-      e->arenas[PT_ARENA_TSR].cap = want;
-      continue;
-    }
-    if (!c.ok) {
-      pt_set_error("Lore wireless net: activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-  }
-  return PT_OK;
+    return c.rc;
+  });
 }
 
 }  // namespace PT_FMT_NS

@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -207,36 +207,22 @@ __global__ __launch_bounds__(256) void scatter4_kernel(const float* __restrict__
   out[((size_t)tok[2 * t] * PT_TSR_MAX_CELLS + tok[2 * t + 1]) * 4 + c] = x[(size_t)t * 8 + c];
 }
 
-struct P {
-  pt_engine* e;
-  const PtModel* m;
-  hipStream_t s;
-  int Npad, x3, mul, rc;
-  const PtTensor* get(const std::string& n) {
-    const PtTensor* t = m->find(n);
-    if (!t && rc == PT_OK) {
-      pt_set_error("Lore processor weight blob lacks tensor '%s'", n.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  }
+struct P : NetCtx {
+  int Npad;
   // y = x W^T + b over all tokens: x bf16 [Npad, cin] -> bf16 [Npad, out_c] at channel out_coff, or fp32 [Npad, f32_cs]
   void gemm(const bf16_t* x, int cin, const std::string& q, int N, int relu, bf16_t* out, int out_c, int out_coff,
             float* out_f32 = nullptr, int f32_cs = 0, const float* res_f32 = nullptr, int nv = 0) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK) return;
     ConvDesc c;
-    c.in = x; c.B = 1; c.H = Npad / 32; c.W = 32; c.Cin = cin;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = 1; c.stride = 1; c.relu = relu; c.split = x3; c.n_valid = nv;
+    if (!conv_desc(c, rows_map(x, Npad, cin), q, N, 1, 1, relu)) return;
+    c.n_valid = nv;
     if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = f32_cs; c.res_f32 = res_f32;
+      to_f32(c, out_f32, f32_cs);
+      c.res_f32 = res_f32;
     } else {
-      c.out = out; c.out_cstride = out_c * mul; c.out_coff = out_coff; c.out_lo_off = out_c;
+      to_map(c, rows_map(out, Npad, out_c));
+      c.out_coff = out_coff;
     }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
 };
 
@@ -246,12 +232,8 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
                     int use_2dpe, float* d_logic, float* d_stacked, hipStream_t s) {
   PT_REQUIRE(d_logi && h_counts && n_tables > 0 && d_logic && d_stacked, "tsr process: null pointer");
   PT_REQUIRE(!use_2dpe || d_dets, "tsr process: 2-D position embeddings need the cell quads");
-  auto it = e->models.find(PT_MODEL_LORE_PROCESSOR);
-  if (it == e->models.end()) {
-    pt_set_error("Lore processor weights not loaded (pt_weights_load(PT_MODEL_LORE_PROCESSOR))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_LORE_PROCESSOR")) return PT_ERR_STATE;
+  const PtModel* M = pt_find_model(e, PT_MODEL_LORE_PROCESSOR, "Lore processor", "PT_MODEL_LORE_PROCESSOR");
+  if (!M) return PT_ERR_STATE;
   std::vector<int> tok, tiles;
   int N = 0;
   for (int t = 0; t < n_tables; ++t) {
@@ -263,9 +245,7 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
   }
   if (N == 0) return PT_OK;
   P p;
-  p.e = e; p.m = &it->second; p.s = s; p.rc = PT_OK;
-  p.x3 = pt_split(e) ? 1 : 0;
-  p.mul = p.x3 ? 2 : 1;
+  p.init(e, M, "Lore processor", s, 1, PT_ARENA_TSRP);      // n = 1: every GEMM sees the tokens as one [Npad / 32, 32] map
   p.Npad = (N + 127) / 128 * 128;
   const int Npad = p.Npad, x3 = p.x3;
   const PtTensor* meta = p.get("meta");
@@ -273,7 +253,7 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
   int layers[2];
   {
     // the two layer counts: read from the blob once per loaded model (a per-call hipMemcpy would wait for the whole default stream)
-    std::vector<int32_t>& hw = it->second.host_words["meta"];
+    std::vector<int32_t>& hw = e->models[PT_MODEL_LORE_PROCESSOR].host_words["meta"];
     if (hw.size() != 2) {
       hw.assign(2, 0);
       PT_HIP_CHECK(hipMemcpy(hw.data(), meta->d_ptr, 8, hipMemcpyDeviceToHost));
@@ -284,35 +264,19 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
 
   // activations from the arena (grown once if needed)
   const size_t be = sizeof(bf16_t) * p.mul;
-  size_t off = 0;
-  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
-  const size_t o_x = carve((size_t)Npad * 256 * 4), o_x0 = carve((size_t)Npad * 256 * be), o_xb = carve((size_t)Npad * 256 * be),
-               o_qkv = carve((size_t)Npad * 768 * be), o_att = carve((size_t)Npad * 256 * be),
-               o_h = carve((size_t)Npad * 2048 * be), o_cat = carve((size_t)Npad * 512 * be),
-               o_l32 = carve((size_t)Npad * 32 * be), o_le = carve((size_t)Npad * 256 * be),
-               o_lg = carve((size_t)Npad * 8 * 4), o_sk = carve((size_t)Npad * 8 * 4),
-               o_tok = carve(tok.size() * 4), o_tiles = carve(tiles.size() * 4);
-  if (off > e->arenas[PT_ARENA_TSRP].cap) {
-    PT_HIP_CHECK(hipDeviceSynchronize());
-    if (e->arenas[PT_ARENA_TSRP].base) PT_HIP_CHECK(hipFree(e->arenas[PT_ARENA_TSRP].base));
-    e->arenas[PT_ARENA_TSRP].base = nullptr; e->arenas[PT_ARENA_TSRP].cap = 0;
-    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->arenas[PT_ARENA_TSRP].base), off + (1u << 20)));
-    e->arenas[PT_ARENA_TSRP].cap = off + (1u << 20);
-  }
-  char* base = e->arenas[PT_ARENA_TSRP].base;
-  float* x = reinterpret_cast<float*>(base + o_x);
-  bf16_t* x0 = reinterpret_cast<bf16_t*>(base + o_x0);
-  bf16_t* xb = reinterpret_cast<bf16_t*>(base + o_xb);
-  bf16_t* qkv = reinterpret_cast<bf16_t*>(base + o_qkv);
-  bf16_t* att = reinterpret_cast<bf16_t*>(base + o_att);
-  bf16_t* hbuf = reinterpret_cast<bf16_t*>(base + o_h);
-  bf16_t* cat = reinterpret_cast<bf16_t*>(base + o_cat);
-  bf16_t* l32 = reinterpret_cast<bf16_t*>(base + o_l32);
-  bf16_t* le = reinterpret_cast<bf16_t*>(base + o_le);
-  float* lg = reinterpret_cast<float*>(base + o_lg);
-  float* sk = reinterpret_cast<float*>(base + o_sk);
-  int* d_tok = reinterpret_cast<int*>(base + o_tok);
-  int* d_tiles = reinterpret_cast<int*>(base + o_tiles);
+  float *x, *lg, *sk;
+  bf16_t *x0, *xb, *qkv, *att, *hbuf, *cat, *l32, *le;
+  int *d_tok, *d_tiles;
+  const int prc = pt_arena_plan(e, PT_ARENA_TSRP, "tsr process", [&](auto&& take) {
+    auto act = [&](int C) { return reinterpret_cast<bf16_t*>(take((size_t)Npad * C * be)); };
+    x = reinterpret_cast<float*>(take((size_t)Npad * 256 * 4));
+    x0 = act(256); xb = act(256); qkv = act(768); att = act(256); hbuf = act(2048); cat = act(512); l32 = act(32); le = act(256);
+    lg = reinterpret_cast<float*>(take((size_t)Npad * 8 * 4));
+    sk = reinterpret_cast<float*>(take((size_t)Npad * 8 * 4));
+    d_tok = reinterpret_cast<int*>(take(tok.size() * 4));
+    d_tiles = reinterpret_cast<int*>(take(tiles.size() * 4));
+  });
+  if (prc != PT_OK) return prc;
   {
     // token and tile maps go through an engine-owned pinned slot (the vectors die with this call, and a stream synchronise here would
     // make the host wait for everything queued on s)
@@ -331,15 +295,14 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
   {
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr tok prepare");
     hipLaunchKernelGGL(tok_prepare_kernel, dim3(Npad), dim3(256), 0, s, d_logi, d_dets, d_tok, N, use_2dpe,
-                       reinterpret_cast<const float*>(xpe->d_ptr), reinterpret_cast<const float*>(ype->d_ptr), x0, cat, x3);
+                       F(xpe), F(ype), x0, cat, x3);
   }
   auto norm = [&](const std::string& q) {
     const PtTensor* a = q.empty() ? nullptr : p.get(q + ".alpha");
     const PtTensor* b = q.empty() ? nullptr : p.get(q + ".bias");
     if (p.rc != PT_OK) return;
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr norm");
-    hipLaunchKernelGGL(norm_kernel, dim3((Npad + 3) / 4), dim3(256), 0, s, x, a ? reinterpret_cast<const float*>(a->d_ptr) : nullptr,
-                       b ? reinterpret_cast<const float*>(b->d_ptr) : nullptr, xb, Npad, x3);
+    hipLaunchKernelGGL(norm_kernel, dim3((Npad + 3) / 4), dim3(256), 0, s, x, a ? F(a) : nullptr, b ? F(b) : nullptr, xb, Npad, x3);
   };
   auto transformer = [&](const std::string& q, const bf16_t* in, int cin, int nl, float* out4) {
     p.gemm(in, cin, q + ".linear", 256, 0, nullptr, 0, 0, x, 256);

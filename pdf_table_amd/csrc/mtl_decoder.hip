@@ -40,7 +40,7 @@
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -1125,46 +1125,37 @@ struct MtlState {
   int* h_poll = nullptr;        // pinned
 };
 
-struct Ctx {
-  pt_engine* e;
-  const PtModel* m;
-  hipStream_t s;
-  int x3, mul, rc;
+struct Ctx : NetCtx {
   bool rowfused = true;        // false: every Linear on conv_igemm_kernel + mtl_ln_kernel
-  const PtTensor* get(const std::string& n) {
-    const PtTensor* t = m->find(n);
-    if (!t && rc == PT_OK) {
-      pt_set_error("MtlTabNet decoder weight blob lacks tensor '%s'", n.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
+  using NetCtx::F;
+  bool open(pt_engine* e_, hipStream_t s_) {      // false: the decoder blob is not loaded (error set)
+    const PtModel* m_ = pt_find_model(e_, PT_MODEL_MTL_DECODER, "MtlTabNet decoder", "PT_MODEL_MTL_DECODER");
+    if (m_) init(e_, m_, "MtlTabNet decoder", s_, 1, PT_ARENA_TSR);
+    return m_ != nullptr;
   }
   const float* F(const std::string& n) {
     const PtTensor* t = get(n);
-    return t ? reinterpret_cast<const float*>(t->d_ptr) : nullptr;
+    return t ? F(t) : nullptr;
   }
   // y = x W^T + b over `rows` rows (multiple of 128): x bf16 [rows, cin] (hi | lo) -> bf16 [rows, out_cs] or fp32 [rows, f32_cs]
   void gemm(const bf16_t* x, long long rows, int cin, const std::string& q, int N, int relu, bf16_t* out, int out_cs, float* out_f32 = nullptr,
             int f32_cs = 0, const float* res_f32 = nullptr, int nv = 0) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
     if (rc != PT_OK) return;
-    if (fusable(rows, cin, N, out_f32, f32_cs, nv, out_cs)) {
+    if (fusable(rows, cin, N, out_f32, f32_cs, nv, out_cs)) {      // (lin and conv_desc fetch the weights themselves)
       Lin l{x, nullptr, "", q, out, out_f32, res_f32, f32_cs, nv};
       lin(1, &l, rows, cin, N, relu, out_cs, nullptr);
       return;
     }
     ConvDesc c;
-    c.in = x; c.B = 1; c.H = (int)(rows / 32); c.W = 32; c.Cin = cin;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = 1; c.stride = 1; c.relu = relu; c.split = x3; c.n_valid = nv;
+    if (!conv_desc(c, rows_map(x, rows, cin), q, N, 1, 1, relu)) return;
+    c.n_valid = nv;
     if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = f32_cs; c.res_f32 = res_f32;
+      to_f32(c, out_f32, f32_cs);
+      c.res_f32 = res_f32;
     } else {
-      c.out = out; c.out_cstride = out_cs * mul; c.out_coff = 0; c.out_lo_off = out_cs;
+      to_map(c, rows_map(out, rows, out_cs));
     }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    launch(c);
   }
   // one Linear: bf16 rows `x`, or (xf != null) LayerNorm `lnq` of the fp32 rows xf [rows, 512]; weights `q`; bf16 rows `out` or fp32 rows `out_f32` (+ res)
   struct Lin {
@@ -1189,7 +1180,7 @@ struct Ctx {
       const float *g = nullptr, *be = nullptr;
       if (l[b].xf) { g = F(l[b].lnq + ".g"); be = F(l[b].lnq + ".b"); }
       if (rc != PT_OK) return;
-      rb[b] = RowB{l[b].x, l[b].xf, g, be, reinterpret_cast<const bf16_t*>(w->d_ptr), reinterpret_cast<const float*>(bi->d_ptr), l[b].out, l[b].out_f32,
+      rb[b] = RowB{l[b].x, l[b].xf, g, be, W(w), F(bi), l[b].out, l[b].out_f32,
                    l[b].res, l[b].f32_cs, l[b].nv};
     }
     if (nb == 1) rb[1] = rb[0];
@@ -1383,13 +1374,8 @@ void pt_mtl_release(pt_engine* e) {
 }
 
 int pt_mtl_decoder_config(pt_engine* e, int32_t* out13) {
-  auto it = e->models.find(PT_MODEL_MTL_DECODER);
-  if (it == e->models.end()) {
-    pt_set_error("MtlTabNet decoder weights not loaded (pt_weights_load(PT_MODEL_MTL_DECODER))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_MTL_DECODER")) return PT_ERR_STATE;
-  Ctx c{e, &it->second, nullptr, 0, 1, PT_OK};
+  Ctx c;
+  if (!c.open(e, nullptr)) return PT_ERR_STATE;
   Meta mt;
   const int rc = read_meta(c, &mt);
   if (rc != PT_OK) return rc;
@@ -1402,13 +1388,8 @@ int pt_mtl_decoder_config(pt_engine* e, int32_t* out13) {
 int pt_mtl_structure(pt_engine* e, const float* f3, int n, int hw, float* d_tag_logits, float* d_boxes, int32_t* h_lens, int32_t* h_cell_counts,
                      int force_redecode, hipStream_t s) {
   PT_REQUIRE(e && f3 && n > 0 && hw > 0 && hw <= PE_ROWS && d_tag_logits && d_boxes && h_lens && h_cell_counts, "pt_tsr_mtl_structure: bad arguments");
-  auto it = e->models.find(PT_MODEL_MTL_DECODER);
-  if (it == e->models.end()) {
-    pt_set_error("MtlTabNet decoder weights not loaded (pt_weights_load(PT_MODEL_MTL_DECODER))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_MTL_DECODER")) return PT_ERR_STATE;
-  Ctx c{e, &it->second, s, pt_split(e) ? 1 : 0, pt_split(e) ? 2 : 1, PT_OK};
+  Ctx c;
+  if (!c.open(e, s)) return PT_ERR_STATE;
   Meta mt;
   int rc = read_meta(c, &mt);
   if (rc != PT_OK) return rc;
@@ -1658,13 +1639,8 @@ int pt_mtl_cells(pt_engine* e, int total, int32_t* d_cell_ids, float* d_cell_pro
     pt_set_error("pt_tsr_mtl_cells: call pt_tsr_mtl_structure first");
     return PT_ERR_STATE;
   }
-  auto it = e->models.find(PT_MODEL_MTL_DECODER);
-  if (it == e->models.end()) {
-    pt_set_error("MtlTabNet decoder weights not loaded (pt_weights_load(PT_MODEL_MTL_DECODER))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_MTL_DECODER")) return PT_ERR_STATE;
-  Ctx c{e, &it->second, s, st->x3, st->x3 ? 2 : 1, PT_OK};
+  Ctx c;
+  if (!c.open(e, s)) return PT_ERR_STATE;
   PT_REQUIRE((pt_split(e) ? 1 : 0) == st->x3, "pt_tsr_mtl_cells: the precision changed since pt_tsr_mtl_structure");
   Meta mt;
   int rc = read_meta(c, &mt);

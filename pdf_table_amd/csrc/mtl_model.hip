@@ -13,7 +13,7 @@
 
 #include <string>
 
-#include "common.h"
+#include "net_ctx.h"
 
 namespace PT_FMT_NS {
 
@@ -155,67 +155,31 @@ __global__ __launch_bounds__(256) void gc_add_relu_kernel(const bf16_t* __restri
 // x bf16 [n, H, W, 32] (3 real channels, the rest zero; hi/lo mode: [hi 32 | lo 32]) -> f3 fp32 [n, H/8, W/8, 512]
 int pt_mtl_backbone_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W_, float* f3, hipStream_t s) {
   PT_REQUIRE(e && x && f3 && n > 0 && H > 0 && W_ > 0 && H % 8 == 0 && W_ % 8 == 0, "mtl backbone: input %dx%d must be multiples of 8", H, W_);
-  auto it = e->models.find(PT_MODEL_MTL_BACKBONE);
-  if (it == e->models.end()) {
-    pt_set_error("MtlTabNet backbone weights not loaded (pt_weights_load(PT_MODEL_MTL_BACKBONE))");
-    return PT_ERR_STATE;
-  }
-  if (!pt_model_format_ok(it->second, "PT_MODEL_MTL_BACKBONE")) return PT_ERR_STATE;
-  const PtModel& M = it->second;
-  const int x3 = pt_split(e) ? 1 : 0, m = x3 ? 2 : 1;
-  int rc = PT_OK;
-  auto get = [&](const std::string& name) -> const PtTensor* {
-    const PtTensor* t = M.find(name);
-    if (!t && rc == PT_OK) {
-      pt_set_error("MtlTabNet backbone weight blob lacks tensor '%s'", name.c_str());
-      rc = PT_ERR_FORMAT;
-    }
-    return t;
-  };
-  PtArena& A = e->arenas[PT_ARENA_TSR];
+  const PtModel* M = pt_find_model(e, PT_MODEL_MTL_BACKBONE, "MtlTabNet backbone", "PT_MODEL_MTL_BACKBONE");
+  if (!M) return PT_ERR_STATE;
+  NetCtx c;
+  c.init(e, M, "MtlTabNet backbone", s, n, PT_ARENA_TSR);
+  const int x3 = c.x3, m = c.mul;
+  int& rc = c.rc;
+  auto get = [&](const std::string& name) { return c.get(name); };
   const size_t big = (size_t)n * H * W_ * 128;            // the largest activation: conv2's output at full resolution
   bf16_t* buf[4] = {nullptr, nullptr, nullptr, nullptr};
   float *tvec = nullptr, *scratch = nullptr, *part = nullptr;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    A.reset();
-    bool ok = true;
-    for (int i = 0; i < 4; ++i) {
-      buf[i] = reinterpret_cast<bf16_t*>(A.take(big * m * sizeof(bf16_t)));
-      if (!buf[i]) ok = false;
-    }
-    tvec = reinterpret_cast<float*>(A.take((size_t)n * 512 * sizeof(float)));
-    scratch = reinterpret_cast<float*>(A.take((size_t)n * (H / 4) * (W_ / 4) * sizeof(float)));
-    part = reinterpret_cast<float*>(A.take((size_t)n * (((H / 4) * (W_ / 4) + GC_CHUNK - 1) / GC_CHUNK) * 512 * sizeof(float)));
-    if (!tvec || !scratch || !part) ok = false;
-    if (ok) break;
-    if (attempt == 1) {
-      pt_set_error("activation arena allocation failed");
-      return PT_ERR_HIP;
-    }
-    PT_HIP_CHECK(hipDeviceSynchronize());
-    if (A.base) PT_HIP_CHECK(hipFree(A.base));
-    A.base = nullptr;
-    const size_t want = pt_arena_round(A.high);
-    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&A.base), want));
-    A.cap = want;
-  }
+  const int prc = pt_arena_plan(e, PT_ARENA_TSR, "mtl backbone", [&](auto&& take) {
+    for (int i = 0; i < 4; ++i) buf[i] = reinterpret_cast<bf16_t*>(take(big * m * sizeof(bf16_t)));
+    tvec = reinterpret_cast<float*>(take((size_t)n * 512 * sizeof(float)));
+    scratch = reinterpret_cast<float*>(take((size_t)n * (H / 4) * (W_ / 4) * sizeof(float)));
+    part = reinterpret_cast<float*>(take((size_t)n * (((H / 4) * (W_ / 4) + GC_CHUNK - 1) / GC_CHUNK) * 512 * sizeof(float)));
+  });
+  if (prc != PT_OK) return prc;
   auto conv = [&](const bf16_t* in, int hh, int ww, int cin, const std::string& q, int N, int ks, bf16_t* out, int relu, const bf16_t* res,
                   float* out_f32 = nullptr) {
-    const PtTensor* w = get(q + (x3 ? ".w3" : ".w"));
-    const PtTensor* b = get(q + ".b");
-    if (rc != PT_OK) return;
-    ConvDesc c;
-    c.in = in; c.B = n; c.H = hh; c.W = ww; c.Cin = cin;
-    c.w = reinterpret_cast<const bf16_t*>(w->d_ptr); c.bias = reinterpret_cast<const float*>(b->d_ptr);
-    c.N = N; c.ks = ks; c.stride = 1; c.relu = relu; c.split = x3;
-    if (out_f32) {
-      c.out_f32 = out_f32; c.out_cstride = N;
-    } else {
-      c.out = out; c.out_cstride = N * m; c.out_lo_off = N;
-    }
-    if (res) { c.res = res; c.res_mode = 1; }
-    const int r = pt_launch_conv(e, c, s);
-    if (r != PT_OK) rc = r;
+    ConvDesc d;
+    if (!c.conv_desc(d, T{const_cast<bf16_t*>(in), hh, ww, cin}, q, N, ks, 1, relu)) return;
+    if (out_f32) c.to_f32(d, out_f32, N);
+    else c.to_map(d, T{out, hh, ww, N});
+    if (res) { d.res = res; d.res_mode = 1; }
+    c.launch(d);
   };
   // one BasicBlock: in (buf[a]) -> out (returned buffer index); uses the other three buffers as temporaries
   auto block = [&](int a, int hh, int ww, int cin, int planes, const std::string& q, bool gcb) -> int {
@@ -242,7 +206,6 @@ int pt_mtl_backbone_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int
       rc = PT_ERR_FORMAT;
       return t3;
     }
-    auto F = [](const PtTensor* t) { return reinterpret_cast<const float*>(t->d_ptr); };
     {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "mtl gc context");
       const int HW = hh * ww, nchunk = (HW + GC_CHUNK - 1) / GC_CHUNK;
