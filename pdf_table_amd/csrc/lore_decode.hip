@@ -9,7 +9,8 @@
 //
 //   lore_sigmoid_kernel   hm logits -> scores (2 classes)
 //   lore_peaks_kernel     3x3 max-pool equality (-inf padding) + threshold -> (score, index) keys, atomically appended
-//   lore_sort_kernel      one workgroup per list: bitonic sort of <= 16384 64-bit keys in LDS
+//   lore_sort_kernel      one workgroup per list: bitonic sort of <= 16384 64-bit keys in LDS (more peaks than that: the
+//                         first K are selected from the score map by bisection on the key, then sorted)
 //   lore_boxes_kernel     centre + reg, 4 corner points = centre - wh / st  (fp32, same operation order)
 //   lore_snap_kernel      one wave per cell: bbox overlap + strict point-in-quad (fp64) against all corners, 64 at a
 //                         time, then the order-dependent "snap the nearest vertex" update replayed in corner order
@@ -33,8 +34,27 @@ __global__ __launch_bounds__(256) void lore_sigmoid_kernel(const float* __restri
   sig[2 * i + 1] = 1.f / (1.f + expf(-hm[8 * i + 1]));
 }
 
+// 3x3 max-pool equality (-inf padding) + threshold at pixel (y, x) of one table's score map sb [H][W][2]; s: the score there
+// (lore_peaks_kernel's own test, restated for the rebuild of an over-full list in lore_sort_kernel)
+__device__ __forceinline__ bool heat_is_peak(const float* __restrict__ sb, int H, int W, int y, int x, int cls, float thr, float& s) {
+  s = sb[((size_t)y * W + x) * 2 + cls];
+  if (!(s >= thr)) return false;
+  for (int dy = -1; dy <= 1; ++dy)
+    for (int dx = -1; dx <= 1; ++dx) {
+      const int yy = y + dy, xx = x + dx;
+      if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+      if (sb[((size_t)yy * W + xx) * 2 + cls] > s) return false;
+    }
+  return true;
+}
+
+__device__ __forceinline__ unsigned long long heat_key(float s, unsigned pixel) {
+  return ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(0xFFFFFFFFu - pixel);
+}
+
 // keys[(b * 2 + cls) * CAP + slot] = score_bits << 32 | (0xFFFFFFFF - pixel index): descending key order is
-// (score desc, index asc)
+// (score desc, index asc).  counts[list] is the number of peaks; those whose slot is >= CAP are not stored (which ones
+// depends on the order of the atomics): lore_sort_kernel takes such a list from the score map instead
 template <int NTHR>
 __global__ __launch_bounds__(NTHR) void lore_peaks_kernel(const float* __restrict__ sig, int B, int H, int W, float thr_cell,
                                                           float thr_corner, unsigned long long* __restrict__ keys,
@@ -54,7 +74,7 @@ __global__ __launch_bounds__(NTHR) void lore_peaks_kernel(const float* __restric
   for (int cls = 0; cls < 2; ++cls) {
     const float s = sb[((size_t)y * W + x) * 2 + cls];
     bool peak = live && (s >= (cls ? thr_corner : thr_cell));
-    if (peak) {
+    if (peak) {      // the test of heat_is_peak, in the form this kernel has always had
       for (int dy = -1; dy <= 1 && peak; ++dy)
         for (int dx = -1; dx <= 1; ++dx) {
           const int yy = y + dy, xx = x + dx;
@@ -90,21 +110,77 @@ __global__ __launch_bounds__(NTHR) void lore_peaks_kernel(const float* __restric
   }
 }
 
+// peaks of list (b, cls) whose key is >= lo, counted by the whole workgroup (every thread returns the total)
+__device__ int heat_count_from(const float* __restrict__ sb, int H, int W, int cls, float thr, unsigned long long lo, int* s_acc) {
+  const int npix = H * W;
+  if (threadIdx.x == 0) *s_acc = 0;
+  __syncthreads();
+  int c = 0;
+  for (int i = threadIdx.x; i < npix; i += blockDim.x) {
+    float s;
+    if (heat_is_peak(sb, H, W, i / W, i % W, cls, thr, s) && heat_key(s, (unsigned)i) >= lo) ++c;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(s_acc, c);
+  __syncthreads();
+  const int tot = *s_acc;
+  __syncthreads();
+  return tot;
+}
+
+// A list with more than CAP peaks: the key buffer holds an arbitrary CAP of them, so the first k (<= CAP) are taken from
+// the score map itself.  The keys are distinct (their index halves are), so the k-th largest is the largest floor with at
+// least k keys at or above it: found bit by bit, one counting pass over the map (3x3 test recomputed) per bit; the k keys
+// at or above it then go to sk[0, k) in arrival order -- the sort that follows puts them in their only order.
+// (not inlined: the sort kernel's common path keeps its registers and code)
+__device__ __noinline__ void heat_take_from_map(const float* __restrict__ sb, int H, int W, int cls, float thr, int k, unsigned long long* sk) {
+  __shared__ int s_acc;
+  unsigned long long lo = 0ull;
+  for (int bit = 63; bit >= 0; --bit) {
+    const unsigned long long cand = lo | (1ull << bit);
+    if (heat_count_from(sb, H, W, cls, thr, cand, &s_acc) >= k) lo = cand;
+  }
+  if (threadIdx.x == 0) s_acc = 0;
+  __syncthreads();
+  const int npix = H * W;
+  for (int i = threadIdx.x; i < npix; i += blockDim.x) {
+    float s;
+    if (!heat_is_peak(sb, H, W, i / W, i % W, cls, thr, s)) continue;
+    const unsigned long long key = heat_key(s, (unsigned)i);
+    if (key < lo) continue;
+    const int slot = atomicAdd(&s_acc, 1);
+    if (slot < k) sk[slot] = key;          // exactly k keys pass: the bound only keeps a wrong floor inside the buffer
+  }
+  __syncthreads();
+}
+
 // Sorts list `blockIdx.x` (n = min(counts, CAP) keys) descending; writes the first min(n, kmax) to out and that count.
+// With sig (the score maps [lists / 2][H][W][2] the keys came from; thresholds thr_even / thr_odd) a list whose count
+// exceeds CAP is rebuilt from its map: its first kmax peaks, whatever lore_peaks_kernel managed to store.
 __global__ __launch_bounds__(1024) void lore_sort_kernel(const unsigned long long* __restrict__ keys,
                                                           const int* __restrict__ counts, int count_stride,
                                                           int stride_in, int kmax_even, int kmax_odd,
                                                           unsigned long long* __restrict__ out, int stride_out,
-                                                          int* __restrict__ out_counts) {
+                                                          int* __restrict__ out_counts, const float* __restrict__ sig,
+                                                          int H, int W, float thr_even, float thr_odd) {
   a16_kernel_enter();
   extern __shared__ unsigned long long sk[];
   const int list = blockIdx.x;
+  const int kmax = (list & 1) ? kmax_odd : kmax_even;
   int n = counts[list * count_stride];
+  const bool overflow = sig != nullptr && n > CAP && kmax > 0;      // uniform over the workgroup
   if (n > stride_in) n = stride_in;
   if (n > CAP) n = CAP;
+  if (overflow) n = kmax < CAP ? kmax : CAP;
   int P = 2;
   while (P < n) P <<= 1;
-  for (int i = threadIdx.x; i < P; i += blockDim.x) sk[i] = i < n ? keys[(size_t)list * stride_in + i] : 0ull;
+  if (overflow) {
+    heat_take_from_map(sig + (size_t)(list >> 1) * H * W * 2, H, W, list & 1, (list & 1) ? thr_odd : thr_even, n, sk);
+    for (int i = n + threadIdx.x; i < P; i += blockDim.x) sk[i] = 0ull;
+  } else {
+    for (int i = threadIdx.x; i < P; i += blockDim.x) sk[i] = i < n ? keys[(size_t)list * stride_in + i] : 0ull;
+  }
   __syncthreads();
   for (int k = 2; k <= P; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1) {
@@ -118,7 +194,6 @@ __global__ __launch_bounds__(1024) void lore_sort_kernel(const unsigned long lon
       }
       __syncthreads();
     }
-  const int kmax = (list & 1) ? kmax_odd : kmax_even;
   const int m = n < kmax ? n : kmax;
   for (int i = threadIdx.x; i < m; i += blockDim.x) out[(size_t)list * stride_out + i] = sk[i];
   if (threadIdx.x == 0) out_counts[list] = m;
@@ -429,14 +504,17 @@ __global__ __launch_bounds__(256) void lore_gather_kernel(const float* __restric
 // The heat-map half of a CenterNet-style decode, shared by Lore's decode and CenterNet's (centernet_decode.hip): sigmoid of the two
 // classes of hm (fp32, channel stride 8), 3x3 peaks (max-pool equality) at or above thr0 / thr1, and per (table, class) list the
 // first k0 / k1 of them in (score desc, pixel index asc) order.  cnt: int [2B] raw peak counts, zeroed by the caller; keys, sorted:
-// u64 [2B][PT_HEAT_CAP] (score_bits << 32 | ~pixel index); kept: int [2B] the kept counts.  At most PT_HEAT_CAP peaks per list
-// take part.
+// u64 [2B][PT_HEAT_CAP] (score_bits << 32 | ~pixel index); kept: int [2B] the kept counts.  The result is exactly the first
+// k0 / k1 peaks in that order whatever their number: a list with more than PT_HEAT_CAP peaks (a flat or saturated map: every pixel of
+// a plateau is a peak) does not fit `keys`, and its sort workgroup selects them from `sig` instead (a device-side branch on cnt, no
+// extra launch, no host synchronisation; lists within the capacity take the path they always took).
 int pt_heat_peaks_topk(const float* hm, int B, int H, int W, float thr0, float thr1, int k0, int k1, float* sig, unsigned long long* keys,
                        int* cnt, unsigned long long* sorted, int* kept, hipStream_t s) {
   PT_REQUIRE(hm && sig && keys && cnt && sorted && kept && B > 0 && k0 <= CAP && k1 <= CAP, "heat peaks: bad arguments");
   PT_REQUIRE((long long)H * W < (1ll << 31), "heat peaks: map too large");
   static bool attr_done = false;
   if (!attr_done) {
+    // dynamic LDS: the CAP keys.  The kernel also has one static word (heat_take_from_map's counter): 128 KiB + 4 bytes of the 160 KiB
     PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&lore_sort_kernel),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, CAP * 8));
     attr_done = true;
@@ -444,7 +522,8 @@ int pt_heat_peaks_topk(const float* hm, int B, int H, int W, float thr0, float t
   const size_t npix = (size_t)B * H * W;
   hipLaunchKernelGGL(lore_sigmoid_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, hm, sig, (long long)npix);
   hipLaunchKernelGGL(lore_peaks_kernel<1024>, dim3((unsigned)((npix + 1023) / 1024)), dim3(1024), 0, s, sig, B, H, W, thr0, thr1, keys, cnt);
-  hipLaunchKernelGGL(lore_sort_kernel, dim3(2 * B), dim3(1024), CAP * 8, s, keys, cnt, 1, CAP, k0, k1, sorted, CAP, kept);
+  hipLaunchKernelGGL(lore_sort_kernel, dim3(2 * B), dim3(1024), CAP * 8, s, keys, cnt, 1, CAP, k0, k1, sorted, CAP, kept,
+                     (const float*)sig, H, W, thr0, thr1);
   PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }
@@ -511,7 +590,7 @@ static int decode_boxes(const DecodeState* ds, const float* reg0, const float* r
     hipLaunchKernelGGL(lore_rekey_kernel, dim3((K_CELLS + 255) / 256, B), dim3(256), 0, s, ds->rev, cnt + 2 * B, CAP, ds->keys2);
     // one list per table; its length is the kept cell count (the even entries of the kept counts)
     hipLaunchKernelGGL(lore_sort_kernel, dim3(B), dim3(1024), CAP * 8, s, ds->keys2, cnt + 2 * B, 2, CAP, K_CELLS, K_CELLS,
-                       ds->sorted2, CAP, cnt + 4 * B);
+                       ds->sorted2, CAP, cnt + 4 * B, (const float*)nullptr, 0, 0, 0.f, 0.f);
   }
   PT_HIP_CHECK(hipGetLastError());
   return PT_OK;

@@ -398,7 +398,7 @@ eng = HipEngine(0)
 eng.load_weights(L.PT_MODEL_LORE_DLA34, pack_lore_dla34(lore_dla34_state_dict(seed=2, hm_bias=(-1.2, -0.6))))
 eng.set_precision(L.PT_PRECISION_BF16X3 if mode == "bf16x3" else L.PT_PRECISION_BF16)
 g = torch.Generator().manual_seed(77)
-n, H, W = 3, 256, 320
+n, H, W = (int(v) for v in sys.argv[4:7]) if len(sys.argv) > 4 else (3, 256, 320)
 x = torch.randn(n, H, W, 3, generator=g) * 0.7
 x4 = torch.zeros(n, H, W, 8 if mode == "bf16x3" else 4)
 hi = x.to(torch.bfloat16).float()
@@ -413,7 +413,7 @@ np.savez(out, c0=c0, c1=c1, d0=d0.cpu().numpy(), d1=d1.cpu().numpy(), l0=l0.cpu(
 '''
 
 
-def _run_fused(tmp_path, mode, wiz_rev, variant):
+def _run_fused(tmp_path, mode, wiz_rev, variant, shape=None):
     import os
     import subprocess
     import sys
@@ -422,7 +422,8 @@ def _run_fused(tmp_path, mode, wiz_rev, variant):
     if variant is not None:
         e["PT_CONV_VARIANT"] = str(variant)
     e["PYTHONPATH"] = os.path.dirname(os.path.dirname(os.path.abspath(__file__))) + os.pathsep + e.get("PYTHONPATH", "")
-    subprocess.run([sys.executable, "-c", _FUSED_SCRIPT, mode, "1" if wiz_rev else "0", out], check=True, env=e, timeout=300)
+    subprocess.run([sys.executable, "-c", _FUSED_SCRIPT, mode, "1" if wiz_rev else "0", out] + [str(v) for v in shape or ()],
+                   check=True, env=e, timeout=300)
     return np.load(out)
 
 
@@ -439,6 +440,19 @@ def test_forward_decode_fused_is_bit_identical(tmp_path, mode, wiz_rev):
     for b in range(len(c0)):         # rows beyond a table's count are unspecified in both paths
         k = int(c0[b])
         assert np.array_equal(r["d0"][b, :max(k, 1)], r["d1"][b, :max(k, 1)])
+        assert np.array_equal(r["l0"][b, :k], r["l1"][b, :k]), b
+
+
+def test_forward_decode_fused_is_bit_identical_across_a_table_seam(tmp_path):
+    """the same claim at 2 x 96 x 160: 24 x 40 maps, 960 pixels each, so the workgroup of the peak kernel that holds the seam holds
+    pixels of both tables, and the peak-patch and sparse-base kernels run over a batch whose tables are smaller than a workgroup"""
+    r = _run_fused(tmp_path, "bf16", True, 0, shape=(2, 96, 160))
+    c0, c1 = r["c0"], r["c1"]
+    print("fused decode, 24 x 40 maps: cells above vis_thresh per table", c0.tolist())
+    assert np.array_equal(c0, c1) and (c0 > 0).all(), (c0, c1)
+    for b in range(len(c0)):
+        k = int(c0[b])
+        assert np.array_equal(r["d0"][b, :k], r["d1"][b, :k])
         assert np.array_equal(r["l0"][b, :k], r["l1"][b, :k]), b
 
 
