@@ -129,7 +129,7 @@ int pt_weights_load_device(pt_engine* e, int model_kind, const void* d_blob, siz
 /* ---- stage 1: layout detection (PicoDet) -------------------------------------------------------- */
 #define PT_LAYOUT_LEVELS 4
 #define PT_LAYOUT_HEAD_CS 40   /* fp32 values per anchor: ncls class logits, then 4 * (reg_max + 1) box logits, zero padded */
-#define PT_LAYOUT_CAND_FLOATS 48 /* candidate record: int32 level, int32 anchor, 40 head values, padding */
+#define PT_LAYOUT_CAND_FLOATS 48 /* candidate record: int32 level, int32 anchor, 40 head values, zero padding */
 
 /* Anchors of level l for an inp_h x inp_w input: strides 8, 16, 32 and the extra 5x5/s2 level (csp_pan.py:265-270). */
 int pt_layout_plan(int inp_h, int inp_w, int32_t fm_h[PT_LAYOUT_LEVELS], int32_t fm_w[PT_LAYOUT_LEVELS]);
@@ -506,6 +506,18 @@ int pt_op_layernorm(pt_engine* e, const uint16_t* d_in, long long rows, int c_pa
 int pt_op_softmax(pt_engine* e, const uint16_t* d_in, long long rows, int c_pad, int c, float* d_out_f32, uint16_t* d_out_bf16, int split, pt_stream stream);
 int pt_op_attention(pt_engine* e, const uint16_t* d_qkv, int B, int T, int heads, int d, int qkv_cstride, float scale, uint16_t* d_out, int out_cstride,
                     int split, pt_stream stream);
+
+/* ONNX LSTM layer, the recurrence (csrc/lstm_op.hip; since ABI 17).  Hidden size H <= 128; Hp = H rounded up to 16.  The input projection is the
+ * caller's: d_pregates [B T rows][pg_cstride] (row b T + t) = X W^T + Wb + Rb from pt_op_conv2d, channel d 4 Hp + gate Hp + unit with the gates in
+ * ONNX order i, o, f, c and zeros in the padded units.  d_r_packed: the recurrent weights R [dirs, 4H, H] in MFMA operand order
+ * (pdf_table_amd/weights.py::pack_lstm_r; pt_op_lstm_packed_elems(H, dirs, split) 16-bit values, 0 for an unsupported H).  Zero initial states.
+ * dirs 1: one direction, walked t = T - 1 .. 0 when reverse; dirs 2: direction 0 forward, 1 reverse.  d_y [B T rows][y_cstride]: h_t at channel
+ * d H + unit (the caller zeroes the padding channels once).  split (PT_PRECISION_BF16X3): pre-gates, R and h are (hi | lo) pairs, the lo half of a
+ * row at cstride / 2.  c is kept in fp32 for the whole sequence, h is rounded to the storage format once per step.  One workgroup per direction and
+ * 16 sequences, no cross-workgroup synchronisation; no allocation and no host synchronisation (capturable). */
+int pt_op_lstm(pt_engine* e, const uint16_t* d_pregates, int pg_cstride, const uint16_t* d_r_packed, int T, int B, int H, int dirs, int reverse,
+               uint16_t* d_y, int y_cstride, int split, pt_stream stream);
+int pt_op_lstm_packed_elems(int H, int dirs, int split);
 
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------

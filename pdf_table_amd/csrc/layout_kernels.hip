@@ -478,7 +478,7 @@ __global__ __launch_bounds__(256) void add_kernel(const bf16_t* __restrict__ a, 
 }
 
 // head: fp32 [B][A][40] of one level (ncls class logits, then 4 x (reg_max + 1) box logits).  An anchor whose best
-// sigmoid score exceeds thr_lo is appended to cands[b] as (level, anchor, 40 raw values) -- 48 floats per record.
+// sigmoid score exceeds thr_lo is appended to cands[b] as (level, anchor, 40 raw values, 6 zeros) -- 48 floats per record.
 __global__ __launch_bounds__(256) void pico_candidates_kernel(const float* __restrict__ head, int B, int A, int ncls,
                                                                int level, float thr_lo, int max_cands,
                                                                float* __restrict__ cands, int* __restrict__ counts) {
@@ -496,6 +496,7 @@ __global__ __launch_bounds__(256) void pico_candidates_kernel(const float* __res
   o[0] = __int_as_float(level);
   o[1] = __int_as_float(a);
   for (int c = 0; c < 40; ++c) o[2 + c] = h[c];
+  for (int c = 42; c < 48; ++c) o[c] = 0.f;   // the padding is part of the record a caller copies and compares: never what the buffer held before
 }
 
 // LightSegDetector.binarize after its first pointwise conv (dbnet.py:383-386 with DwPwConvTranspose :75-99), one thread

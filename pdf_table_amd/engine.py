@@ -898,6 +898,21 @@ class HipEngine:
                                          self._stream()), "pt_op_attention")
         return out
 
+    def op_lstm(self, pregates: torch.Tensor, r_packed: torch.Tensor, hidden: int, dirs: int, reverse: bool, out_c: int, split: bool = False) -> torch.Tensor:
+        """The recurrence of an ONNX LSTM layer (pt_op_lstm; hidden <= 128, zero initial states).  pregates [B, 1, T, dirs * 4 * Hp] (x m halves
+        when split) = X W^T + Wb + Rb, gates i, o, f, c per direction; r_packed: weights.pack_lstm_r(R) on the device -> token rows
+        [B, 1, T, out_c] (x m): h_t at channel d * hidden + unit, forward units first, the channels from dirs * hidden on zero."""
+        self._chk(pregates, self.act_dtype, "pregates")
+        B, T = pregates.shape[0], pregates.shape[-2]
+        m = 2 if split else 1
+        need = self.lib.pt_op_lstm_packed_elems(int(hidden), int(dirs), int(split))
+        if need == 0 or r_packed.numel() != need or not r_packed.is_contiguous() or r_packed.element_size() != 2:
+            raise ValueError(f"op_lstm: packed R of {r_packed.numel()} values for hidden {hidden}, dirs {dirs}, split {int(split)} ({need} expected)")
+        out = torch.zeros((B, 1, T, int(out_c) * m), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_lstm(self._h, _ptr(pregates), pregates.shape[-1], _ptr(r_packed), T, B, int(hidden), int(dirs), int(bool(reverse)), _ptr(out),
+                                    out.shape[-1], int(split), self._stream()), "pt_op_lstm")
+        return out
+
     def op_stem7x7(self, x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, split: bool = False) -> torch.Tensor:
         self._chk(x, self.act_dtype, "x")
         B, H, W, _ = x.shape

@@ -7,7 +7,8 @@ pre-processor: 32 x 804, three 300-px chunks, 201 tokens per line, vocabulary fr
 ``model="PP-OCRv4" / "PP-OCRv3" / "PP-Table"`` -- the ONNX recognisers ``fix_model_names()`` selects for every language
 (model/ocr_pdf/configuration_ocr_document.py:138-141) -- are served from a ``model.onnx`` / ``inference.onnx`` under ``task_path``: the
 engine's ``PPOcrRecPreProcessor`` kernel (48-px, width-sorted mini-batches), the generic graph executor (conv backbone, SVTR-type
-attention / LayerNorm neck, CTC head with its Softmax: pdf_table_amd/onnx_exec.py) and ``CTCLabelDecode``; without a file they fail
+attention / LayerNorm neck or the BiLSTM neck of the CRNN-type mobile / table recognisers, CTC head with its Softmax:
+pdf_table_amd/onnx_exec.py) and ``CTCLabelDecode``; without a file they fail
 loudly, naming the hub id the reference would have fetched.  ``LightweightEdge`` is not built.
 
 Two ways in:
@@ -105,7 +106,7 @@ class OcrRecognitionTask(BaseInferTask):
             outs = self._exec.run_lines_graphed(x, 3) if self._batch1 else [self._exec.run_device_graphed(x, 3)]    # dynamic batch: one walk
             probs = []
             for (a,) in outs:
-                if not a.seq or a.c != len(self._ctc.character):
+                if not a.seq or a.tm or a.c != len(self._ctc.character):
                     raise UnsupportedOnnxGraph(f"recogniser output of shape {a.shape()}: [B, T, {len(self._ctc.character)}] (blank + dictionary"
                                                " + space) is expected")
                 v = self._exec.values(a)                         # fp32 probabilities [b, 1, T, classes] (the executor keeps a final Softmax in fp32)

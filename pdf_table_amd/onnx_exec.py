@@ -29,7 +29,16 @@ graphs on the CPU for the tests only).  Supported today: Conv (groups 1: 1x1 / 3
 "same" padding), ConvTranspose 2x2 / stride 2, BatchNormalization (folded), Relu / HardSwish / Sigmoid / HardSigmoid /
 Relu6, a BatchNormalization that stands alone, Add, Mul by a per-channel gate, MaxPool(3, 2, 1) and k x k / stride k,
 AveragePool k x k / stride k, GlobalAveragePool, Resize / Upsample (nearest, integer factor, by scales or sizes), Concat over
-channels, Gemm / Flatten after a global pool.
+channels, Gemm / Flatten after a global pool; LayerNormalization, Gelu / swish, Softmax, fused-qkv attention on token rows; LSTM (forward /
+reverse / bidirectional, hidden size <= 128, zero initial states, default activations).
+
+Recurrent layers (CRNN-type recognisers: the PP-OCR mobile / table recognisers, any exported nn.LSTM): X [T, B, I] must be token rows read
+time-major -- what Squeeze / Transpose / Reshape make of a conv map [B, C, 1, W].  The input projection X W^T + Wb + Rb of all steps and both
+directions is ONE ``pt_op_conv2d`` (4 Hp D channels, Hp = H rounded up to 16), the recurrence ONE ``pt_op_lstm`` (csrc/lstm_op.hip: the
+recurrent weights of a direction stay in LDS, one workgroup per direction and 16 sequences); Y [T, D, B, H] is a ``_View`` over the token rows
+[B, 1, T, pad64(D H)] the kernel writes, so the exporter's Transpose + Reshape and the following LSTM / MatMul move no data.  A Gemm / activation
+of a time-major tensor runs on the same rows and keeps the view; a time-major graph output is transposed on the host.  sequence_lens,
+peepholes, clip, other activations, layout = 1, used Y_h / Y_c, non-zero or computed initial states and more than 128 units raise.
 
 Two arithmetic modes, like the dedicated launch graphs (``precision=`` of the constructor): ``"bf16"`` -- bf16 operands, fp32 accumulate, every
 activation rounded to bf16 (the throughput mode) -- and ``"bf16x3"``, the tolerance mode: every activation is a (hi | lo) pair of bf16 halves
@@ -51,7 +60,7 @@ import torch
 from . import lib as L
 from .engine import HipEngine
 from .onnx_import import Layer, OnnxGraph, UnsupportedOnnxGraph, load_onnx
-from .weights import split_bf16, tile_conv_weight, tile_conv_weight_x3
+from .weights import lstm_padded_sizes, pack_lstm_r, split_bf16, tile_conv_weight, tile_conv_weight_x3
 
 __all__ = ["HipGraphExecutor"]
 
@@ -70,12 +79,15 @@ class _Act:
     c: int
     flat: bool = False      # the ONNX tensor is [B, C] (after Flatten / Gemm), held here as [B, 1, 1, C]
     seq: bool = False       # the ONNX tensor is [B, T, C] (token rows), held here as [B, 1, T, Cpad]
+    tm: bool = False        # graph outputs only: token rows whose ONNX tensor is time-major [T, B, C] (what a bare nn.LSTM returns)
 
     def shape(self):
         """the ONNX (logical) shape"""
         B, H, W = self.t.shape[:3]
         if self.flat:
             return (B, self.c)
+        if self.seq and self.tm:
+            return (W, B, self.c)
         if self.seq:
             return (B, W, self.c)
         return (B, self.c, H, W)
@@ -98,6 +110,24 @@ class _Scores:
     d: int
     scale: float
     soft: bool = False
+
+
+def lstm_gemm_operands(W: np.ndarray, Bv: Optional[np.ndarray], cin_pad: int):
+    """ONNX LSTM W [D, 4H, I] and B [D, 8H] = [Wb | Rb] -> the input projection as ONE 1x1 convolution over token rows: weight
+    [D 4 Hp, cin_pad, 1, 1] and bias [D 4 Hp] = Wb + Rb, output channel d 4 Hp + gate Hp + unit with the gates in ONNX order i, o, f, c.  Units
+    H .. Hp (Hp = H rounded up to 16) are zero rows with zero bias: their gates are 0, so their c and h stay exactly 0."""
+    D, H4, I = W.shape
+    H = H4 // 4
+    Hp, _ = lstm_padded_sizes(H)
+    wp = torch.zeros(D * 4 * Hp, cin_pad, 1, 1)
+    bp = torch.zeros(D * 4 * Hp)
+    for d in range(D):
+        for g in range(4):
+            o = d * 4 * Hp + g * Hp
+            wp[o:o + H, :I, 0, 0] = torch.from_numpy(np.ascontiguousarray(W[d, g * H:(g + 1) * H], dtype=np.float32))
+            if Bv is not None:
+                bp[o:o + H] = torch.from_numpy(Bv[d, g * H:(g + 1) * H].astype(np.float64) + Bv[d, (4 + g) * H:(5 + g) * H].astype(np.float64)).float()
+    return wp, bp
 
 
 _CAPTURE_LOCK = threading.Lock()      # graph capture is serialised across executors and host threads (see HipGraphExecutor._graphed)
@@ -136,6 +166,8 @@ class HipGraphExecutor:
         self._seen: set = set()                                 # shapes that ran once eagerly (the next call captures)
         self._bad: set = set()                                  # shapes whose capture raised: eager from then on
         self._fuse = self._plan_add_fusion()
+        # every tensor some layer reads (constants included): an LSTM's Y_h / Y_c are supported only when nothing does
+        self._read = {nm for l in self.layers for nm in list(l.inputs) + list(l.attrs.get("all_inputs", ())) if nm} | set(self.outputs)
 
     def _plan_add_fusion(self) -> Dict[int, tuple]:
         """Residual adds folded into the producing convolution's epilogue at load time: conv k (groups 1, 1x1 / 3x3, no activation of its own)
@@ -312,6 +344,103 @@ class HipGraphExecutor:
             raise UnsupportedOnnxGraph(f"{lay.name}: activation '{kind}'")
         return _Act(self.eng.op_act(y.t, _ACT_KIND[kind], lay.attrs.get("act_alpha", 0.2), lay.attrs.get("act_beta", 0.5), split=self.split), y.c, y.flat, y.seq)
 
+    # ---- recurrent layers ----------------------------------------------------------------------------------------------
+    def _time_major_rows(self, v, what: str) -> Optional[_Act]:
+        """a logical tensor [T, B, C] whose element (t, b, c) is channel c of token row (b, t) of a materialised tensor -- what Squeeze /
+        Transpose / Reshape make of a conv map [B, C, 1, W], and what an LSTM's Y becomes after the exporter's Transpose + Reshape -> those token
+        rows [B, 1, T, Cpad]; None if the index array says anything else"""
+        if isinstance(v, _Act):
+            v = self._as_view(v)
+        if not isinstance(v, _View) or v.idx.ndim != 3 or v.scale != 1.0:
+            return None
+        try:
+            a = self._realize(_View(v.base, np.ascontiguousarray(v.idx.transpose(1, 0, 2))), what)
+        except UnsupportedOnnxGraph:
+            return None
+        return a if a.seq else None
+
+    @staticmethod
+    def _time_major_view(a: _Act) -> _View:
+        """token rows [B, T, C] seen as the time-major tensor [T, B, C]"""
+        B, T, C = a.shape()
+        return _View(a, np.ascontiguousarray(np.arange(B * T * C, dtype=np.int64).reshape(B, T, C).transpose(1, 0, 2)))
+
+    def _lstm_plan(self, lay: Layer, env):
+        """what of an ONNX LSTM node is built (host only): zero initial states -- absent, or constants that fold to zeros, the Shape ->
+        ConstantOfShape / Expand chain of a dynamic-batch export included --, default activations, layout 0, hidden size <= 128, Y_h / Y_c
+        unread; anything else raises naming the layer and the reason.  -> (H, Hp, D, reverse, name of Y)"""
+        a, na = lay.attrs, lay.attrs.get("node_attrs", {})
+        names = list(a.get("all_inputs", lay.inputs)) + [""] * 8
+        outs = list(a.get("all_outputs", lay.outputs)) + [""] * 3
+        H = int(a["hidden_size"])
+        direction = a.get("direction", "forward")
+        direction = direction.decode() if isinstance(direction, bytes) else str(direction)
+        D = 2 if direction == "bidirectional" else 1
+
+        def refuse(why):
+            raise UnsupportedOnnxGraph(f"{lay.name}: LSTM {why}")
+        if direction not in ("forward", "reverse", "bidirectional"):
+            refuse(f"direction '{direction}'")
+        if names[4]:
+            refuse("with sequence_lens (every sequence runs all T steps here)")
+        if names[7]:
+            refuse("with peephole weights (P)")
+        if "clip" in na:
+            refuse(f"with clip = {na['clip']}")
+        acts = [x.decode() if isinstance(x, bytes) else str(x) for x in na.get("activations", [])]
+        if (acts and acts != ["Sigmoid", "Tanh", "Tanh"] * D) or "activation_alpha" in na or "activation_beta" in na:
+            refuse(f"with activations {acts} (the default Sigmoid, Tanh, Tanh is built)")
+        if int(na.get("layout", 0)) != 0:
+            refuse("with layout = 1 (batch-major X and Y)")
+        if int(na.get("input_forget", 0)) != 0:
+            refuse("with input_forget = 1")
+        Hp, _ = lstm_padded_sizes(H)
+        if Hp > 128:
+            refuse(f"of {H} hidden units: the generic executor's recurrent kernel keeps R in LDS, 128 units at the most (precision '{self.precision}'; "
+                   "the 256-unit CRNN has a dedicated launch graph)")
+        for nm, what in ((names[5], "initial_h"), (names[6], "initial_c")):
+            if nm:
+                v = env[nm] if nm in env else self.graph.init.get(nm)
+                if not isinstance(v, np.ndarray) or np.any(v != 0):
+                    refuse(f"with a {'non-zero' if isinstance(v, np.ndarray) else 'computed'} {what} (absent or all-zero initial states are built)")
+        for nm, what in ((outs[1], "Y_h"), (outs[2], "Y_c")):
+            if nm and nm in self._read:
+                refuse(f"whose {what} output is used (Y is built)")
+        W, R = lay.extra["W"], lay.extra["R"]
+        if W.shape[0] != D or tuple(R.shape) != (D, 4 * H, H) or W.shape[1] != 4 * H:
+            refuse(f"weights W {tuple(W.shape)} / R {tuple(R.shape)} do not match {D} direction(s) of {H} units")
+        return H, Hp, D, direction == "reverse", outs[0]
+
+    def _lstm(self, k: int, lay: Layer, env) -> None:
+        """ONNX LSTM: the input projection of all steps and both directions is ONE row GEMM (4 Hp D channels, bias Wb + Rb), the recurrence
+        is pt_op_lstm; Y [T, D, B, H] is a view over the token rows [B, 1, T, pad64(D H)] the kernel writes (forward units first), so the
+        exporter's Transpose + Reshape and the next layer move no data."""
+        H, Hp, D, reverse, y_name = self._lstm_plan(lay, env)
+        W, R, Bv = lay.extra["W"], lay.extra["R"], lay.extra.get("B")
+
+        def refuse(why):
+            raise UnsupportedOnnxGraph(f"{lay.name}: LSTM {why}")
+        xv = env.get(lay.attrs.get("all_inputs", lay.inputs)[0])
+        x = self._time_major_rows(xv, lay.name) if xv is not None else None
+        if x is None:
+            shp = xv.idx.shape if isinstance(xv, _View) else (xv.shape() if isinstance(xv, _Act) else None)
+            refuse(f"input X of logical shape {shp} is not token rows read time-major ([T, B, I] = Squeeze / Transpose / Reshape of a conv map "
+                   "[B, C, 1, W], or of token rows [B, T, C])")
+        if x.c != W.shape[2]:
+            refuse(f"weights expect {W.shape[2]} input channels, X has {x.c}")
+        d = self._dev.get(k)
+        if d is None or d["cin_pad"] != self._cp(x):
+            cp = self._cp(x)
+            wp, bp = lstm_gemm_operands(W, Bv, cp)
+            d = self._dev[k] = {"cin_pad": cp, "w": self._up(self._tile(wp).view(np.int16)), "b": bp.to(self.eng._tdev),
+                                "r": self._up(pack_lstm_r(R, self.fmt, self.split).view(np.int16))}
+        pg = self.eng.op_conv2d(x.t, d["w"], d["b"], 1, 1, split=int(self.split))
+        y = _Act(self.eng.op_lstm(pg, d["r"], H, D, reverse, _pad64(D * H), split=self.split), D * H, seq=True)
+        Bn, T = y.t.shape[0], y.t.shape[2]
+        idx = ((np.arange(Bn)[None, None, :, None] * T + np.arange(T)[:, None, None, None]) * (D * H)
+               + np.arange(D)[None, :, None, None] * H + np.arange(H)[None, None, None, :])
+        env[y_name] = _View(y, np.ascontiguousarray(idx.astype(np.int64)))
+
     # ---- the graph -------------------------------------------------------------------------------------------------
     def run(self, x) -> List[np.ndarray]:
         """x: float NCHW image batch (numpy / torch) -> the graph outputs as float32 NCHW arrays, in graph order"""
@@ -322,8 +451,9 @@ class HipGraphExecutor:
         nhwc = xt.permute(0, 2, 3, 1).to(self.eng._tdev)
         for a in self.run_device(nhwc if self.split else nhwc.to(self.adt), xt.shape[1]):
             v = self.values(a)
-            if a.seq:                                    # token rows: [B, T, C]
-                outs.append(v[:, 0].contiguous().cpu().numpy())
+            if a.seq:                                    # token rows: [B, T, C] ([T, B, C] for a time-major output: a host-side transpose)
+                rows = v[:, 0].transpose(0, 1) if a.tm else v[:, 0]
+                outs.append(rows.contiguous().cpu().numpy())
                 continue
             o = v.permute(0, 3, 1, 2).contiguous().cpu().numpy()
             outs.append(o.reshape(o.shape[0], -1) if a.flat else o)
@@ -545,6 +675,30 @@ class HipGraphExecutor:
         n = int(nhwc.shape[0])
         return self._graphed(("lines",) + tuple(nhwc.shape) + (nhwc.dtype, int(c)), nhwc, lambda x: [self.run_device(x[i:i + 1], c) for i in range(n)])
 
+    def _host_layer(self, lay: Layer, env) -> bool:
+        """the layers that run on the host: shape plumbing over constants and views (_glue), integer shape arithmetic, a scalar factor folded
+        into a view.  True: env holds the layer's outputs."""
+        op = lay.op
+        if op == "glue" or (op == "concat" and all((i in self.graph.init or isinstance(env.get(i), np.ndarray)) for i in lay.inputs)):
+            for o, v in zip(lay.outputs, self._glue(lay, env)):
+                env[o] = np.asarray(v) if isinstance(v, (np.generic, int, float)) else v      # host constants stay ndarrays (0-d included)
+            return True
+        raw = [env[i] for i in lay.inputs if i in env]
+        if op in ("add", "mul", "sub", "div") and lay.extra and all(np.asarray(v).size == 1 for v in lay.extra.values()) and len(raw) == 1 \
+                and isinstance(raw[0], (_View, _Scores, np.ndarray)):
+            cst = float(np.asarray(next(iter(lay.extra.values()))).reshape(-1)[0])
+            v = raw[0]
+            if isinstance(v, np.ndarray):            # integer shape arithmetic
+                first_is_const = lay.attrs["all_inputs"][0] not in env
+                a_, b_ = (cst, v) if first_is_const else (v, cst)
+                env[lay.outputs[0]] = np.asarray({"add": np.add, "mul": np.multiply, "sub": np.subtract, "div": np.floor_divide if v.dtype.kind in "iu" else np.divide}[op](a_, b_))
+                return True
+            if op in ("mul", "div"):                 # the 1 / sqrt(d) of an attention, on q or on the scores
+                f = cst if op == "mul" else 1.0 / cst
+                env[lay.outputs[0]] = _View(v.base, v.idx, v.scale * f) if isinstance(v, _View) else _Scores(v.base, v.heads, v.d, v.scale * f, v.soft)
+                return True
+        return False
+
     def run_device(self, nhwc: torch.Tensor, c: int) -> List[_Act]:
         """bf16 NHWC batch on the device whose first ``c`` channels are the image (what pt_det_preprocess / pt_cls_preprocess
         write) -> the graph outputs as device activations (bf16 NHWC, ``.t[..., :.c]`` are the real channels; ``values()`` gives them as fp32 in
@@ -574,24 +728,9 @@ class HipGraphExecutor:
         skip = set()                                     # Add / activation layers folded into a convolution's epilogue (self._fuse)
         for k, lay in enumerate(self.layers):
             op = lay.op
-            if op == "glue" or (op == "concat" and all((i in self.graph.init or isinstance(env.get(i), np.ndarray)) for i in lay.inputs)):
-                for o, v in zip(lay.outputs, self._glue(lay, env)):
-                    env[o] = np.asarray(v) if isinstance(v, (np.generic, int, float)) else v      # host constants stay ndarrays (0-d included)
+            if self._host_layer(lay, env):
                 continue
             raw = [env[i] for i in lay.inputs if i in env]
-            if op in ("add", "mul", "sub", "div") and lay.extra and all(np.asarray(v).size == 1 for v in lay.extra.values()) and len(raw) == 1 \
-                    and isinstance(raw[0], (_View, _Scores, np.ndarray)):
-                cst = float(np.asarray(next(iter(lay.extra.values()))).reshape(-1)[0])
-                v = raw[0]
-                if isinstance(v, np.ndarray):            # integer shape arithmetic
-                    first_is_const = lay.attrs["all_inputs"][0] not in env
-                    a_, b_ = (cst, v) if first_is_const else (v, cst)
-                    env[lay.outputs[0]] = np.asarray({"add": np.add, "mul": np.multiply, "sub": np.subtract, "div": np.floor_divide if v.dtype.kind in "iu" else np.divide}[op](a_, b_))
-                    continue
-                if op in ("mul", "div"):                 # the 1 / sqrt(d) of an attention, on q or on the scores
-                    f = cst if op == "mul" else 1.0 / cst
-                    env[lay.outputs[0]] = _View(v.base, v.idx, v.scale * f) if isinstance(v, _View) else _Scores(v.base, v.heads, v.d, v.scale * f, v.soft)
-                    continue
             if op == "matmul":
                 env[lay.outputs[0]] = self._attention(lay, raw[0], raw[1])
                 continue
@@ -602,7 +741,17 @@ class HipGraphExecutor:
                 continue
             if k in skip:
                 continue
-            ins = [R(v, lay.name) for v in raw]
+            if op == "lstm":
+                self._lstm(k, lay, env)
+                continue
+            tmaj = None                                  # Gemm / MatMul / activation of a time-major tensor [T, B, C]: the same rows, the same view of the result
+            try:
+                ins = [R(v, lay.name) for v in raw]
+            except UnsupportedOnnxGraph:
+                tmaj = self._time_major_rows(raw[0], lay.name) if op in ("gemm", "act") and len(raw) == 1 else None
+                if tmaj is None:
+                    raise
+                ins = [tmaj]
             if op == "conv":
                 fz = self._fuse.get(k)
                 y = None
@@ -720,9 +869,20 @@ class HipGraphExecutor:
                 y = _Act(self.eng.op_conv2d(src.t, d["w"], d["b"], 1, 1, split=int(self.split)), d["n"], not src.seq, src.seq)
             else:
                 raise UnsupportedOnnxGraph(f"{lay.name}: layer kind '{op}' has no executor")
+            if tmaj is not None:
+                y = self._time_major_view(y)
             for o in lay.outputs:
                 env[o] = y
         for name in self.outputs:
             if name not in env:
                 raise UnsupportedOnnxGraph(f"graph output '{name}' was not produced")
-        return [R(env[name], f"graph output '{name}'") for name in self.outputs]
+        res = []
+        for name in self.outputs:
+            try:
+                res.append(R(env[name], f"graph output '{name}'"))
+            except UnsupportedOnnxGraph:
+                tm = self._time_major_rows(env[name], name)
+                if tm is None:
+                    raise
+                res.append(_Act(tm.t, tm.c, seq=True, tm=True))      # a time-major output [T, B, C]: run() transposes on the host
+        return res

@@ -18,8 +18,8 @@ prepare_onnx_model`` utils/deploy_utils.py:243-280; ``infer`` :366-370 calls ``p
 A graph of any other architecture is executed layer by layer by ``pdf_table_amd.onnx_exec.HipGraphExecutor`` -- one engine
 call per layer of the list -- as long as it is made of the operators that executor lists (convolutional networks:
 detection / layout / classification backbones, necks and heads); ``recognise`` still raises ``UnsupportedOnnxGraph`` with
-the layer inventory for such a graph, and the executor names the first operator it has no kernel for (sequence models:
-attention / LayerNorm blocks of SVTR-type recognisers).  There is no CPU execution path in the product (oracle/onnx_ref.py
+the layer inventory for such a graph, and the executor names the first operator it has no kernel for (it runs the attention /
+LayerNorm blocks of SVTR-type recognisers and the LSTM layers of CRNN-type ones up to 128 hidden units).  There is no CPU execution path in the product (oracle/onnx_ref.py
 executes graphs on the CPU for the tests only).
 """
 from __future__ import annotations
@@ -331,7 +331,10 @@ class OnnxGraph:
                                   "act_alpha": float(n.attrs.get("alpha", 0.2)), "act_beta": float(n.attrs.get("beta", 0.5))}))
             elif t == "LSTM":
                 out.append(Layer("lstm", n.name or n.outputs[0], [n.inputs[0]], [o for o in n.outputs if o],
-                                 {"hidden_size": int(n.attrs["hidden_size"]), "direction": n.attrs.get("direction", "forward")},
+                                 # all_inputs / all_outputs keep the node's positions (X, W, R, B, sequence_lens, initial_h, initial_c, P -> Y, Y_h, Y_c;
+                                 # "" = absent) and node_attrs everything else the generic executor has to refuse (clip, activations, layout ...)
+                                 {"hidden_size": int(n.attrs["hidden_size"]), "direction": n.attrs.get("direction", "forward"),
+                                  "all_inputs": list(n.inputs), "all_outputs": list(n.outputs), "node_attrs": dict(n.attrs)},
                                  extra={"W": np.asarray(self.init[n.inputs[1]], np.float32), "R": np.asarray(self.init[n.inputs[2]], np.float32),
                                         "B": np.asarray(self.init[n.inputs[3]], np.float32) if len(n.inputs) > 3 and n.inputs[3] in self.init else None}))
             elif t in ("Gemm", "MatMul"):
@@ -540,8 +543,8 @@ class _IO:
 class HipOnnxSession:
     """the ``ort.InferenceSession`` surface the reference's ``infer`` uses (``run`` / ``get_inputs`` / ``get_providers``) over
     the HIP engine: a graph ``recognise`` maps to DB-ResNet18 runs on that launch graph (input float [B, 3, H, W] with H, W
-    multiples of 32 -> probability map [B, 1, H, W]); any other convolutional graph runs layer by layer through
-    ``pdf_table_amd.onnx_exec.HipGraphExecutor`` (``arch == "generic"``)."""
+    multiples of 32 -> probability map [B, 1, H, W]); any other graph -- convolutional, SVTR-type, or a CRNN-type recogniser with LSTM layers
+    of up to 128 units -- runs layer by layer through ``pdf_table_amd.onnx_exec.HipGraphExecutor`` (``arch == "generic"``)."""
 
     def __init__(self, src, engine=None, device: int = 0):
         from . import lib as L

@@ -81,6 +81,46 @@ def tile_conv_weight_x3(w: torch.Tensor) -> np.ndarray:
     return np.concatenate([th, th, tl], axis=1)
 
 
+def lstm_padded_sizes(hidden: int) -> Tuple[int, int]:
+    """(Hp, KS) of pt_op_lstm: the hidden size rounded up to 16, and the K steps of 32 that cover it"""
+    hp = (hidden + 15) // 16 * 16
+    return hp, (hp + 31) // 32
+
+
+def _lstm_r_index(hidden: int):
+    """for every value of one packed half of one direction, in packed order [(Hp / 16) unit blocks][4 gates][KS][64 lanes][8]: its row and column in
+    R [4H, H] and whether it is a real entry (padded units / padded K are zeros)"""
+    hp, ks = lstm_padded_sizes(hidden)
+    ub, g, kk, lane, j = np.meshgrid(np.arange(hp // 16), np.arange(4), np.arange(ks), np.arange(64), np.arange(8), indexing="ij")
+    unit = ub * 16 + (lane & 15)
+    k = kk * 32 + 8 * (lane >> 4) + j
+    return g * hidden + unit, k, (unit < hidden) & (k < hidden)
+
+
+def pack_lstm_r(r: np.ndarray, fmt: str = "bf16", split: bool = False) -> np.ndarray:
+    """ONNX LSTM recurrent weights R [dirs, 4H, H] (gates i, o, f, c) -> the 16-bit operand image pt_op_lstm keeps in LDS (csrc/lstm_op.hip):
+    uint16 [dirs][halves][(Hp / 16) * 4 * KS fragments][64 lanes][8], fragment (ub * 4 + gate) * KS + kk, lane l, element j =
+    R[gate * H + ub * 16 + (l & 15)][kk * 32 + 8 (l >> 4) + j] -- the A operand of the 16x16x32 MFMA; zeros where the unit or k is >= H.
+    split: two halves per direction, round16(R) and round16(R - hi) (the tolerance mode's three passes)."""
+    r = np.asarray(r, np.float32)
+    dirs, h4, hidden = r.shape
+    assert h4 == 4 * hidden and 0 < hidden <= 128, r.shape
+    row, col, real = _lstm_r_index(hidden)
+    full = torch.from_numpy(np.where(real, r[:, np.where(real, row, 0), np.where(real, col, 0)], np.float32(0.0)))
+    halves = split_bf16(full, fmt) if split else (full,)
+    return np.stack([to_bf16_bits(t, fmt).reshape(dirs, -1, 64, 8) for t in halves], axis=1)
+
+
+def unpack_lstm_r(packed: np.ndarray, hidden: int, fmt: str = "bf16") -> np.ndarray:
+    """the inverse of pack_lstm_r for tests and tools: -> fp32 [dirs, 4H, H] of the stored 16-bit values (hi + lo when there are two halves)"""
+    row, col, real = _lstm_r_index(hidden)
+    p = np.asarray(packed)
+    vals = torch.from_numpy(p.view(np.int16).reshape(p.shape[0], p.shape[1], *row.shape).copy()).view(FORMATS[fmt]).to(torch.float32).sum(1).numpy()
+    out = np.zeros((p.shape[0], 4 * hidden, hidden), np.float32)
+    out[:, row[real], col[real]] = vals[:, real]
+    return out
+
+
 def tile_conv_weight_f16x2(w: torch.Tensor) -> np.ndarray:
     """F16X2 tiles: ONE fp16 rounding of the weights (RNE), the same tile for the x_hi and the x_lo K chunks ->
     fp16 bits [N/64][2*Cin/32][taps][64][32] (stored under the 16-bit tag of the container)."""
