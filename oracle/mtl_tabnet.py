@@ -223,7 +223,9 @@ def mtl_preprocess(img, size=480):
         fw, fh = size / fh * fw, size
     else:
         fh, fw = size / fw * fh, size
-    nw, nh = int(fw), int(fh)
+    # a side that truncates to 0 (a crop more than `size` times as long as it is thick): cv2.resize raises there in the reference; the engine's
+    # contract is a 1-pixel side (mtl_resized, csrc/mtl_decoder.hip), restated here so that img_shape and the image stay comparable
+    nw, nh = max(int(fw), 1), max(int(fh), 1)
     r = db_pre.cv2_resize_linear_u8(img, nw, nh)
     pad = np.zeros((size, size, 3), dtype=np.uint8)
     pad[:nh, :nw] = r

@@ -78,7 +78,9 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 def pplcnet_preprocess(img_rgb: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
     """PPLCNetImageProcessor.preprocess (image_processing_pplcnet.py:327-455) for one RGB uint8 image:
-    resize -> * 1/255 -> (x - mean) / std -> float32 [3, out_h, out_w]"""
-    r = pil_resize_bilinear_u8(img_rgb, out_h, out_w).astype(np.float32) * np.float32(1 / 255)
+    resize -> * 1/255 -> (x - mean) / std -> float32 [3, out_h, out_w].  The rescale is transformers.image_transforms.rescale
+    (:305-312): the product in float64, then the cast to float32 -- not a float32 product, which differs in the last bit for 126 of
+    the 256 byte values; the normalisation is float32 arithmetic"""
+    r = (pil_resize_bilinear_u8(img_rgb, out_h, out_w).astype(np.float64) * (1 / 255)).astype(np.float32)
     r = (r - np.array(IMAGENET_MEAN, np.float32)) / np.array(IMAGENET_STD, np.float32)
     return np.ascontiguousarray(r.transpose(2, 0, 1)).astype(np.float32)
