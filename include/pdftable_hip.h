@@ -519,6 +519,27 @@ int pt_op_lstm(pt_engine* e, const uint16_t* d_pregates, int pg_cstride, const u
                uint16_t* d_y, int y_cstride, int split, pt_stream stream);
 int pt_op_lstm_packed_elems(int H, int dirs, int split);
 
+/* Per-axis strides, 1x3 / 3x1 kernels and rectangular pools (csrc/rect_ops.hip; since ABI 18): what a text-line recogniser's graph holds beyond the
+ * square operators above -- PaddleOCR's recognisers shrink the image height and keep its width.  No allocation and no host synchronisation
+ * (capturable).  Unsupported arguments return PT_ERR_INVALID with a message naming the values.
+ * pt_op_conv2d_rect: dense convolution on the matrix pipe, kh, kw each 1 or 3 and sh, sw each 1 or 2, independently; padding k / 2 per axis, so
+ * Ho = (H + 2 (kh / 2) - kh) / sh + 1 and likewise Wo.  Cin a multiple of 32, N of 64; d_w_tiled [N/64][Cin/32][kh kw][64][32]
+ * (weights.tile_conv_weight; three K sections w_hi | w_hi | w_lo from tile_conv_weight_x3 when split), d_bias fp32 [N].  fp32 accumulate, bias,
+ * act 0 none / 1 ReLU / 2 hardswish, one rounding on store into channels [out_coff, out_coff + N) of pixels out_cstride wide (the lo half
+ * out_lo_off further when split; all three multiples of 4).  Only kept outputs are computed and only existing taps multiplied; padding reads as
+ * zero and never reaches into the neighbouring image; H == 1 (token rows [B, 1, T, C]) is a first-class case.  No residual operand.  The first 3-tap
+ * call on a device raises that kernel's LDS limit (a host-side setting): made inside a stream capture it returns PT_ERR_STATE, so call once before capturing. */
+int pt_op_conv2d_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Cin, const uint16_t* d_w_tiled, const float* d_bias, int N, int kh,
+                      int kw, int sh, int sw, uint16_t* d_out, int out_cstride, int out_coff, int act, int split, int out_lo_off, pt_stream stream);
+/* depthwise k x k (k 3 or 5, pad k/2) with a stride per axis (sh, sw each 1 or 2) + bias + act; operands as pt_op_dwconv */
+int pt_op_dwconv_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C, const float* d_w_taps, const float* d_bias, int k, int sh, int sw,
+                      int act, uint16_t* d_out, int split, pt_stream stream);
+/* kind 0 max, 1 average over kh x kw windows (1 <= kh, kw <= 4, kh kw >= 2), stride = window, no padding; Ho = H / kh, Wo = W / kw rounded down
+ * (trailing rows / columns are dropped).  Max copies the winner's bits (compared on hi + lo when split, both halves copied); average sums in fp32,
+ * multiplies by 1 / (kh kw) and rounds (splits again) once.  C a multiple of 8. */
+int pt_op_pool_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C, int kind, int kh, int kw, uint16_t* d_out, int split,
+                    pt_stream stream);
+
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------
  * Replaces ClsImagePulcTask._preprocess/_run_model (ocr_pdf/cls_image_pulc_task.py:48-84): PPLCNetImageProcessor

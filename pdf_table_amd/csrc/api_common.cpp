@@ -22,6 +22,6 @@ const char* pt_last_error(void) { return g_err; }
 // modulated deformable convolution as a single operator); 11: pt_engine_set_mtl_kv_fp8; 10: pt_tsr_mtl_preprocess / decoder_config / structure / cells
 // (MtlTabNet decoders); 9: pt_rec_cvit_* (ConvNextViT recogniser); 8: pt_op_dwconv / add / maxpool / avgpool / chan_mean / scale_channels / act (generic
 // ONNX executor); 7: pt_rec_pp_preprocess*; 6: pt_engine_set_lstm_cluster, pt_engine_check clears what it reports
-int pt_abi_version(void) { return 17; }
+int pt_abi_version(void) { return 18; }
 
 }  // extern "C"

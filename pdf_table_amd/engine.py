@@ -804,6 +804,50 @@ class HipEngine:
         L.check(self.lib.pt_op_avgpool(self._h, _ptr(x), B, H, W, Cc // 2 if split else Cc, k, _ptr(out), int(split), self._stream()), "pt_op_avgpool")
         return out
 
+    # ---- per-axis strides, 1x3 / 3x1 kernels, rectangular pools (csrc/rect_ops.hip, ABI 18: the geometry of text-line recognisers) ----
+    def op_conv2d_rect(self, x: torch.Tensor, w_tiled: torch.Tensor, bias: torch.Tensor, kh: int, kw: int, sh: int = 1, sw: int = 1, act: int = 0,
+                       out: Optional[torch.Tensor] = None, out_coff: int = 0, split: int = 0) -> torch.Tensor:
+        """Dense convolution with kh, kw in {1, 3} and sh, sw in {1, 2} chosen per axis, padding k // 2 per axis.  x [B,H,W,Cin] ([hi | lo] when
+        split); w_tiled: weights.tile_conv_weight of [N, Cin, kh, kw] (tile_conv_weight_x3 when split); bias f32 [N]; act 0 none, 1 ReLU,
+        2 hardswish.  out / out_coff: write channels [out_coff, out_coff + N) of a wider tensor (the lo half at out.shape[-1] // 2 further)."""
+        self._chk(x, self.act_dtype, "x")
+        self._chk(bias, torch.float32, "bias")
+        B, H, W, Cin = x.shape
+        m = 2 if split else 1
+        Cin //= m
+        N = bias.numel()
+        Ho, Wo = (H + 2 * (kh // 2) - kh) // sh + 1, (W + 2 * (kw // 2) - kw) // sw + 1
+        if out is None:
+            out = torch.empty((B, Ho, Wo, N * m), dtype=self.act_dtype, device=self._tdev)
+        else:
+            self._chk(out, self.act_dtype, "out")
+            if tuple(out.shape[:3]) != (B, Ho, Wo):
+                raise ValueError(f"op_conv2d_rect: out must be [{B},{Ho},{Wo},C], got {tuple(out.shape)}")
+        L.check(self.lib.pt_op_conv2d_rect(self._h, _ptr(x), B, H, W, Cin, _ptr(w_tiled), _ptr(bias), N, kh, kw, sh, sw, _ptr(out), out.shape[-1],
+                                           out_coff, int(act), int(split), out.shape[-1] // 2, self._stream()), "pt_op_conv2d_rect")
+        return out
+
+    def op_dwconv_rect(self, x: torch.Tensor, w_taps: torch.Tensor, bias: torch.Tensor, k: int, sh: int, sw: int, act: int = 0, split: bool = False) -> torch.Tensor:
+        """depthwise k x k (3 / 5, pad k // 2) with a stride per axis; operands as op_dwconv"""
+        self._chk(x, self.act_dtype, "x")
+        self._chk(w_taps, torch.float32, "w_taps")
+        self._chk(bias, torch.float32, "bias")
+        B, H, W, Cc = x.shape
+        pad = k // 2
+        out = torch.empty((B, (H + 2 * pad - k) // max(sh, 1) + 1, (W + 2 * pad - k) // max(sw, 1) + 1, Cc), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_dwconv_rect(self._h, _ptr(x), B, H, W, Cc // 2 if split else Cc, _ptr(w_taps), _ptr(bias), k, sh, sw, act, _ptr(out),
+                                           int(split), self._stream()), "pt_op_dwconv_rect")
+        return out
+
+    def op_pool_rect(self, x: torch.Tensor, kind: int, kh: int, kw: int, split: bool = False) -> torch.Tensor:
+        """kind 0 max / 1 average over kh x kw windows, stride = window, no padding, sizes rounded down: [B,H,W,C] -> [B,H//kh,W//kw,C]"""
+        self._chk(x, self.act_dtype, "x")
+        B, H, W, Cc = x.shape
+        out = torch.empty((B, H // max(kh, 1), W // max(kw, 1), Cc), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_pool_rect(self._h, _ptr(x), B, H, W, Cc // 2 if split else Cc, kind, kh, kw, _ptr(out), int(split), self._stream()),
+                "pt_op_pool_rect")
+        return out
+
     def op_chan_mean(self, x: torch.Tensor, split: bool = False) -> torch.Tensor:
         """GlobalAveragePool: [B, H, W, C] -> [B, 1, 1, C]"""
         self._chk(x, self.act_dtype, "x")

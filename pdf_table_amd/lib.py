@@ -42,7 +42,7 @@ PT_CENTERNET_MAX_CELLS = 1000
 PT_ROTATE_90_CLOCKWISE, PT_ROTATE_180, PT_ROTATE_90_COUNTERCLOCKWISE = 0, 1, 2   # cv2.rotate codes (pt_page_quarter_turn)
 PT_REC_H, PT_REC_W, PT_REC_T, PT_REC_NCLS = 32, 640, 160, 7644
 PT_PROF_CLASSES = ("conv3x3", "conv1x1", "stem", "other")
-EXPECTED_ABI = 17         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h)
+EXPECTED_ABI = 18         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h)
 
 _lib = None
 
@@ -139,6 +139,9 @@ def _proto(lib):
         "pt_op_attention": (i, [vp, vp, i, i, i, i, i, C.c_float, vp, i, i, vp]),
         "pt_op_lstm": (i, [vp, vp, i, vp, i, i, i, i, i, vp, i, i, vp]),
         "pt_op_lstm_packed_elems": (i, [i, i, i]),
+        "pt_op_conv2d_rect": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, i, i, vp, i, i, i, i, i, vp]),
+        "pt_op_dwconv_rect": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, i, vp, i, vp]),
+        "pt_op_pool_rect": (i, [vp, vp, i, i, i, i, i, i, i, vp, i, vp]),
         "pt_profile_enable": (i, [vp, i]),
         "pt_profile_read": (i, [vp, vp, vp, vp]),
         "pt_profile_read_labels": (i, [vp, C.c_char_p, i]),

@@ -9,7 +9,8 @@ convolutional graph layer by layer:
   * ``OnnxGraph.layers()`` (BatchNorm folded, activations attached) is walked once at load time: convolution weights are
     padded and tiled for the MFMA implicit-GEMM kernel, depthwise weights put tap-major, everything uploaded;
   * ``run()`` issues ONE engine call per layer through the C ABI -- ``pt_op_conv2d`` (1x1 / 3x3, stride 1 / 2, ReLU /
-    hardswish / residual-add epilogue, 2x2 transposed convs as pixel-shuffle GEMMs), ``pt_op_dwconv``, ``pt_op_maxpool``,
+    hardswish / residual-add epilogue, 2x2 transposed convs as pixel-shuffle GEMMs), ``pt_op_conv2d_rect`` (a stride that differs per axis, 1x3 / 3x1
+    kernels: csrc/rect_ops.hip), ``pt_op_dwconv`` / ``pt_op_dwconv_rect``, ``pt_op_maxpool``, ``pt_op_avgpool``, ``pt_op_pool_rect``,
     ``pt_op_chan_mean``, ``pt_op_scale_channels``, ``pt_op_add``, ``pt_op_act``;
   * activations are bf16 NHWC tensors whose channel count is padded to a multiple of 64 with zeros (what the GEMM tiles
     want; zero weights keep the padding zero); PyTorch only owns the device memory and does the data MOVEMENT between
@@ -25,10 +26,11 @@ exactly one of the layouts its kernel reads -- NCHW map <-> token rows, a channe
 Anything else raises.
 
 There is no CPU path: an operator outside this set raises ``UnsupportedOnnxGraph`` naming it (oracle/onnx_ref.py executes
-graphs on the CPU for the tests only).  Supported today: Conv (groups 1: 1x1 / 3x3; depthwise: 3x3 / 5x5; stride 1 / 2,
-"same" padding), ConvTranspose 2x2 / stride 2, BatchNormalization (folded), Relu / HardSwish / Sigmoid / HardSigmoid /
-Relu6, a BatchNormalization that stands alone, Add, Mul by a per-channel gate, MaxPool(3, 2, 1) and k x k / stride k,
-AveragePool k x k / stride k, GlobalAveragePool, Resize / Upsample (nearest, integer factor, by scales or sizes), Concat over
+graphs on the CPU for the tests only).  Supported today: Conv (groups 1: kernels of 1 / 3 per axis -- 1x1, 3x3, 1x3, 3x1; depthwise: 3x3 / 5x5;
+stride 1 / 2 chosen per axis -- (2,1) and (1,2) included; padding k // 2 per axis), ConvTranspose 2x2 / stride 2, BatchNormalization (folded),
+Relu / HardSwish / Sigmoid / HardSigmoid / Relu6, a BatchNormalization that stands alone, Add, Mul by a per-channel gate, MaxPool(3, 2, 1),
+MaxPool / AveragePool over kh x kw windows (1 .. 4 per axis) with stride = window and no padding, sizes rounded down (ceil_mode only where
+both sizes divide), GlobalAveragePool, Resize / Upsample (nearest, integer factor, by scales or sizes), Concat over
 channels, Gemm / Flatten after a global pool; LayerNormalization, Gelu / swish, Softmax, fused-qkv attention on token rows; LSTM (forward /
 reverse / bidirectional, hidden size <= 128, zero initial states, default activations).
 
@@ -187,6 +189,8 @@ class HipGraphExecutor:
         for k, lay in enumerate(self.layers):
             if lay.op != "conv" or lay.act is not None or lay.attrs.get("group", 1) != 1 or lay.attrs["kernel"][0] not in (1, 3) or len(lay.outputs) != 1:
                 continue
+            if self._is_rect(lay):          # pt_op_conv2d_rect has no residual operand: conv -> pt_op_add -> activation, as unfused layers run
+                continue
             out = lay.outputs[0]
             if out in self.outputs or len(uses.get(out, ())) != 1:
                 continue
@@ -258,19 +262,26 @@ class HipGraphExecutor:
         return v
 
     # ---- layers ----------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _is_rect(lay: Layer) -> bool:
+        """a convolution whose kernel or stride differs between the axes: the csrc/rect_ops.hip entry points, not today's square ones"""
+        k, s_ = lay.attrs["kernel"], lay.attrs["strides"]
+        return k[0] != k[1] or s_[0] != s_[1]
+
     def _conv(self, k: int, lay: Layer, x: _Act, res: Optional[_Act] = None, res_act: int = 0) -> _Act:
         """res: the other operand of a residual Add folded into this convolution (plain group-1 convolutions without an activation of their own),
         res_act: the epilogue activation that follows the Add"""
         a = lay.attrs
         kh, kw = a["kernel"]
         sh, sw = a["strides"]
-        if a["dilations"] != [1, 1] or kh != kw or sh != sw or sh not in (1, 2):
-            raise UnsupportedOnnxGraph(f"{lay.name}: conv {a} (square kernels, stride 1 / 2, no dilation)")
-        if list(a["pads"]) != [kh // 2] * 4:
-            raise UnsupportedOnnxGraph(f"{lay.name}: conv padding {a['pads']} is not k // 2 on every side")
+        rect = self._is_rect(lay)
+        if a["dilations"] != [1, 1] or sh not in (1, 2) or sw not in (1, 2):
+            raise UnsupportedOnnxGraph(f"{lay.name}: conv {a} (no dilation; stride 1 / 2 per axis; dense kernels of 1 / 3 per axis, depthwise 3x3 / 5x5)")
+        if list(a["pads"]) != [kh // 2, kw // 2, kh // 2, kw // 2]:
+            raise UnsupportedOnnxGraph(f"{lay.name}: conv padding {a['pads']} of a {kh}x{kw} kernel is not k // 2 on every side of each axis")
         fused = _ACT_CODE.get(lay.act, None) if lay.act in _ACT_CODE else 0
         post = None if lay.act in _ACT_CODE else lay.act
-        if a["group"] == 1 and kh == 7 and sh == 2 and x.c == 3 and lay.weight.shape[0] <= 64 and lay.act == "relu":
+        if a["group"] == 1 and not rect and kh == 7 and sh == 2 and x.c == 3 and lay.weight.shape[0] <= 64 and lay.act == "relu":
             # the ResNet stem: 7x7 / stride 2 on the 3-channel image + ReLU -> the engine's stem kernel (K = [7][8][4], NHWC4 input)
             d = self._dev.get(k)
             if d is None:
@@ -293,15 +304,25 @@ class HipGraphExecutor:
             x4 = self._zeros(x.t.shape[:-1], 4)           # NHWC4 image ([hi rgb0 | lo rgb0] in the tolerance mode)
             self._copy(x.t, x4, 3)
             return _Act(self.eng.op_stem7x7(x4, d["w"], d["b"], split=self.split), d["n"])
-        if a["group"] == 1:
+        if a["group"] == 1 and rect:
+            # per-axis stride or a 1x3 / 3x1 kernel (the down-sampling blocks and the neck of a text-line recogniser): pt_op_conv2d_rect computes
+            # only the kept outputs and multiplies only the existing taps; same tiles as the square path, with kh kw taps
+            if kh not in (1, 3) or kw not in (1, 3):
+                raise UnsupportedOnnxGraph(f"{lay.name}: dense {kh}x{kw} convolution with strides {a['strides']} (the MFMA kernels cover kernels of 1 and 3 "
+                                           "per axis with strides of 1 and 2 per axis)")
+            if res is not None:
+                raise UnsupportedOnnxGraph(f"{lay.name}: a residual folded into a {kh}x{kw} / {a['strides']} convolution (that kernel has no residual operand)")
+            d = self._conv_operands(k, lay, self._cp(x), x.c)
+            y = _Act(self.eng.op_conv2d_rect(x.t, d["w"], d["b"], kh, kw, sh, sw, act=fused, split=int(self.split)), d["n"])
+        elif a["group"] == 1:
             if kh not in (1, 3):
-                raise UnsupportedOnnxGraph(f"{lay.name}: {kh}x{kw} convolution (the MFMA kernel covers 1x1 and 3x3)")
+                raise UnsupportedOnnxGraph(f"{lay.name}: dense {kh}x{kw} convolution (the MFMA kernels cover kernels of 1 and 3 per axis)")
             d = self._conv_operands(k, lay, self._cp(x), x.c)
             y = _Act(self.eng.op_conv2d(x.t, d["w"], d["b"], kh, sh, relu=fused if res is None else res_act, res=None if res is None else res.t,
                                         res_mode=0 if res is None else 1, split=int(self.split)), d["n"])
         elif a["group"] == x.c and lay.weight.shape[0] == x.c and lay.weight.shape[1] == 1:
-            if kh not in (3, 5):
-                raise UnsupportedOnnxGraph(f"{lay.name}: depthwise {kh}x{kw} (3x3 and 5x5 are built)")
+            if kh != kw or kh not in (3, 5):
+                raise UnsupportedOnnxGraph(f"{lay.name}: depthwise {kh}x{kw} (3x3 and 5x5 are built, with strides of 1 and 2 per axis)")
             d = self._dev.get(k)
             if d is None:
                 cp = self._cp(x)
@@ -311,10 +332,22 @@ class HipGraphExecutor:
                 if lay.bias is not None:
                     bt[:x.c] = lay.bias
                 d = self._dev[k] = {"w": self._up(wt), "b": self._up(bt)}
-            y = _Act(self.eng.op_dwconv(x.t, d["w"], d["b"], kh, sh, fused, split=self.split), x.c)
+            if rect:         # stride (2,1) / (1,2): the height of a text line shrinks, its width stays
+                y = _Act(self.eng.op_dwconv_rect(x.t, d["w"], d["b"], kh, sh, sw, fused, split=self.split), x.c)
+            else:
+                y = _Act(self.eng.op_dwconv(x.t, d["w"], d["b"], kh, sh, fused, split=self.split), x.c)
         else:
             raise UnsupportedOnnxGraph(f"{lay.name}: grouped convolution (group {a['group']} of {x.c} channels)")
         return self._post_act(lay, y, post)
+
+    @staticmethod
+    def _pool_rect_ok(a: dict, hh: int, ww: int) -> bool:
+        """pt_op_pool_rect: kh x kw windows (1 .. 4 per axis, at least two elements), stride = window, no padding, floor semantics -- a ceil_mode
+        that would change the size is refused"""
+        kk, st, pd = list(a["kernel"]), list(a["strides"]), a["pads"]
+        if st != kk or any(pd) or not (1 <= kk[0] <= 4 and 1 <= kk[1] <= 4 and kk[0] * kk[1] >= 2) or hh < kk[0] or ww < kk[1]:
+            return False
+        return not a.get("ceil_mode") or (hh % kk[0] == 0 and ww % kk[1] == 0)
 
     def _convT(self, k: int, lay: Layer, x: _Act) -> _Act:
         a = lay.attrs
@@ -778,15 +811,26 @@ class HipGraphExecutor:
             elif op == "maxpool":
                 a = lay.attrs
                 kk, st, pd = a["kernel"], a["strides"], a["pads"]
-                if kk[0] != kk[1] or st[0] != st[1] or len(set(pd)) != 1 or a.get("ceil_mode"):
-                    raise UnsupportedOnnxGraph(f"{lay.name}: MaxPool {a}")
-                y = _Act(self.eng.op_maxpool(ins[0].t, kk[0], st[0], pd[0], split=self.split), ins[0].c)
+                hh, ww = ins[0].t.shape[1], ins[0].t.shape[2]
+                square = kk[0] == kk[1] and st[0] == st[1] and len(set(pd)) == 1 and not a.get("ceil_mode")
+                if square and ((kk[0] == 3 and st[0] == 2 and pd[0] == 1) or (st[0] == kk[0] and pd[0] == 0 and kk[0] >= 2 and hh % kk[0] == 0 and ww % kk[0] == 0)):
+                    y = _Act(self.eng.op_maxpool(ins[0].t, kk[0], st[0], pd[0], split=self.split), ins[0].c)
+                elif self._pool_rect_ok(a, hh, ww):
+                    y = _Act(self.eng.op_pool_rect(ins[0].t, 0, kk[0], kk[1], split=self.split), ins[0].c)
+                else:
+                    raise UnsupportedOnnxGraph(f"{lay.name}: MaxPool {a} on a {hh} x {ww} map (built: MaxPool(3, 2, 1), and kh x kw windows of 1 .. 4 per axis "
+                                               "with stride = window and no padding, sizes rounded down; ceil_mode only where both sizes divide)")
             elif op == "avgpool":
                 a = lay.attrs
                 kk, st, pd = a["kernel"], a["strides"], a["pads"]
-                if kk[0] != kk[1] or st != kk or any(pd) or a.get("ceil_mode") or ins[0].t.shape[1] % kk[0] or ins[0].t.shape[2] % kk[0]:
-                    raise UnsupportedOnnxGraph(f"{lay.name}: AveragePool {a} (k x k / stride k without padding is built)")
-                y = _Act(self.eng.op_avgpool(ins[0].t, kk[0], split=self.split), ins[0].c)
+                hh, ww = ins[0].t.shape[1], ins[0].t.shape[2]
+                if not (kk[0] != kk[1] or st != kk or any(pd) or a.get("ceil_mode") or hh % kk[0] or ww % kk[0]):
+                    y = _Act(self.eng.op_avgpool(ins[0].t, kk[0], split=self.split), ins[0].c)
+                elif self._pool_rect_ok(a, hh, ww):
+                    y = _Act(self.eng.op_pool_rect(ins[0].t, 1, kk[0], kk[1], split=self.split), ins[0].c)
+                else:
+                    raise UnsupportedOnnxGraph(f"{lay.name}: AveragePool {a} on a {hh} x {ww} map (built: kh x kw windows of 1 .. 4 per axis with stride = window "
+                                               "and no padding, sizes rounded down; ceil_mode only where both sizes divide)")
             elif op == "bn":
                 # a BatchNormalization that could not be folded into a convolution: per-channel affine = a depthwise 3x3 whose only
                 # non-zero tap is the centre one
