@@ -540,6 +540,23 @@ int pt_op_dwconv_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, i
 int pt_op_pool_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C, int kind, int kh, int kw, uint16_t* d_out, int split,
                     pt_stream stream);
 
+/* PP-OCRv4 mobile detector blocks (csrc/det_ops.hip; added under ABI 18: two new entry points, no existing signature changed, so the version stays).  No allocation and no host synchronisation (capturable).
+ * pt_op_affine_act: y = s2[c] act(s1[c] x + b1[c]) + b2[c] over npix pixels of Cpad channels (a multiple of 8), 16-bit NHWC in the engine's storage
+ * format; act 0 none / 1 ReLU / 2 hardswish; the four vectors are fp32 [Cpad]; channels C .. Cpad of the output are written as zeros whatever the
+ * vectors hold there.  fp32 arithmetic, one rounding on store; split: (hi | lo) rows of 2 Cpad values, computed on hi + lo and split again.
+ * PP-LCNetV3's LearnableAffineBlock (scale x + bias) where it cannot be folded into a convolution, with the activation in front of it.
+ * pt_op_db_tail: the tail of a DB head in one launch -- ConvTranspose 2x2 / 2 (C -> C1) + ReLU, ConvTranspose 2x2 / 2 (C1 -> 1), Sigmoid:
+ *   out[b, 4y + 2dy + ey, 4x + 2dx + ex] = sigmoid(b2 + sum_c1 W2[c1, 0, ey, ex] relu(b1[c1] + sum_c W1[c, c1, dy, dx] x[b, y, x, c]))
+ * d_in 16-bit [B, H, W, Cpad] ([hi | lo] when split; channels C .. Cpad must hold zeros: the kernel reads C rounded up to 8, 16, 24, 32, 48 or 64 channels, i.e. up to 15 of them, against zero weights -- a NaN or Inf there would reach the result), d_w1 fp32 [C, C1, 2, 2],
+ * d_b1 fp32 [C1], d_w2 fp32 [C1, 1, 2, 2], d_b2 fp32 [1] (BatchNorm already folded), 1 <= C, C1 <= 64; d_out fp32 [B, 4H, 4W], 16-byte aligned.
+ * fp32 accumulation (fused multiply-adds); the C1-channel intermediate is never rounded to 16 bits.
+ * Alignment: d_w2, d_out and the four vectors of pt_op_affine_act are read / written 16 bytes at a time and must be 16-byte aligned (as are all
+ * 16-bit tensors of this ABI). */
+int pt_op_affine_act(pt_engine* e, const uint16_t* d_in, long long npix, int Cpad, int C, const float* d_s1, const float* d_b1, const float* d_s2,
+                     const float* d_b2, int act, uint16_t* d_out, int split, pt_stream stream);
+int pt_op_db_tail(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Cpad, int C, int C1, const float* d_w1, const float* d_b1,
+                  const float* d_w2, const float* d_b2, float* d_out, int split, pt_stream stream);
+
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------
  * Replaces ClsImagePulcTask._preprocess/_run_model (ocr_pdf/cls_image_pulc_task.py:48-84): PPLCNetImageProcessor

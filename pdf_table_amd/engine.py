@@ -848,6 +848,41 @@ class HipEngine:
                 "pt_op_pool_rect")
         return out
 
+    def op_affine_act(self, x: torch.Tensor, c: int, s1: Optional[torch.Tensor] = None, b1: Optional[torch.Tensor] = None, act: int = 0,
+                      s2: Optional[torch.Tensor] = None, b2: Optional[torch.Tensor] = None, split: bool = False) -> torch.Tensor:
+        """y = s2[c] act(s1[c] x + b1[c]) + b2[c] over a 16-bit NHWC map [.., Cpad] (csrc/det_ops.hip); act 0 none / 1 ReLU / 2 hardswish; the vectors are
+        fp32 [Cpad] (None: identity); channels c .. Cpad of the result are zeros"""
+        self._chk(x, self.act_dtype, "x")
+        cp = x.shape[-1] // 2 if split else x.shape[-1]
+        vec = []
+        for name, v, fill in (("s1", s1, 1.0), ("b1", b1, 0.0), ("s2", s2, 1.0), ("b2", b2, 0.0)):
+            if v is None:
+                v = torch.full((cp,), fill, dtype=torch.float32, device=self._tdev)
+            self._chk(v, torch.float32, name)
+            if v.numel() != cp:
+                raise ValueError(f"op_affine_act: {name} has {v.numel()} entries, the rows {cp} channels")
+            vec.append(v)
+        out = torch.empty_like(x)
+        L.check(self.lib.pt_op_affine_act(self._h, _ptr(x), x.numel() // x.shape[-1], cp, int(c), _ptr(vec[0]), _ptr(vec[1]), _ptr(vec[2]), _ptr(vec[3]),
+                                          int(act), _ptr(out), int(split), self._stream()), "pt_op_affine_act")
+        return out
+
+    def op_db_tail(self, x: torch.Tensor, c: int, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor, split: bool = False) -> torch.Tensor:
+        """the tail of a DB head in one launch (csrc/det_ops.hip): x 16-bit [B, H, W, Cpad] whose first c channels are real, w1 fp32 [c, C1, 2, 2],
+        b1 [C1], w2 [C1, 1, 2, 2], b2 [1] -> sigmoid(convT(relu(convT(x)))) as fp32 [B, 4H, 4W, 1]"""
+        self._chk(x, self.act_dtype, "x")
+        for name, v in (("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+            self._chk(v, torch.float32, name)
+        B, H, W, Cc = x.shape
+        cp = Cc // 2 if split else Cc
+        c1 = b1.numel()
+        if tuple(w1.shape) != (int(c), c1, 2, 2) or tuple(w2.shape) != (c1, 1, 2, 2) or b2.numel() != 1:
+            raise ValueError(f"op_db_tail: w1 {tuple(w1.shape)} / b1 [{c1}] / w2 {tuple(w2.shape)} / b2 [{b2.numel()}] for {c} input channels")
+        out = torch.empty((B, 4 * H, 4 * W, 1), dtype=torch.float32, device=self._tdev)
+        L.check(self.lib.pt_op_db_tail(self._h, _ptr(x), B, H, W, cp, int(c), c1, _ptr(w1), _ptr(b1), _ptr(w2), _ptr(b2), _ptr(out), int(split),
+                                       self._stream()), "pt_op_db_tail")
+        return out
+
     def op_chan_mean(self, x: torch.Tensor, split: bool = False) -> torch.Tensor:
         """GlobalAveragePool: [B, H, W, C] -> [B, 1, 1, C]"""
         self._chk(x, self.act_dtype, "x")

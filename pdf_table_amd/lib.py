@@ -42,7 +42,8 @@ PT_CENTERNET_MAX_CELLS = 1000
 PT_ROTATE_90_CLOCKWISE, PT_ROTATE_180, PT_ROTATE_90_COUNTERCLOCKWISE = 0, 1, 2   # cv2.rotate codes (pt_page_quarter_turn)
 PT_REC_H, PT_REC_W, PT_REC_T, PT_REC_NCLS = 32, 640, 160, 7644
 PT_PROF_CLASSES = ("conv3x3", "conv1x1", "stem", "other")
-EXPECTED_ABI = 18         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h)
+EXPECTED_ABI = 18         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h).  pt_op_affine_act /
+#                           pt_op_db_tail were ADDED under 18: no existing signature changed, and a library without them fails to bind by name (_proto)
 
 _lib = None
 
@@ -142,12 +143,17 @@ def _proto(lib):
         "pt_op_conv2d_rect": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, i, i, vp, i, i, i, i, i, vp]),
         "pt_op_dwconv_rect": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, i, vp, i, vp]),
         "pt_op_pool_rect": (i, [vp, vp, i, i, i, i, i, i, i, vp, i, vp]),
+        "pt_op_affine_act": (i, [vp, vp, C.c_longlong, i, i, vp, vp, vp, vp, i, vp, i, vp]),
+        "pt_op_db_tail": (i, [vp, vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, i, vp]),
         "pt_profile_enable": (i, [vp, i]),
         "pt_profile_read": (i, [vp, vp, vp, vp]),
         "pt_profile_read_labels": (i, [vp, C.c_char_p, i]),
     }
     for name, (res, args) in P.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is missing: loud by design
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:      # a library older than this binding (entry points are also ADDED without a version bump): loud by design
+            raise PtError(f"{LIB_PATH} does not export {name}: it was built from older sources; rebuild it (`python -m pdf_table_amd.build --force`)") from None
         fn.restype = res
         fn.argtypes = args
     return P

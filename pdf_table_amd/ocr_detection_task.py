@@ -95,7 +95,8 @@ class OcrDetectionTask(BaseInferTask):
                 # RSE-FPN + DB head): the layer list runs operator by operator between the engine's pre-processing and
                 # its bitmap / box-score kernels; an operator without a kernel is named when the first batch reaches it
                 from .onnx_exec import HipGraphExecutor
-                ex = HipGraphExecutor(graph, engine=self._engine, precision=self._exec_precision)
+                # fused_head=True: the DB head's tail (two 2x2 transposed convs, ReLU, Sigmoid) as one launch with an fp32 map (opt-in)
+                ex = HipGraphExecutor(graph, engine=self._engine, precision=self._exec_precision, fuse_db_tail=bool(self.kwargs.get("fused_head", False)))
                 if len(ex.outputs) != 1:
                     raise UnsupportedOnnxGraph(f"{onnx_path}: a text detector returns one probability map, this graph returns {ex.outputs}")
 

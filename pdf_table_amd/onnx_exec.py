@@ -11,7 +11,9 @@ convolutional graph layer by layer:
   * ``run()`` issues ONE engine call per layer through the C ABI -- ``pt_op_conv2d`` (1x1 / 3x3, stride 1 / 2, ReLU /
     hardswish / residual-add epilogue, 2x2 transposed convs as pixel-shuffle GEMMs), ``pt_op_conv2d_rect`` (a stride that differs per axis, 1x3 / 3x1
     kernels: csrc/rect_ops.hip), ``pt_op_dwconv`` / ``pt_op_dwconv_rect``, ``pt_op_maxpool``, ``pt_op_avgpool``, ``pt_op_pool_rect``,
-    ``pt_op_chan_mean``, ``pt_op_scale_channels``, ``pt_op_add``, ``pt_op_act``;
+    ``pt_op_chan_mean``, ``pt_op_scale_channels``, ``pt_op_add``, ``pt_op_act``, ``pt_op_affine_act`` (a constant per-channel affine the importer could
+    not fold into a convolution, with the ReLU / hardswish in front of it: PP-LCNetV3's LearnableAffineBlock; csrc/det_ops.hip) and, with
+    ``fuse_db_tail=True``, ``pt_op_db_tail`` (a DB head's two transposed convolutions, ReLU and Sigmoid in one launch, fp32 result);
   * activations are bf16 NHWC tensors whose channel count is padded to a multiple of 64 with zeros (what the GEMM tiles
     want; zero weights keep the padding zero); PyTorch only owns the device memory and does the data MOVEMENT between
     layers that has no arithmetic in it (NCHW <-> NHWC, channel concat, nearest-neighbour up-sampling, the final cast).
@@ -28,7 +30,9 @@ Anything else raises.
 There is no CPU path: an operator outside this set raises ``UnsupportedOnnxGraph`` naming it (oracle/onnx_ref.py executes
 graphs on the CPU for the tests only).  Supported today: Conv (groups 1: kernels of 1 / 3 per axis -- 1x1, 3x3, 1x3, 3x1; depthwise: 3x3 / 5x5;
 stride 1 / 2 chosen per axis -- (2,1) and (1,2) included; padding k // 2 per axis), ConvTranspose 2x2 / stride 2, BatchNormalization (folded),
-Relu / HardSwish / Sigmoid / HardSigmoid / Relu6, a BatchNormalization that stands alone, Add, Mul by a per-channel gate, MaxPool(3, 2, 1),
+Relu / HardSwish / Sigmoid / HardSigmoid / Relu6, a BatchNormalization that stands alone, Add, Mul by a per-channel gate, Mul / Add / Sub / Div of a feature
+map with a constant scalar or [C, 1, 1] / [1, C, 1, 1] vector (x - c and x / c included; folded into the neighbouring convolution where that is exact, chains
+collapsed; c - x and c / x are refused), MaxPool(3, 2, 1),
 MaxPool / AveragePool over kh x kw windows (1 .. 4 per axis) with stride = window and no padding, sizes rounded down (ceil_mode only where
 both sizes divide), GlobalAveragePool, Resize / Upsample (nearest, integer factor, by scales or sizes), Concat over
 channels, Gemm / Flatten after a global pool; LayerNormalization, Gelu / swish, Softmax, fused-qkv attention on token rows; LSTM (forward /
@@ -136,7 +140,10 @@ _CAPTURE_LOCK = threading.Lock()      # graph capture is serialised across execu
 
 
 class HipGraphExecutor:
-    def __init__(self, src, engine: Optional[HipEngine] = None, device: int = 0, precision: str = "bf16"):
+    def __init__(self, src, engine: Optional[HipEngine] = None, device: int = 0, precision: str = "bf16", fuse_db_tail: bool = False):
+        """fuse_db_tail: run a DB head's tail -- convT 2x2 / 2 + ReLU -> convT 2x2 / 2 to one channel + Sigmoid, the graph's output -- as ONE
+        pt_op_db_tail launch with an fp32 result (see _plan_db_tail).  Off by default: the fused launch keeps the intermediate in fp32 where the layered
+        route rounds it to 16 bits, so its bits differ from the layered route's."""
         if precision not in ("bf16", "bf16x3", "f16"):
             raise ValueError(f"precision '{precision}': 'bf16' (throughput), 'f16' (single-pass IEEE half, the reference's fp16) or 'bf16x3' "
                              "(tolerance mode, (hi | lo) activations)")
@@ -168,6 +175,7 @@ class HipGraphExecutor:
         self._seen: set = set()                                 # shapes that ran once eagerly (the next call captures)
         self._bad: set = set()                                  # shapes whose capture raised: eager from then on
         self._fuse = self._plan_add_fusion()
+        self._tail = self._plan_db_tail() if fuse_db_tail else {}
         # every tensor some layer reads (constants included): an LSTM's Y_h / Y_c are supported only when nothing does
         self._read = {nm for l in self.layers for nm in list(l.inputs) + list(l.attrs.get("all_inputs", ())) if nm} | set(self.outputs)
 
@@ -210,6 +218,63 @@ class HipGraphExecutor:
             plan[k] = (j, other, act)
             taken.add(j)
         return plan
+
+    def _plan_db_tail(self) -> Dict[int, int]:
+        """convT (2x2 / 2, no padding, group 1) + ReLU -> convT (2x2 / 2, one output channel) + Sigmoid whose output is a graph output, every
+        intermediate read by the next layer only (the importer attaches an activation to its convolution under exactly that condition), at most 64
+        channels into and between them -> {index of the first convT: index of the second}: one pt_op_db_tail launch (csrc/det_ops.hip)."""
+        uses: Dict[str, List[int]] = {}
+        for j, lay in enumerate(self.layers):
+            for nm in lay.inputs:
+                uses.setdefault(nm, []).append(j)
+
+        def tail_convT(lay, act):
+            a = lay.attrs
+            return (lay.op == "convT" and a["kernel"] == [2, 2] and a["strides"] == [2, 2] and a["group"] == 1 and not any(a["pads"])
+                    and a["dilations"] == [1, 1] and not any(lay.attrs.get("node_attrs", {}).get("output_padding", ())) and lay.act == act and len(lay.outputs) == 1)
+        plan: Dict[int, int] = {}
+        for k, lay in enumerate(self.layers):
+            if not tail_convT(lay, "relu") or lay.outputs[0] in self.outputs or len(uses.get(lay.outputs[0], ())) != 1:
+                continue
+            j = uses[lay.outputs[0]][0]
+            nx = self.layers[j]
+            if not tail_convT(nx, "sigmoid") or nx.outputs[0] not in self.outputs or uses.get(nx.outputs[0]):
+                continue
+            if nx.weight.shape[1] != 1 or nx.weight.shape[0] != lay.weight.shape[1] or lay.weight.shape[0] > 64 or lay.weight.shape[1] > 64:
+                continue
+            plan[k] = j
+        return plan
+
+    def _db_tail(self, k: int, x: _Act) -> _Act:
+        lay, nx = self.layers[k], self.layers[self._tail[k]]
+        if x.c != lay.weight.shape[0]:
+            raise UnsupportedOnnxGraph(f"{lay.name}: weight expects {lay.weight.shape[0]} input channels, the tensor has {x.c}")
+        d = self._dev.get(k)
+        if d is None or "w2" not in d:
+            c1 = lay.weight.shape[1]
+            d = self._dev[k] = {"w1": self._up(lay.weight.astype(np.float32)), "b1": self._up(np.zeros(c1, np.float32) if lay.bias is None else lay.bias.astype(np.float32)),
+                                "w2": self._up(nx.weight.astype(np.float32)), "b2": self._up(np.zeros(1, np.float32) if nx.bias is None else nx.bias.astype(np.float32))}
+        return _Act(self.eng.op_db_tail(x.t, x.c, d["w1"], d["b1"], d["w2"], d["b2"], split=self.split), 1)
+
+    def _affine(self, k: int, lay: Layer, x: _Act) -> _Act:
+        """y = s2 act(s1 x + b1) + b2 with per-channel constants (scalars broadcast): pt_op_affine_act"""
+        if lay.attrs.get("act") not in _ACT_CODE:
+            raise UnsupportedOnnxGraph(f"{lay.name}: activation '{lay.attrs.get('act')}' inside a constant affine")
+        cp = self._cp(x)
+        d = self._dev.get(k)
+        if d is None or d["cp"] != cp:
+            d = {"cp": cp}
+            for nm, fill in (("s1", 1.0), ("b1", 0.0), ("s2", 1.0), ("b2", 0.0)):
+                v = lay.extra.get(nm)
+                v = np.full(1, fill) if v is None else np.asarray(v, np.float64).reshape(-1)
+                if v.size not in (1, x.c) or (v.size != 1 and (x.seq or x.flat)):
+                    raise UnsupportedOnnxGraph(f"{lay.name}: a constant of {v.size} entries with a {x.shape()} tensor (built: a scalar, or one value per channel "
+                                               "of a feature map [B, C, H, W])")
+                full = np.zeros(cp, np.float32)
+                full[:x.c] = np.broadcast_to(v, (x.c,)).astype(np.float32)
+                d[nm] = self._up(full)
+            self._dev[k] = d
+        return _Act(self.eng.op_affine_act(x.t, x.c, d["s1"], d["b1"], _ACT_CODE[lay.attrs.get("act")], d["s2"], d["b2"], split=self.split), x.c, x.flat, x.seq)
 
     # ---- weights ---------------------------------------------------------------------------------------------------
     def _up(self, a: np.ndarray, dtype=None) -> torch.Tensor:
@@ -717,6 +782,21 @@ class HipGraphExecutor:
                 env[o] = np.asarray(v) if isinstance(v, (np.generic, int, float)) else v      # host constants stay ndarrays (0-d included)
             return True
         raw = [env[i] for i in lay.inputs if i in env]
+        if op == "affine" and len(raw) == 1 and isinstance(raw[0], (_View, _Scores, np.ndarray)):
+            # what the importer could not tell from a feature map's affine: arithmetic on a host constant, and the scalar in front of an attention
+            v, chain = raw[0], lay.attrs.get("chain")
+            if chain is None or (not isinstance(v, np.ndarray) and any(c.size != 1 for _, c in chain)):
+                raise UnsupportedOnnxGraph(f"{lay.name}: constant arithmetic with an activation, or with a per-channel constant, on a re-indexed tensor")
+            for cop, cst in chain:
+                if isinstance(v, np.ndarray):
+                    v = np.asarray({"add": np.add, "mul": np.multiply, "sub": np.subtract, "div": np.divide}[cop](v, cst))
+                elif cop in ("mul", "div"):
+                    f = float(cst.reshape(-1)[0]) if cop == "mul" else 1.0 / float(cst.reshape(-1)[0])
+                    v = _View(v.base, v.idx, v.scale * f) if isinstance(v, _View) else _Scores(v.base, v.heads, v.d, v.scale * f, v.soft)
+                else:
+                    raise UnsupportedOnnxGraph(f"{lay.name}: {cop.capitalize()} of a re-indexed tensor with a constant (a scalar factor in front of an attention is built)")
+            env[lay.outputs[0]] = v
+            return True
         if op in ("add", "mul", "sub", "div") and lay.extra and all(np.asarray(v).size == 1 for v in lay.extra.values()) and len(raw) == 1 \
                 and isinstance(raw[0], (_View, _Scores, np.ndarray)):
             cst = float(np.asarray(next(iter(lay.extra.values()))).reshape(-1)[0])
@@ -807,7 +887,15 @@ class HipGraphExecutor:
                 if y is None:
                     y = self._conv(k, lay, ins[0])
             elif op == "convT":
+                if k in self._tail and not (ins[0].seq or ins[0].flat):
+                    y = self._db_tail(k, ins[0])
+                    skip.add(self._tail[k])
+                    for o in self.layers[self._tail[k]].outputs:
+                        env[o] = y
+                    continue
                 y = self._convT(k, lay, ins[0])
+            elif op == "affine":
+                y = self._affine(k, lay, ins[0])
             elif op == "maxpool":
                 a = lay.attrs
                 kk, st, pd = a["kernel"], a["strides"], a["pads"]
@@ -861,13 +949,13 @@ class HipGraphExecutor:
                 y = _Act(self.eng.op_layernorm(x.t, x.c, d["g"], d["b"], lay.attrs["epsilon"], split=self.split), x.c, x.flat, x.seq)
             elif op == "add":
                 if len(ins) != 2 or lay.extra:
-                    raise UnsupportedOnnxGraph(f"{lay.name}: Add with a constant operand")
+                    raise UnsupportedOnnxGraph(f"{lay.name}: Add with a constant operand (built: a scalar, or a [C, 1, 1] / [1, C, 1, 1] vector, added to a feature map)")
                 if ins[0].t.shape != ins[1].t.shape:
                     raise UnsupportedOnnxGraph(f"{lay.name}: Add of {tuple(ins[0].t.shape)} and {tuple(ins[1].t.shape)} (broadcasting is not built)")
                 y = _Act(self.eng.op_add(ins[0].t, ins[1].t, split=self.split), ins[0].c, ins[0].flat, ins[0].seq)
             elif op == "mul":
                 if len(ins) != 2 or lay.extra:
-                    raise UnsupportedOnnxGraph(f"{lay.name}: Mul with a constant operand")
+                    raise UnsupportedOnnxGraph(f"{lay.name}: Mul with a constant operand (built: a scalar, or a [C, 1, 1] / [1, C, 1, 1] vector, times a feature map)")
                 if ins[0].t.shape == ins[1].t.shape:
                     y = _Act(self.eng.op_mul(ins[0].t, ins[1].t, split=self.split), ins[0].c, ins[0].flat, ins[0].seq)
                 else:
@@ -911,6 +999,12 @@ class HipGraphExecutor:
                 lay2 = Layer("conv", lay.name, lay.inputs, lay.outputs, {}, weight=lay.weight.reshape(lay.weight.shape[0], -1, 1, 1), bias=lay.bias)
                 d = self._conv_operands(k, lay2, self._cp(src), src.c)
                 y = _Act(self.eng.op_conv2d(src.t, d["w"], d["b"], 1, 1, split=int(self.split)), d["n"], not src.seq, src.seq)
+            elif op in ("sub", "div"):
+                sym = "-" if op == "sub" else "/"
+                if lay.extra and lay.attrs["all_inputs"][0] in self.graph.init:
+                    raise UnsupportedOnnxGraph(f"{lay.name}: {op.capitalize()} with the constant as its first operand (c {sym} x; built: x {sym} c with a scalar or a "
+                                               "per-channel vector of a feature map)")
+                raise UnsupportedOnnxGraph(f"{lay.name}: {op.capitalize()} of {'a tensor and a constant of this shape' if lay.extra else 'two computed tensors'} has no kernel")
             else:
                 raise UnsupportedOnnxGraph(f"{lay.name}: layer kind '{op}' has no executor")
             if tmaj is not None:

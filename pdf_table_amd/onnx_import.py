@@ -6,7 +6,9 @@ prepare_onnx_model`` utils/deploy_utils.py:243-280; ``infer`` :366-370 calls ``p
 
   * ``pdf_table_amd.onnx_proto`` decodes the file without the ``onnx`` package;
   * ``OnnxGraph.layers()`` normalises the node list into the ENGINE LAYER LIST -- one record per kernel-sized unit:
-    Conv / ConvTranspose with the following BatchNormalization folded (float64) and the following activation attached,
+    Conv / ConvTranspose with the following BatchNormalization and constant affine (scale x + bias) folded (float64) and the following activation attached,
+    every other constant affine of a feature map as one ``affine`` layer (chains collapsed, the ReLU / hardswish in front of it included) or folded forward
+    into an unpadded 1x1 convolution,
     pooling, Resize, Add, Concat, Mul, GlobalAveragePool, LSTM, Gemm / MatMul, shape glue -- and names every operator the
     engine has no kernel for (``unsupported_ops``);
   * ``recognise()`` matches the layer list against the network architectures the engine has launch graphs for
@@ -52,7 +54,7 @@ class UnsupportedOnnxGraph(RuntimeError):
 @dataclass
 class Layer:
     """one entry of the engine layer list"""
-    op: str                               # conv | convT | maxpool | avgpool | gap | resize | add | mul | concat | lstm | gemm | act | glue
+    op: str                               # conv | convT | maxpool | avgpool | gap | resize | add | mul | affine | concat | lstm | gemm | act | glue
     name: str
     inputs: List[str]
     outputs: List[str]
@@ -67,7 +69,8 @@ class Layer:
         w = "" if self.weight is None else f" w{list(self.weight.shape)}"
         a = f" +{self.act}" if self.act else ""
         at = {k: v for k, v in self.attrs.items() if k in ("kernel", "strides", "pads", "group", "scale", "axis")}
-        return f"{self.op}{w}{' +bn' if self.bn_folded else ''}{a} {at if at else ''}".rstrip()
+        f = (" +affine" if self.attrs.get("affine_folded") else "") + (" affine+" if self.attrs.get("affine_folded_in") else "")
+        return f"{self.op}{w}{' +bn' if self.bn_folded else ''}{f}{a} {at if at else ''}".rstrip()
 
 
 class OnnxGraph:
@@ -138,6 +141,79 @@ class OnnxGraph:
     def _only(self, tensor: str, op: str) -> Optional[int]:
         """index of the ONLY consumer of `tensor` if it is an `op` node"""
         return self._sole_consumer(tensor, (op,))
+
+    def _affine_const(self, n: OnnxNode):
+        """Mul / Add / Sub / Div of a computed tensor with ONE floating-point constant of size 1, or of shape [C, 1, 1] / [1, C, 1, 1] (a per-channel
+        vector of a feature map [B, C, H, W]) -> (s, b) with node(x) = s x + b, float64 vectors of 1 or C entries; x - c and x / c fold the obvious
+        way, c - x and c / x are not affine in this sense (None, like every other operand shape)"""
+        if n.op_type not in ("Add", "Mul", "Sub", "Div") or len(n.inputs) != 2:
+            return None
+        ci = [q for q, i in enumerate(n.inputs) if i in self.init]
+        if len(ci) != 1 or (ci[0] == 0 and n.op_type in ("Sub", "Div")):
+            return None
+        v = np.asarray(self.init[n.inputs[ci[0]]])
+        if v.dtype.kind != "f" or not (v.size == 1 or (v.ndim == 3 and v.shape[1:] == (1, 1)) or (v.ndim == 4 and v.shape[0] == 1 and v.shape[2:] == (1, 1))):
+            return None
+        c = v.astype(np.float64).reshape(-1)
+        if n.op_type == "Div" and np.any(c == 0):
+            return None
+        one, zero = np.ones_like(c), np.zeros_like(c)
+        return {"Mul": (c, zero), "Add": (one, c), "Sub": (one, -c), "Div": (1.0 / c, zero)}[n.op_type]
+
+    def _affine_chain(self, tensor: str, s=None, b=None):
+        """the affine nodes that follow `tensor` one after the other, each the ONLY consumer of the one before, collapsed into one (s, b):
+        -> (node indices, s, b, last output); no node: ([], s, b, tensor)"""
+        idx = []
+        while True:
+            j = self._sole_consumer(tensor, ("Add", "Mul", "Sub", "Div"))
+            sb = self._affine_const(self.nodes[j]) if j is not None else None
+            if sb is None:
+                return idx, s, b, tensor
+            s, b = (sb[0], sb[1]) if s is None else (sb[0] * s, sb[0] * b + sb[1])
+            idx.append(j)
+            tensor = self.nodes[j].outputs[0]
+
+    def _plain_act_after(self, tensor: str):
+        """a ReLU or hardswish (the node, or x * HardSigmoid(x)) that is the only consumer of `tensor`: -> (node indices, kind, output) or None"""
+        hs = self._hardswish_pair(tensor)
+        if hs is not None:
+            return [hs[0], hs[1]], "hardswish", hs[2]
+        j = self._sole_consumer(tensor, ("Relu", "HardSwish"))
+        if j is None:
+            return None
+        return [j], _ACTS[self.nodes[j].op_type], self.nodes[j].outputs[0]
+
+    def _affine_layer(self, k: int, used: set) -> Optional[Layer]:
+        """node k opens y = s2 act(s1 x + b1) + b2 (layer kind 'affine', pt_op_affine_act): an affine chain, optionally a ReLU / hardswish behind it and a
+        second chain behind that; or a stand-alone ReLU / hardswish with an affine chain behind it.  None: node k is neither."""
+        n = self.nodes[k]
+        x = None
+        s1 = b1 = act = None
+        chain = []
+        if n.op_type in ("Relu", "HardSwish"):
+            x, cur, act, idx1 = n.inputs[0], n.outputs[0], _ACTS[n.op_type], [k]
+        else:
+            sb = self._affine_const(n)
+            if sb is None:
+                return None
+            x = next(i for i in n.inputs if i not in self.init)
+            idx1, s1, b1, cur = self._affine_chain(n.outputs[0], sb[0], sb[1])
+            idx1 = [k] + idx1
+            chain = [(self.nodes[j].op_type.lower(), np.asarray(next(self.init[i] for i in self.nodes[j].inputs if i in self.init))) for j in idx1]
+            a = self._plain_act_after(cur)
+            if a is not None:
+                # the activation joins only if an affine chain follows it (otherwise it stays a layer of its own, as before)
+                idx2, s2, b2, end = self._affine_chain(a[2])
+                if idx2:
+                    used.update(idx1 + a[0] + idx2)
+                    return Layer("affine", n.name or end, [x], [end], {"act": a[1], "nodes": len(idx1) + len(idx2)}, extra={"s1": s1, "b1": b1, "s2": s2, "b2": b2})
+            used.update(idx1)
+            return Layer("affine", n.name or cur, [x], [cur], {"act": None, "nodes": len(idx1), "chain": chain}, extra={"s1": s1, "b1": b1, "s2": None, "b2": None})
+        idx2, s2, b2, end = self._affine_chain(cur)
+        if not idx2:
+            return None
+        used.update(idx1 + idx2)
+        return Layer("affine", n.name or end, [x], [end], {"act": act, "nodes": len(idx2)}, extra={"s1": None, "b1": None, "s2": s2, "b2": b2})
 
     def _match_layernorm(self, k: int):
         """ReduceMean(x, -1) -> Sub(x, .) -> Pow(., 2) -> ReduceMean(-1) -> Add(eps) -> Sqrt -> Div(sub, .) -> Mul(gamma) -> Add(beta): how
@@ -276,6 +352,20 @@ class OnnxGraph:
                     lay.bn_folded = True
                     used.add(j)
                     cur = bn.outputs[0]
+                # a constant affine behind the convolution (PP-LCNetV3's LearnableAffineBlock: scale x + bias with two learned scalars), nothing between
+                # them and nothing else reading the convolution: W' = s W, bias' = s bias + b in float64, like the BatchNorm above
+                ja, sa, ba, cur_a = self._affine_chain(cur)
+                if ja and not (t == "ConvTranspose" and lay.attrs["group"] != 1 and sa.size != 1):
+                    shp = (-1, 1, 1, 1) if t == "Conv" else (1, -1, 1, 1)
+                    sv, bv = np.broadcast_to(sa, (cout,)), np.broadcast_to(ba, (cout,))
+                    if sa.size not in (1, cout) or ba.size not in (1, cout):
+                        raise UnsupportedOnnxGraph(f"{t} '{n.name}': a per-channel constant of {max(sa.size, ba.size)} entries behind {cout} output channels")
+                    lay.weight = (lay.weight.astype(np.float64) * sv.reshape(shp)).astype(np.float32)
+                    b0 = np.zeros(cout) if lay.bias is None else lay.bias.astype(np.float64)
+                    lay.bias = (b0 * sv + bv).astype(np.float32)
+                    lay.attrs["affine_folded"] = len(ja)
+                    used.update(ja)
+                    cur = cur_a
                 hs = self._hardswish_pair(cur)
                 if hs is not None:                  # x * HardSigmoid(x): how hardswish exports below opset 14 (and from Paddle)
                     lay.act = "hardswish"
@@ -319,6 +409,8 @@ class OnnxGraph:
                 out.append(Layer("resize", n.name or n.outputs[0], [n.inputs[0]], [n.outputs[0]],
                                  {"mode": n.attrs.get("mode", "nearest"), "scale": scale, "sizes": sizes,
                                   "coordinate_transformation_mode": n.attrs.get("coordinate_transformation_mode", "")}))
+            elif t in ("Add", "Mul", "Sub", "Div", "Relu", "HardSwish") and (aff := self._affine_layer(k, used)) is not None:
+                out.append(aff)
             elif t in ("Add", "Mul", "Sub", "Div"):
                 consts = {i: self.init[i] for i in n.inputs if i in self.init}
                 out.append(Layer(t.lower(), n.name or n.outputs[0], [i for i in n.inputs if i not in consts], [n.outputs[0]], {"all_inputs": list(n.inputs)},
@@ -359,7 +451,40 @@ class OnnxGraph:
             else:
                 out.append(Layer("glue" if t in ENGINE_OPS else "unsupported", n.name or n.outputs[0], [i for i in n.inputs if i not in self.init],
                                  list(n.outputs), {"onnx_op": t, "all_inputs": list(n.inputs), "node_attrs": dict(n.attrs)}))
-        return out
+        return self._fold_affine_forward(out)
+
+    def _fold_affine_forward(self, layers: List[Layer]) -> List[Layer]:
+        """an `affine` layer without an activation whose ONLY reader is a 1x1 / stride-1 / group-1 convolution without padding: folded into that
+        convolution's input side -- W'[o, i] = W[o, i] s[i], bias'[o] = bias[o] + sum_i W[o, i] b[i], float64 -- which is exact because no zero is
+        padded in behind the affine (in front of a padded 3x3 / 5x5 the border would see b where the graph has 0: those stay on the kernel)"""
+        readers: Dict[str, List[int]] = {}
+        for j, lay in enumerate(layers):
+            for nm in set(lay.inputs) | set(lay.attrs.get("all_inputs", ())):
+                readers.setdefault(nm, []).append(j)
+        drop = set()
+        for k, lay in enumerate(layers):
+            if lay.op != "affine" or lay.attrs.get("act") is not None or lay.extra.get("s2") is not None or lay.outputs[0] in self.graph_outputs:
+                continue
+            r = readers.get(lay.outputs[0], [])
+            if len(r) != 1:
+                continue
+            cv = layers[r[0]]
+            a = cv.attrs
+            if cv.op != "conv" or a["kernel"] != [1, 1] or a["strides"] != [1, 1] or a["group"] != 1 or any(a["pads"]) or a["dilations"] != [1, 1] \
+                    or cv.inputs != [lay.outputs[0]]:
+                continue
+            cin = cv.weight.shape[1]
+            s, b = lay.extra["s1"], lay.extra["b1"]
+            if s.size not in (1, cin) or b.size not in (1, cin):
+                continue
+            w = cv.weight.astype(np.float64)
+            b0 = np.zeros(w.shape[0]) if cv.bias is None else cv.bias.astype(np.float64)
+            cv.bias = (b0 + (w[:, :, 0, 0] * np.broadcast_to(b, (cin,))[None, :]).sum(1)).astype(np.float32)
+            cv.weight = (w * np.broadcast_to(s, (cin,)).reshape(1, -1, 1, 1)).astype(np.float32)
+            cv.inputs = list(lay.inputs)
+            cv.attrs["affine_folded_in"] = lay.attrs["nodes"]
+            drop.add(k)
+        return [lay for k, lay in enumerate(layers) if k not in drop]
 
     def summary(self) -> str:
         lines = [f"ONNX graph '{self.model.graph_name}' (opset {self.model.opset}, producer '{self.model.producer}'): "
