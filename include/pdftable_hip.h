@@ -444,6 +444,18 @@ int pt_op_conv1x1_ex(pt_engine* e, const uint16_t* d_in, int B, int H, int W, in
 int pt_op_dcn(pt_engine* e, const uint16_t* d_in, const float* d_om, int B, int H, int W, int C, const uint16_t* d_w_tiled,
               const float* d_bias, int N, uint16_t* d_out, int relu, int split, pt_stream stream);
 
+/* IDAUp's up-sampler: depthwise ConvTranspose2d(C, C, 2f, stride f, padding f/2, groups = C) of d_in [B,h,w,C] (+ d_add [B,h*f,w*f,C], may be
+ * NULL) -> d_out [B,h*f,w*f,C]; d_w fp32 [(2f)^2][C] (tap-major), f = 2 or 4, C % 8 == 0 ([hi | lo] maps when split).  Added under ABI 18 (no existing signature changed). */
+int pt_op_dwconvt_up_add(pt_engine* e, const uint16_t* d_in, const float* d_w, const uint16_t* d_add, uint16_t* d_out, int B, int h, int w, int C,
+                         int f, int split, pt_stream stream);
+/* pt_op_dcn followed by pt_op_dwconvt_up_add(d_up_in, d_up_w, add = the convolution's output) in one launch, bit for bit: the up-sampler runs in
+ * the convolution's epilogue and the un-summed output is never written.  d_up_in [B,up_h,up_w,N] with up_h * up_f == H and up_w * up_f == W,
+ * d_up_w fp32 [(2 up_f)^2][N].  C == N == 64 (up_f 2 or 4) or 128 (up_f 2), split == 0, default kernel settings only (no PT_DCN_* variable, no
+ * pt_engine_set_dcn_mfma): anything else is PT_ERR_INVALID.  Added under ABI 18. */
+int pt_op_dcn_up_add(pt_engine* e, const uint16_t* d_in, const float* d_om, int B, int H, int W, int C, const uint16_t* d_w_tiled,
+                     const float* d_bias, int N, uint16_t* d_out, int relu, int split, const uint16_t* d_up_in, int up_h, int up_w,
+                     const float* d_up_w, int up_f, pt_stream stream);
+
 /* Stem of the ResNet-18 backbone: 7x7 s2 p3 conv (BN folded) + ReLU on a bf16 NHWC4 image (dbnet.py:272-275).
  * d_w is bf16 [64][7][8][4] (K padded: tap s=7 and channel 3 are zero), d_bias fp32 [64]; out bf16 [B,H/2,W/2,64]. */
 int pt_op_stem7x7(pt_engine* e, const uint16_t* d_in, int B, int H, int W, const uint16_t* d_w, const float* d_bias,

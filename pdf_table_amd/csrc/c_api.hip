@@ -1019,6 +1019,25 @@ int pt_op_dcn(pt_engine* e, const uint16_t* d_in, const float* d_om, int B, int 
   return pt_launch_dcn_fused(e, d_in, d_om, d_w_tiled, d_bias, d_out, B, H, W, C, N, split, relu, reinterpret_cast<hipStream_t>(stream));
 }
 
+int pt_op_dwconvt_up_add(pt_engine* e, const uint16_t* d_in, const float* d_w, const uint16_t* d_add, uint16_t* d_out, int B, int h, int w, int C,
+                         int f, int split, pt_stream stream) {
+  PT_REQUIRE(e && d_in && d_w && d_out, "pt_op_dwconvt_up_add: null argument");
+  PT_REQUIRE(B > 0 && h > 0 && w > 0 && C > 0, "pt_op_dwconvt_up_add: empty map (B=%d h=%d w=%d C=%d)", B, h, w, C);
+  return pt_launch_dwconvt_up_add(d_in, d_w, d_add, d_out, B, h, w, C, f, split, reinterpret_cast<hipStream_t>(stream));
+}
+
+int pt_op_dcn_up_add(pt_engine* e, const uint16_t* d_in, const float* d_om, int B, int H, int W, int C, const uint16_t* d_w_tiled,
+                     const float* d_bias, int N, uint16_t* d_out, int relu, int split, const uint16_t* d_up_in, int up_h, int up_w,
+                     const float* d_up_w, int up_f, pt_stream stream) {
+  PT_REQUIRE(e && d_in && d_om && d_w_tiled && d_bias && d_out && d_up_in && d_up_w, "pt_op_dcn_up_add: null argument");
+  PT_REQUIRE(B > 0 && H > 0 && W > 0, "pt_op_dcn_up_add: empty map (B=%d H=%d W=%d)", B, H, W);
+  PT_REQUIRE(split == 0, "pt_op_dcn_up_add: the (hi | lo) modes keep the two launches (pt_op_dcn, pt_op_dwconvt_up_add)");
+  PT_REQUIRE((up_f == 2 || up_f == 4) && up_h > 0 && up_w > 0 && up_h * up_f == H && up_w * up_f == W,
+             "pt_op_dcn_up_add: a %dx%d map times %d is not the %dx%d output", up_h, up_w, up_f, H, W);
+  return pt_launch_dcn_fused(e, d_in, d_om, d_w_tiled, d_bias, d_out, B, H, W, C, N, split, relu, reinterpret_cast<hipStream_t>(stream), nullptr, nullptr,
+                             d_up_in, d_up_w, up_f);
+}
+
 // ---- profiling ---------------------------------------------------------------------------------------
 int pt_profile_enable(pt_engine* e, int on) {
   PT_REQUIRE(e != nullptr, "pt_profile_enable: null engine");

@@ -322,8 +322,14 @@ int pt_launch_det_preprocess(const uint8_t* pages, int n, int h, int w, int nh, 
 // fused modulated deformable 3x3 convolution (lore_kernels.hip): x NHWC bf16, om fp32 [pixel][32], w tiled as a 1x1 conv over K = 9C
 // omw / omb != null (allowed when pt_dcn_fuses_om): the layer's 27-channel offset / mask conv runs in the kernel's prologue from its `.om` weight tiles; om is not read
 int pt_launch_dcn_fused(pt_engine* e, const bf16_t* x, const float* om, const bf16_t* w, const float* bias, bf16_t* out,
-                        int B, int H, int W, int C, int N, int split, int relu, hipStream_t s, const bf16_t* omw = nullptr, const float* omb = nullptr);
+                        int B, int H, int W, int C, int N, int split, int relu, hipStream_t s, const bf16_t* omw = nullptr, const float* omb = nullptr,
+                        const bf16_t* up_in = nullptr, const float* up_w = nullptr, int up_f = 0);
 bool pt_dcn_fuses_om(const pt_engine* e, int C, int split);
+// up_f = 2 | 4 (allowed when pt_dcn_fuses_up): out = up(up_in) + this layer's output, the next IDAUp step's dwconvT up + add in the kernel's epilogue;
+// up_in [B, H / up_f, W / up_f, N], up_w the up-sampler's fp32 [(2 up_f)^2][N] table
+bool pt_dcn_fuses_up(const pt_engine* e, int C, int N, int split);
+int pt_launch_dwconvt_up_add(const bf16_t* in, const float* w, const bf16_t* add, bf16_t* out, int B, int h, int wd, int C, int f, int split,
+                             hipStream_t s);
 int pt_launch_maxpool3x3s2(const bf16_t* in, int B, int H, int W, int C, bf16_t* out, int split, hipStream_t s);
 int pt_launch_stem7x7_pool(pt_engine* e, const bf16_t* in, int B, int H, int W, const bf16_t* w, const float* bias, bf16_t* out,
                            hipStream_t s);   // ResNet-18 stem + MaxPool2d(3,2,1) in one kernel (bf16 mode)

@@ -74,9 +74,10 @@ struct DlaCtx : NetCtx {
     conv(t, q + ".conv2", cout, 3, 1, o, 1, &residual);
     return o;
   }
+  // pooled: MaxPool2d(stride)(x) when the caller already holds it (the outer tree of a two-level stage pools the same x with the same stride)
   T tree(const std::string& q, int levels, const T& x, int cin, int cout, int stride, bool level_root,
-         std::vector<T> children) {
-    T bottom = stride > 1 ? maxpool2(x) : x;
+         std::vector<T> children, const T* pooled = nullptr) {
+    T bottom = stride > 1 ? (pooled ? *pooled : maxpool2(x)) : x;
     if (level_root) children.push_back(bottom);
     if (levels == 1) {
       T residual = bottom;
@@ -92,7 +93,11 @@ struct DlaCtx : NetCtx {
       conv_cat(ins, q + ".root", cout, o, 1);      // Root: conv(cat(x2, x1, *children)) + BN + ReLU, one launch
       return o;
     }
-    T x1 = tree(q + ".tree1", levels - 1, x, cin, cout, stride, false, {});
+    // tree1 has this tree's input and stride: it takes `bottom` for its residual instead of pooling x again (the maximum is exact: same bits).
+    // PT_DLA_POOL_ONCE=0: the second launch (A/B switch, read per call)
+    const char* once_env = getenv("PT_DLA_POOL_ONCE");
+    const bool once = stride > 1 && !(once_env && atoi(once_env) == 0);
+    T x1 = tree(q + ".tree1", levels - 1, x, cin, cout, stride, false, {}, once ? &bottom : nullptr);
     children.push_back(x1);
     return tree(q + ".tree2", levels - 1, x1, cout, cout, 1, false, children);
   }

@@ -558,13 +558,24 @@ __global__ __launch_bounds__(256, (SPLIT || NB > 64) ? 2 : 4) void dcn_fused_ker
 // one 32-pixel row tile against the `.om` weight tiles (32 of their 64 rows: the rest is zero padding) straight from L2, chunk -> tap -> k-step like
 // conv_igemm_kernel<3, 1, 0, NHALF = 1> (same sums in the same order), and the 27 values per pixel land in s_om where the table build reads them.  With
 // eight waves the taps are split between two wave groups and summed through s_om.  SPLIT: K walks (x_hi, w_hi), (x_lo, w_hi), (x_hi, w_lo) over the `.om.w3` tiles.
-template <int NB, int NTHR, int SPLIT = 0, int EARLY = 0, int OMF = 0>
+// UPF = 2 or 4 (bf16 / f16 modes, the IDAUp node layers): the NEXT IDAUp step's `up(p') + node output` runs in this kernel's epilogue instead of as a
+// dwconvt_up*_add_kernel launch that reads the node output back from HBM and writes the sum (lore_model.hip: Ctx::ida).  up_in = p', the next step's
+// projection, [B, H / UPF, W / UPF, N]; up_w = the up-sampler's fp32 [(2 UPF)^2][N] table.  Per stored value: the node output is rounded to the storage
+// format exactly as without UPF, the up-sampler's sum is formed as that kernel forms it (from +0, dy outer, dx inner, product and sum rounded
+// separately -- dcn_up_mad below is compiled outside this kernel's contraction pragma; UPF = 2: terms outside the map are zeroed as in
+// dwconvt_up2_add_kernel<1>, UPF = 4: skipped as in dwconvt_up_add_kernel), the rounded node output is added last and the sum is rounded and
+// stored: the bits of the two launches.  The un-summed node output is not written.
+__device__ __forceinline__ float dcn_up_mad(float acc, float v, float wt) { return acc + v * wt; }
+
+template <int NB, int NTHR, int SPLIT = 0, int EARLY = 0, int OMF = 0, int UPF = 0>
 __global__ __launch_bounds__(NTHR, SPLIT ? (NB == 128 ? 1 : 2) : NTHR / 128) void dcn_fused64_kernel(const bf16_t* __restrict__ x, const float* __restrict__ om,
                                                               const bf16_t* __restrict__ w, const float* __restrict__ bias,
                                                               bf16_t* __restrict__ out, long long npix, int H, int W,
                                                               int C, int N, int relu, const bf16_t* __restrict__ omw = nullptr,
-                                                              const float* __restrict__ omb = nullptr) {
+                                                              const float* __restrict__ omb = nullptr, const bf16_t* __restrict__ up_in = nullptr,
+                                                              const float* __restrict__ up_w = nullptr) {
 #pragma clang fp contract(fast)
+  static_assert(UPF == 0 || ((UPF == 2 || UPF == 4) && !SPLIT), "the up-sampling epilogue exists for factors 2 and 4 of the single-pass modes");
   a16_kernel_enter();
   constexpr int ROW = 144;                      // 64 bf16 + 16 B pad
   constexpr int IT = 1024 / NTHR;               // (pixel, 16-byte piece) items per thread per stage
@@ -609,6 +620,27 @@ __global__ __launch_bounds__(NTHR, SPLIT ? (NB == 128 ? 1 : 2) : NTHR / 128) voi
   const int cs = SPLIT ? 2 * C : C;             // channels per pixel in memory
   const int piece = tid & 7, prow = tid >> 3;   // items: pixels prow + 32 j, j = 0..3, 16-byte piece `piece`
   const char* xmap = reinterpret_cast<const char*>(x + (size_t)img0 * cs);     // wave-uniform: the gathers are scalar base + 32-bit lane offset
+  // UPF: the patch of p' under the tile -- rows ty0 / UPF - 1 .. + 8 / UPF, columns alike, clamped into the map -- is requested NOW and waits in registers
+  // until the operand images are free (its HBM latency hides behind the whole kernel; an epilogue that fetched it per lane waited for it four times over)
+  constexpr int UPH = UPF ? 8 / UPF + 2 : 1, UPW = UPF ? 16 / UPF + 2 : 1;
+  constexpr int UPITCH = NB * 2 + 16, WPITCH = NB + 8;      // LDS pitches: a p' pixel in bytes, a weight tap in floats (conflict-free uint2 / float4 reads)
+  constexpr int UPP = UPF ? (UPH * UPW * (NB / 8) + NTHR - 1) / NTHR : 1;
+  constexpr int UPWT = UPF ? (4 * UPF * UPF * (NB / 4) + NTHR - 1) / NTHR : 1;
+  [[maybe_unused]] u32x4 upreg[UPP];
+  if constexpr (UPF != 0) {
+    static_assert(UPH * UPW * UPITCH <= (int)sizeof(s_ab) && 4 * UPF * UPF * WPITCH * 4 <= (int)sizeof(s_gwt), "the staged patch and table must fit the dead buffers");
+    const int uh = H / UPF, uw = W / UPF;
+    const long long ub = (img0 / ((long long)H * W)) * uh;      // image index * rows of p'
+#pragma unroll
+    for (int j = 0; j < UPP; ++j) {
+      const int i = tid + j * NTHR, pp = i / (NB / 8), pc = i - pp * (NB / 8);
+      const int r = pp / UPW, c = pp - r * UPW;
+      const int iy = min(max(ty0 / UPF - 1 + r, 0), uh - 1), ix = min(max(tx0 / UPF - 1 + c, 0), uw - 1);
+      u32x4 v = {0u, 0u, 0u, 0u};
+      if (i < UPH * UPW * (NB / 8)) v = *reinterpret_cast<const u32x4*>(up_in + (size_t)((ub + iy) * uw + ix) * N + n0 + pc * 8);
+      upreg[j] = v;
+    }
+  }
   if constexpr (OMF) {
     constexpr int HP = 180, HROW = 80;            // halo pixels (10 rows x 18 columns); bytes per staged pixel: 32 channels + 16 B pad (conflict-free ds_read_b128)
     constexpr int HIT = (HP * 4 + NTHR - 1) / NTHR;   // 16-byte halo pieces per thread per chunk
@@ -918,10 +950,52 @@ __global__ __launch_bounds__(NTHR, SPLIT ? (NB == 128 ? 1 : 2) : NTHR / 128) voi
       product();
     }
   }
+  if constexpr (UPF != 0) {
+    // the up-sampler's table (L2-resident: every workgroup reads it) -> the sampling table's space, the patch of p' -> the operand images' space
+    float4 wreg[UPWT];
+#pragma unroll
+    for (int j = 0; j < UPWT; ++j) {
+      const int i = tid + j * NTHR;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (i < 4 * UPF * UPF * (NB / 4)) v = *reinterpret_cast<const float4*>(up_w + (size_t)(i / (NB / 4)) * N + n0 + (i % (NB / 4)) * 4);
+      wreg[j] = v;
+    }
+    __syncthreads();      // the last product has read the operand images
+#pragma unroll
+    for (int j = 0; j < UPP; ++j) {
+      const int i = tid + j * NTHR, pp = i / (NB / 8), pc = i - pp * (NB / 8);
+      if (i < UPH * UPW * (NB / 8)) *reinterpret_cast<u32x4*>(s_ab + pp * UPITCH + pc * 16) = upreg[j];
+    }
+#pragma unroll
+    for (int j = 0; j < UPWT; ++j) {
+      const int i = tid + j * NTHR;
+      if (i < 4 * UPF * UPF * (NB / 4)) *reinterpret_cast<float4*>(reinterpret_cast<float*>(&s_gwt[0][0]) + (i / (NB / 4)) * WPITCH + (i % (NB / 4)) * 4) = wreg[j];
+    }
+    __syncthreads();
+  }
   // weights were the MFMA's A operand: a lane owns pixel mt * 32 + lx, its accumulators are runs of four channels
   int y, xq;
   if (locate(mt * 32 + lx, y, xq)) {
     bf16_t* op = out + (size_t)(img0 + (long long)y * W + xq) * (SPLIT ? 2 * N : N) + n0 + ct0 * 32;
+    // UPF: the (up to) 2 x 2 pixels of p' under this output pixel and their rows of the weight table (dwconvt_up_add_kernel's indices: p = UPF / 2, k = 2 UPF), in LDS
+    [[maybe_unused]] const char* up_p[2][2];
+    [[maybe_unused]] const float* up_t[2][2];
+    [[maybe_unused]] bool up_ok[2][2];
+    if constexpr (UPF != 0) {
+      const int uh = H / UPF, uw = W / UPF;
+      const int iy1 = (y + UPF / 2) / UPF, ix1 = (xq + UPF / 2) / UPF;
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int iy = iy1 - dy, ix = ix1 - dx;
+          const int ky = y + UPF / 2 - iy * UPF, kx = xq + UPF / 2 - ix * UPF;      // 0 .. 2 UPF - 1 for either dy / dx
+          up_ok[dy][dx] = iy >= 0 && iy < uh && ix >= 0 && ix < uw;
+          const int iyc = min(max(iy, 0), uh - 1), ixc = min(max(ix, 0), uw - 1);      // the patch holds the clamped pixel there
+          up_p[dy][dx] = s_ab + ((iyc - (ty0 / UPF - 1)) * UPW + (ixc - (tx0 / UPF - 1))) * UPITCH + ct0 * 64;
+          up_t[dy][dx] = reinterpret_cast<const float*>(&s_gwt[0][0]) + (ky * (2 * UPF) + kx) * WPITCH + ct0 * 32;
+        }
+    }
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
@@ -933,7 +1007,24 @@ __global__ __launch_bounds__(NTHR, SPLIT ? (NB == 128 ? 1 : 2) : NTHR / 128) voi
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
         }
-        const uint32_t h0 = f2bf(v[0]), h1 = f2bf(v[1]), h2 = f2bf(v[2]), h3 = f2bf(v[3]);
+        uint32_t h0 = f2bf(v[0]), h1 = f2bf(v[1]), h2 = f2bf(v[2]), h3 = f2bf(v[3]);
+        if constexpr (UPF != 0) {
+          float us[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+              if (UPF == 4 && !up_ok[dy][dx]) continue;
+              uint2 pv = *reinterpret_cast<const uint2*>(up_p[dy][dx] + ch * 2);
+              if (UPF == 2 && !up_ok[dy][dx]) pv = make_uint2(0u, 0u);
+              const float4 wv = *reinterpret_cast<const float4*>(up_t[dy][dx] + ch);
+              us[0] = dcn_up_mad(us[0], bf2f(pv.x & 0xFFFFu), wv.x);
+              us[1] = dcn_up_mad(us[1], bf2f(pv.x >> 16), wv.y);
+              us[2] = dcn_up_mad(us[2], bf2f(pv.y & 0xFFFFu), wv.z);
+              us[3] = dcn_up_mad(us[3], bf2f(pv.y >> 16), wv.w);
+            }
+          h0 = f2bf(us[0] + bf2f(h0)); h1 = f2bf(us[1] + bf2f(h1)); h2 = f2bf(us[2] + bf2f(h2)); h3 = f2bf(us[3] + bf2f(h3));
+        }
         *reinterpret_cast<uint2*>(op + ch) = make_uint2(h0 | (h1 << 16), h2 | (h3 << 16));
         if (SPLIT)
           *reinterpret_cast<uint2*>(op + N + ch) = make_uint2(f2bf(v[0] - bf2f(h0)) | (f2bf(v[1] - bf2f(h1)) << 16),
@@ -1979,13 +2070,31 @@ bool pt_dcn_fuses_om(const pt_engine* e, int C, int split) {
   return on == 2 || (!split && C <= 128);
 }
 
+// The IDAUp node layers (C = N = 64 or 128, single-pass modes) can take the next step's up-sample + add into their epilogue (dcn_fused64_kernel's UPF) --
+// on the default kernels only: the matrix-pipe variants (pt_engine_set_dcn_mfma), the hi/lo modes and every A/B setting of PT_DCN_* keep the two launches.
+// PT_IDA_FUSE_UP=0: the two launches everywhere (A/B switch, read per call).
+bool pt_dcn_fuses_up(const pt_engine* e, int C, int N, int split) {
+  const char* ev = getenv("PT_IDA_FUSE_UP");
+  if ((ev && atoi(ev) == 0) || !e || split || e->dcn_mfma != 0 || C != N || (N != 64 && N != 128)) return false;
+  for (const char* name : {"PT_DCN_FUSED", "PT_DCN_FUSE_OM", "PT_DCN_THREADS", "PT_DCN_EARLY", "PT_DCN_NB", "PT_DCN_MFMA", "PT_DCN_MFMA_NB", "PT_DCN_X3_FAST"})
+    if (getenv(name)) return false;
+  return true;
+}
+
 int pt_launch_dcn_fused(pt_engine* e, const bf16_t* x, const float* om, const bf16_t* w, const float* bias, bf16_t* out,
-                        int B, int H, int W, int C, int N, int split, int relu, hipStream_t s, const bf16_t* omw, const float* omb) {
+                        int B, int H, int W, int C, int N, int split, int relu, hipStream_t s, const bf16_t* omw, const float* omb,
+                        const bf16_t* up_in, const float* up_w, int up_f) {
   PT_REQUIRE(e && x && (om || (omw && omb)) && w && bias && out && C % 32 == 0 && N % 64 == 0, "dcn fused: bad arguments (C=%d N=%d)", C, N);      // e: every path below reads it
   PT_REQUIRE(!omw || pt_dcn_fuses_om(e, C, split), "dcn fused: the offset conv can only be fused on the default fused64 paths (C=%d)", C);
   PT_REQUIRE((long long)H * W * (split ? 2 * C : C) < (1ll << 31), "dcn fused: image too large for 32-bit offsets");
-  // algorithmic bytes: input map once, offsets / masks once, output once, weights once (the 36 corner lines per pixel are cache traffic)
-  const double dcn_bytes = (double)B * H * W * ((split ? 2.0 : 1.0) * 2.0 * (C + N) + 27 * 4.0) + (double)N * 9 * C * 2.0 * (split ? 3 : 1);
+  if (up_f) {
+    PT_REQUIRE(up_in && up_w && (up_f == 2 || (up_f == 4 && N == 64)) && H % up_f == 0 && W % up_f == 0,
+               "dcn fused + up: factor %d must be 2 (or 4 at 64 channels) and divide the %dx%d map", up_f, H, W);
+    PT_REQUIRE(pt_dcn_fuses_up(e, C, N, split), "dcn fused + up: only the default single-pass kernels at C = N = 64 or 128 carry the up-sampling epilogue (C=%d N=%d split=%d)", C, N, split);
+  }
+  // algorithmic bytes: input map once, offsets / masks once, output once, weights once (the 36 corner lines per pixel are cache traffic); + p' once
+  const double dcn_bytes = (double)B * H * W * ((split ? 2.0 : 1.0) * 2.0 * (C + N) + 27 * 4.0) + (double)N * 9 * C * 2.0 * (split ? 3 : 1) +
+                           (up_f ? (double)B * (H / up_f) * (W / up_f) * N * 2.0 : 0.0);
   e->prof.next_bytes = dcn_bytes;
   // (the hi/lo mode keeps 64-channel blocks: with 128 the corner registers of both halves spill)
   static int x3fast = -1;        // PT_DCN_X3_FAST=0: the hi/lo mode on dcn_fused_kernel<1, 64> (A/B switch)
@@ -2016,7 +2125,7 @@ int pt_launch_dcn_fused(pt_engine* e, const bf16_t* x, const float* om, const bf
   if (C % 64 == 0) {
     const long long npix = (long long)B * H * W;
     char label[48];
-    snprintf(label, sizeof(label), "dcn fused %d->%d @%dx%d", C, N, H, W);
+    snprintf(label, sizeof(label), "dcn fused%s %d->%d @%dx%d", up_f ? "+up" : "", C, N, H, W);
     PtProfScope prof(e, s, PT_PROF_OTHER, 0, label);   // gather-bound, kept out of the implicit-GEMM class
     // N >= 128: one workgroup computes 128 output channels from one gather + blend (the expensive half of the kernel)
     // instead of two workgroups repeating it for 64 each (PT_DCN_NB=64: the 64-wide blocks everywhere)
@@ -2041,6 +2150,18 @@ int pt_launch_dcn_fused(pt_engine* e, const bf16_t* x, const float* om, const bf
       mfma_nb = nv ? atoi(nv) : 128;
     }
     const int mfma = e->dcn_mfma;
+    if (up_f) {      // pt_dcn_fuses_up: no PT_DCN_* setting is in force -- the default kernel of either width, with the epilogue
+      const unsigned blk = N == 128 ? 256 : 512;
+#define PT_DCN_UP(NB_, NT_, EARLY_, OMF_, UPF_)                                                                                                   \
+  hipLaunchKernelGGL((dcn_fused64_kernel<NB_, NT_, 0, EARLY_, OMF_, UPF_>), dim3(tiles, N / NB_), dim3(blk), 0, s, x, om, w, bias, out, npix, H, W, C, N, relu, \
+                     omw, omb, up_in, up_w)
+      if (N == 128) { if (omw) PT_DCN_UP(128, 256, 0, 1, 2); else PT_DCN_UP(128, 256, 0, 0, 2); }
+      else if (up_f == 2) { if (omw) PT_DCN_UP(64, 512, 1, 1, 2); else PT_DCN_UP(64, 512, 1, 0, 2); }
+      else { if (omw) PT_DCN_UP(64, 512, 1, 1, 4); else PT_DCN_UP(64, 512, 1, 0, 4); }
+#undef PT_DCN_UP
+      PT_HIP_CHECK(hipGetLastError());
+      return PT_OK;
+    }
     if (mfma == 2 && N == 64) {      // full-line gathers, one workgroup per CU (dcn_mfma2_kernel); wider layers keep dcn_fused64_kernel in this setting
       static bool attr2 = false;
       if (!attr2) {

@@ -17,14 +17,16 @@ namespace PT_FMT_NS {
 
 int pt_launch_dcn_im2col(const bf16_t* x, const float* om, bf16_t* cols, int B, int H, int W, int C, int split,
                          hipStream_t s);
-int pt_launch_dwconvt_up_add(const bf16_t* in, const float* w, const bf16_t* add, bf16_t* out, int B, int h, int wd,
-                             int C, int f, int split, hipStream_t s);
-
 namespace {
 
 struct Ctx : DlaCtx {
-  // DeformConv (lore_dla_34.py:65-83)
-  T dcn(const std::string& q, const T& x, int cout) {
+  struct UpTail {      // the next IDAUp step's `up(p) + this output`, run in a node DCN's epilogue (dcn_fused64_kernel's UPF): f = 0: none
+    T p;
+    const PtTensor* w = nullptr;
+    int f = 0;
+  };
+  // DeformConv (lore_dla_34.py:65-83); up: out = up(up->p) + DeformConv(x)
+  T dcn(const std::string& q, const T& x, int cout, const UpTail* up = nullptr) {
     T o = alloc(x.H, x.W, cout);
     static const bool fused = !(getenv("PT_DCN_FUSED") && atoi(getenv("PT_DCN_FUSED")) == 0);
     // the 27-channel offset / mask conv: inside the deformable conv's kernel where that kernel can (dcn_fused64_kernel<..., OMF = 1>: no launch, no fp32 map
@@ -37,7 +39,8 @@ struct Ctx : DlaCtx {
       const PtTensor* ow = om_inside ? get(q + (x3 ? ".om.w3" : ".om.w")) : nullptr;
       const PtTensor* ob = om_inside ? get(q + ".om.b") : nullptr;
       if (go()) {
-        const int r = pt_launch_dcn_fused(e, x.p, om, W(w), F(b), o.p, n, x.H, x.W, x.C, cout, x3, 1, s, ow ? W(ow) : nullptr, ob ? F(ob) : nullptr);
+        const int r = pt_launch_dcn_fused(e, x.p, om, W(w), F(b), o.p, n, x.H, x.W, x.C, cout, x3, 1, s, ow ? W(ow) : nullptr, ob ? F(ob) : nullptr,
+                                          up ? up->p.p : nullptr, up ? F(up->w) : nullptr, up ? up->f : 0);
         if (r != PT_OK) rc = r;
       }
       return o;
@@ -53,24 +56,49 @@ struct Ctx : DlaCtx {
     conv(c, q + ".dcn", cout, 1, 1, o, 1);
     return o;
   }
-  // IDAUp.forward (lore_dla_34.py:106-112) on layers[startp .. endp)
-  void ida(const std::string& q, std::vector<T>& layers, int startp, int endp, int o_ch, const int* up_f) {
+  // IDAUp.forward (lore_dla_34.py:106-112) on layers[startp .. endp).
+  // Where the node DCN can (pt_dcn_fuses_up), step j + 1's `up(proj) + node_j output` runs in node_j's epilogue: proj_{j+1} -- it reads layers[i + 1] only --
+  // is issued before node_j, and the `dw convT up + add` launch remains for the first step alone, whose skip is somebody else's output.
+  // A fused node never writes its own output, only the sum: `own_nodes` says that nobody but the next step reads the node outputs below the last --
+  // true for ida_2 and ida_up; ida_0 / ida_1 leave theirs in `layers`, where the next IDAUp projects them (DLAUp.forward :128-134).
+  // tail: what the LAST node adds in the same way (ida_2's last node forms ida_up's first sum); first_sum: that sum, received (the first step then
+  // launches neither its proj nor its up-sampler: the caller has)
+  void ida(const std::string& q, std::vector<T>& layers, int startp, int endp, int o_ch, const int* up_f, bool own_nodes = false,
+           const UpTail* tail = nullptr, const T* first_sum = nullptr) {
+    const bool fuse = own_nodes && pt_dcn_fuses_up(e, o_ch, o_ch, x3);
+    T p, u;
+    bool have_p = false, have_u = false;
+    if (first_sum) { u = *first_sum; have_p = have_u = true; }
     for (int i = startp + 1; i < endp; ++i) {
       const int j = i - startp;
       const std::string js = std::to_string(j);
-      T p = dcn(q + ".proj_" + js, layers[i], o_ch);
-      const int f = up_f[j];
-      T u = alloc(p.H * f, p.W * f, o_ch);
-      const PtTensor* wu = get(q + ".up_" + js + ".wf32");
-      if (go()) {
-        e->prof.next_bytes = (double)n * p.H * p.W * o_ch * 2.0 * mul * (1.0 + 2.0 * f * f);      // in once, skip + out at f x f the pixels
-        char label[48];
-        snprintf(label, sizeof(label), "dw convT up + add %d @%dx%d", o_ch, p.H * f, p.W * f);
-        PtProfScope ps(e, s, PT_PROF_OTHER, 0, label);
-        const int r = pt_launch_dwconvt_up_add(p.p, F(wu), layers[i - 1].p, u.p, n, p.H, p.W, o_ch, f, x3, s);
-        if (r != PT_OK) rc = r;
+      if (!have_p) p = dcn(q + ".proj_" + js, layers[i], o_ch);
+      if (!have_u) {
+        const int f = up_f[j];
+        u = alloc(p.H * f, p.W * f, o_ch);
+        const PtTensor* wu = get(q + ".up_" + js + ".wf32");
+        if (go()) {
+          e->prof.next_bytes = (double)n * p.H * p.W * o_ch * 2.0 * mul * (1.0 + 2.0 * f * f);      // in once, skip + out at f x f the pixels
+          char label[48];
+          snprintf(label, sizeof(label), "dw convT up + add %d @%dx%d", o_ch, p.H * f, p.W * f);
+          PtProfScope ps(e, s, PT_PROF_OTHER, 0, label);
+          const int r = pt_launch_dwconvt_up_add(p.p, F(wu), layers[i - 1].p, u.p, n, p.H, p.W, o_ch, f, x3, s);
+          if (r != PT_OK) rc = r;
+        }
       }
-      layers[i] = dcn(q + ".node_" + js, u, o_ch);
+      have_p = have_u = false;
+      UpTail nx;
+      if (fuse && i + 1 < endp) {
+        const std::string ns = std::to_string(j + 1);
+        p = nx.p = dcn(q + ".proj_" + ns, layers[i + 1], o_ch);
+        nx.w = get(q + ".up_" + ns + ".wf32");
+        nx.f = up_f[j + 1];
+        have_p = true;
+      } else if (fuse && tail) {
+        nx = *tail;
+      }
+      layers[i] = dcn(q + ".node_" + js, u, o_ch, nx.f ? &nx : nullptr);
+      if (nx.f) { u = layers[i]; have_u = true; }      // the next step's sum, already
     }
   }
 };
@@ -114,12 +142,20 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
     out.insert(out.begin(), layers[5]);
     c.ida("dla_up.ida_1", layers, 3, 6, 128, f2);
     out.insert(out.begin(), layers[5]);
-    c.ida("dla_up.ida_2", layers, 2, 6, 64, f2);
+    // ida_up's first sum up_1(proj_1(out[1])) + out[0] has ida_2's last node as its skip: proj_1 reads ida_1's result, so it can run before ida_2,
+    // whose last node then adds its up-sampled map in the epilogue
+    const int f24[3] = {1, 2, 4};
+    Ctx::UpTail t2;
+    if (pt_dcn_fuses_up(e, 64, 64, c.x3)) {
+      t2.p = c.dcn("ida_up.proj_1", out[0], 64);
+      t2.w = c.get("ida_up.up_1.wf32");
+      t2.f = f24[1];
+    }
+    c.ida("dla_up.ida_2", layers, 2, 6, 64, f2, true, t2.f ? &t2 : nullptr);
     out.insert(out.begin(), layers[5]);
     // ida_up on clones of out[0..3) (strides 4, 8, 16): up factors 2 and 4
     std::vector<T> y = {out[0], out[1], out[2]};
-    const int f24[3] = {1, 2, 4};
-    c.ida("ida_up", y, 0, 3, 64, f24);
+    c.ida("ida_up", y, 0, 3, 64, f24, true, nullptr, t2.f ? &y[0] : nullptr);
     const T feat = y[2];
     T hid = c.alloc(feat.H, feat.W, 256);
     // only `hm` is needed everywhere: the other five heads run on patch mosaics (lore_decode.hip)

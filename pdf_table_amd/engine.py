@@ -767,6 +767,41 @@ class HipEngine:
                                    self._stream()), "pt_op_dcn")
         return out
 
+    def op_dwconvt_up_add(self, x: torch.Tensor, w_taps: torch.Tensor, add: Optional[torch.Tensor], f: int, split: int = 0) -> torch.Tensor:
+        """IDAUp's up-sampler (pt_op_dwconvt_up_add): depthwise ConvTranspose2d(C, C, 2f, stride f, padding f/2) of x [B,h,w,C] (+ add [B,hf,wf,C]);
+        w_taps fp32 [(2f)^2, C]."""
+        self._chk(x, self.act_dtype, "x")
+        self._chk(w_taps, torch.float32, "w_taps")
+        B, h, w, Cc = x.shape
+        if add is not None:
+            self._chk(add, self.act_dtype, "add")
+            if tuple(add.shape) != (B, h * f, w * f, Cc):
+                raise ValueError(f"op_dwconvt_up_add: add must be {(B, h * f, w * f, Cc)}, got {tuple(add.shape)}")
+        out = torch.empty((B, h * f, w * f, Cc), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_dwconvt_up_add(self._h, _ptr(x), _ptr(w_taps), _ptr(add), _ptr(out), B, h, w, Cc // 2 if split else Cc, int(f),
+                                              int(split), self._stream()), "pt_op_dwconvt_up_add")
+        return out
+
+    def op_dcn_up_add(self, x: torch.Tensor, om: torch.Tensor, w_tiled: torch.Tensor, bias: torch.Tensor, up_in: torch.Tensor, up_taps: torch.Tensor,
+                      f: int, relu: bool = True, split: int = 0) -> torch.Tensor:
+        """op_dcn followed by op_dwconvt_up_add(up_in, up_taps, add=that output, f) as one launch (pt_op_dcn_up_add), bit for bit."""
+        self._chk(x, self.act_dtype, "x")
+        self._chk(om, torch.float32, "om")
+        self._chk(bias, torch.float32, "bias")
+        self._chk(up_in, self.act_dtype, "up_in")
+        self._chk(up_taps, torch.float32, "up_taps")
+        B, H, W, Cc = x.shape
+        if tuple(om.shape) != (B, H, W, 32):
+            raise ValueError(f"op_dcn_up_add: om must be [B,H,W,32], got {tuple(om.shape)}")
+        N = bias.numel()
+        if up_in.dim() != 4 or up_in.shape[0] != B or up_in.shape[3] != N:
+            raise ValueError(f"op_dcn_up_add: up_in must be [{B},h,w,{N}], got {tuple(up_in.shape)}")
+        out = torch.empty((B, H, W, N), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_dcn_up_add(self._h, _ptr(x), _ptr(om), B, H, W, Cc // 2 if split else Cc, _ptr(w_tiled), _ptr(bias), N, _ptr(out), int(relu),
+                                          int(split), _ptr(up_in), up_in.shape[1], up_in.shape[2], _ptr(up_taps), int(f), self._stream()),
+                "pt_op_dcn_up_add")
+        return out
+
     # ---- single operators of the generic ONNX executor (pdf_table_amd/onnx_exec.py); bf16 NHWC, C a multiple of 8 -------
     # (split=True: the tolerance mode's (hi | lo) tensors -- the last dimension holds [hi(C) | lo(C)], C = shape[-1] // 2)
     def op_dwconv(self, x: torch.Tensor, w_taps: torch.Tensor, bias: torch.Tensor, k: int, stride: int = 1, act: int = 0, split: bool = False) -> torch.Tensor:
