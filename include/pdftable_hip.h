@@ -519,6 +519,28 @@ int pt_op_softmax(pt_engine* e, const uint16_t* d_in, long long rows, int c_pad,
 int pt_op_attention(pt_engine* e, const uint16_t* d_qkv, int B, int T, int heads, int d, int qkv_cstride, float scale, uint16_t* d_out, int out_cstride,
                     int split, pt_stream stream);
 
+/* The ConvNextViT recogniser's kernels one at a time (csrc/cvit_model.hip; since ABI 19): the launches of pt_rec_cvit_forward_net on caller-owned
+ * buffers, for op-level tests.  The engine handle and the stream only: no model is loaded.  No allocation, no host synchronisation.  16-bit tensors
+ * are in the engine's storage format; split: (hi | lo) rows as everywhere (PT_PRECISION_BF16X3).
+ * pt_op_cvit_mlp: d_x [rows, C] fp32 += W2 GELU(W1 xb + b1) + b2 in place (cvit_mlp_kernel).  d_xb 16-bit [rows, C]; d_w1 [4C, C]; d_w2p
+ *   [4C / 32][C][32] (weights.py::pack_cvit_mlp); d_b1 fp32 [4C], d_b2 fp32 [C].  C is 96, 192 or 256, rows >= 1 (exactly `rows` rows are read and
+ *   written, nothing is padded).  Single-pass modes only: the (hi | lo) modes run two GEMMs instead and get PT_ERR_INVALID here.
+ * pt_op_cvit_attention: d_qkv [nchunks * 75, 576] = [q | k | v] of 3 heads x 64 (q already scaled) -> d_out [nchunks * 75, 192]; every chunk of 75
+ *   tokens attends to itself only.  split: rows [hi 576 | lo 576] -> [hi 192 | lo 192].
+ * pt_op_cvit_dwconv_ln: depthwise 7x7 (padding 3) + bias + LayerNorm(C, eps 1e-6) of d_x fp32 [B, H, W, C] -> 16-bit [B, H, W, C] ([hi C | lo C]
+ *   when split).  d_w49 fp32 [49][C] (tap-major).  H is 1, 2, 4 or 8, C <= 512, W >= 1; the LayerNorm tile of (8 H C + 16 H) floats must fit 64 KB of LDS.
+ * pt_op_cvit_ln: LayerNorm (d_g == d_beta == NULL: conversion only) of fp32 rows [.., C], C <= 512 -> 16-bit.  mode 0: row to row.  mode 1: rows
+ *   (b, y, x) of [B, H, W] maps, H even, to row (b, y / 2, x) of 2C channels at channel offset (y & 1) C; `rows` = B H W.  mode 2: `rows` OUTPUT rows
+ *   (line, pos) of 201-token lines gathered from 75-token chunks: pos < 69 token pos of chunk 0, pos < 132 token pos - 63 of chunk 1, else token
+ *   pos - 126 of chunk 2; chunk j of a line is chunk d_cmap[3 line + j] of d_x (d_cmap NULL: 3 line + j).  H, W are read in mode 1 only. */
+int pt_op_cvit_mlp(pt_engine* e, const uint16_t* d_xb, long long rows, int C, const uint16_t* d_w1, const float* d_b1, const uint16_t* d_w2p,
+                   const float* d_b2, float* d_x, pt_stream stream);
+int pt_op_cvit_attention(pt_engine* e, const uint16_t* d_qkv, int nchunks, uint16_t* d_out, int split, pt_stream stream);
+int pt_op_cvit_dwconv_ln(pt_engine* e, const float* d_x, int B, int H, int W, int C, const float* d_w49, const float* d_bias, const float* d_g,
+                         const float* d_beta, uint16_t* d_out, int split, pt_stream stream);
+int pt_op_cvit_ln(pt_engine* e, const float* d_x, long long rows, int C, const float* d_g, const float* d_beta, float eps, uint16_t* d_out, int split,
+                  int mode, int H, int W, const int32_t* d_cmap, pt_stream stream);
+
 /* ONNX LSTM layer, the recurrence (csrc/lstm_op.hip; since ABI 17).  Hidden size H <= 128; Hp = H rounded up to 16.  The input projection is the
  * caller's: d_pregates [B T rows][pg_cstride] (row b T + t) = X W^T + Wb + Rb from pt_op_conv2d, channel d 4 Hp + gate Hp + unit with the gates in
  * ONNX order i, o, f, c and zeros in the padded units.  d_r_packed: the recurrent weights R [dirs, 4H, H] in MFMA operand order

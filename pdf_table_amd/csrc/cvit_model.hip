@@ -388,8 +388,8 @@ __global__ __launch_bounds__(64) void cvit_attention_kernel(const bf16_t* __rest
 //   An MFMA here reads 1 KB of LDS (the weight fragment; the row operand is in registers): LDS and matrix pipe are balanced,
 //   neither HBM (10 C bytes per row instead of 26 C) nor the launch count (one kernel instead of two) is the bound.
 //   Epilogue: the lane's 4-channel fp32 runs of its row are added to the residual stream in place.
-// GELU: a packed-fp32 polynomial (gelu_pair below, absolute error < 3e-6) -- the hidden value is rounded to bf16 right after,
-// 2^-9 relative.  The hi/lo mode keeps the two-GEMM path with erff.
+// GELU: a packed-fp32 polynomial (gelu_pair below: within a quarter of the bf16 half-ulp of the erf form) -- the hidden value is
+// rounded to bf16 right after, 2^-9 relative.  The hi/lo mode keeps the two-GEMM path with erff.
 // ---------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(4))) uint32_t cu32x4;
 
@@ -397,10 +397,19 @@ typedef __attribute__((ext_vector_type(2))) float mlp_f2;
 typedef __attribute__((ext_vector_type(2))) __bf16 mlp_b2;
 
 // GELU of two values at once in packed fp32 (v_pk_fma_f32): x * Phi(x) with Phi(x) - 1/2 = x * Q(x^2), Q the degree-9 polynomial
-// of a Chebyshev fit on [-4, 4] (|error of Phi| < 8e-7 there); outside, x is clamped in Phi (Phi(4) = 1 - 3.2e-5) and, on the
-// negative side, in the product too (GELU(x < -4) = -1.3e-4 instead of -> 0).  Absolute error < 3e-6 on [-4, 4], relative error
-// < 5e-4 wherever |GELU| > 1e-3 -- the value is rounded to bf16 (2^-9) right after.  14 packed instructions per pair against
-// ~34 per value for the erf form (exp, reciprocal, unfused multiply-adds under -ffp-contract=off): the kernel is VALU-bound here.
+// of a Chebyshev fit on [-4, 4]; outside, x is clamped in Phi (Phi(4) = 1 - 3.2e-5) and, on the negative side, in the product
+// too (GELU(x < -4) = -1.3e-4 instead of -> 0).  The value is rounded to bf16 (2^-9) right after, so the CONTRACT is what that
+// rounding cannot see, a quarter of the bf16 half-ulp, against 0.5 x (1 + erf(x / sqrt 2)) in fp64 (asserted on the kernel's own
+// output by tests/test_gpu_cvit_ops.py::test_gelu_probe, on these coefficients by tests/test_cvit_ops_host.py):
+//   [-4, 4], |GELU| >= 2^-6: relative error <= 2^-11        [-4, 4] elsewhere: absolute error <= 2^-15
+//   x > 4: relative error <= 2^-11                           x < -4: absolute error <= 2^-12
+// MEASURED (these ten coefficients, fp32 fused multiply-adds, 2.4 M points of [-12, 12]): |error of Phi| 4.9e-6 and absolute error
+// 2.0e-5 on [-4, 4], both largest at +-4 (4.5e-6 absolute for |x| <= 3.6); relative error 1.2e-4 where |GELU| >= 2^-6 but 3.7e-3
+// near x = -3.3, where |GELU| is about 1.5e-3; x > 4: 3.5e-5 relative; x < -4: 1.4e-4 absolute.  The GPU probe reads the STORED
+// value, so its maxima carry the store's half-ulp on top (absolute on [-4, 4] / relative where |GELU| >= 2^-6 / absolute for x < -4 /
+// relative for x > 4): f16 9.9e-4 / 5.8e-4 / 1.39e-4 / 5.2e-4, bf16 7.8e-3 / 4.0e-3 / 1.39e-4 / 2.0e-3; at most 0.64 (f16) and 0.90
+// (bf16) of u |GELU| + contract.  14 packed instructions per pair against ~34 per value for the erf form (exp, reciprocal, unfused
+// multiply-adds under -ffp-contract=off): the kernel is VALU-bound here.
 __device__ __forceinline__ mlp_f2 gelu_pair(mlp_f2 x) {
   const mlp_f2 xp = __builtin_elementwise_max(x, (mlp_f2){-4.f, -4.f});
   const mlp_f2 xc = __builtin_elementwise_min(xp, (mlp_f2){4.f, 4.f});
@@ -591,6 +600,38 @@ int launch_mlp(const bf16_t* xb, const bf16_t* w1, const float* b1, const bf16_t
   return PT_OK;
 }
 
+// the fused MLP at one of its three widths (the instantiations forward_batch runs); any other C: PT_ERR_INVALID
+int launch_mlp_c(int C, const bf16_t* xb, const bf16_t* w1, const float* b1, const bf16_t* w2p, const float* b2, float* x, long long rows, hipStream_t s) {
+  // 128-row workgroups (NW = 4), two per CU; 256-row ones (NW = 8, one per CU, half the weight DMA per row) measured equal at
+  // C = 256 and 5-10 % slower at C = 96 / 192
+  if (C == 96) return launch_mlp<96, true, 4>(xb, w1, b1, w2p, b2, x, rows, s);
+  if (C == 192) return launch_mlp<192, true, 4>(xb, w1, b1, w2p, b2, x, rows, s);
+  if (C == 256) return launch_mlp<256, false, 4>(xb, w1, b1, w2p, b2, x, rows, s);
+  pt_set_error("cvit fused mlp: C = %d (96, 192 or 256)", C);
+  return PT_ERR_INVALID;
+}
+
+void launch_attention(const bf16_t* qkv, int nchunks, bf16_t* out, int split, hipStream_t s) {
+  if (split) hipLaunchKernelGGL(cvit_attention_kernel<1>, dim3(3, 3, nchunks), dim3(64), 0, s, qkv, out);
+  else hipLaunchKernelGGL(cvit_attention_kernel<0>, dim3(3, 3, nchunks), dim3(64), 0, s, qkv, out);
+}
+
+// H in {1, 2, 4, 8}
+void launch_dwconv_ln(const float* x, int B, int H, int W, int C, const float* w, const float* b, const float* g, const float* be, bf16_t* out, int split,
+                      hipStream_t s) {
+  const dim3 grid((W + CV_TX - 1) / CV_TX, B), block((C + 63) / 64 * 64);
+  const size_t lds = ((size_t)H * CV_TX * C + 2 * H * CV_TX) * sizeof(float);
+  if (H == 8) hipLaunchKernelGGL(cvit_dwconv_ln_kernel<8>, grid, block, lds, s, x, W, C, w, b, g, be, out, split);
+  else if (H == 4) hipLaunchKernelGGL(cvit_dwconv_ln_kernel<4>, grid, block, lds, s, x, W, C, w, b, g, be, out, split);
+  else if (H == 2) hipLaunchKernelGGL(cvit_dwconv_ln_kernel<2>, grid, block, lds, s, x, W, C, w, b, g, be, out, split);
+  else hipLaunchKernelGGL(cvit_dwconv_ln_kernel<1>, grid, block, lds, s, x, W, C, w, b, g, be, out, split);
+}
+
+void launch_ln(const float* x, long long rows, int C, const float* g, const float* be, float eps, bf16_t* out, int split, int mode, int H, int W,
+               const int* cmap, hipStream_t s) {
+  hipLaunchKernelGGL(cvit_ln_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, C, g, be, eps, out, split, mode, H, W, cmap);
+}
+
 struct Net : NetCtx {
   const float* f32(const std::string& n) {
     const PtTensor* t = get(n);
@@ -630,13 +671,7 @@ void mlp(Net& p, const bf16_t* xb, bf16_t* hb, float* x, long long rows_pad, int
     const float *b1 = p.f32(q + "." + n1 + ".b"), *b2 = p.f32(q + "." + n2 + ".b");
     if (p.rc != PT_OK) return;
     PtProfScope ps(p.e, p.s, PT_PROF_CONV1X1, 16.0 * rows_pad * (double)C * C, "cvit fused mlp");
-    const bf16_t *W1 = W(w1), *W2 = W(w2);
-    // 128-row workgroups (NW = 4), two per CU; 256-row ones (NW = 8, one per CU, half the weight DMA per row) measured equal at
-    // C = 256 and 5-10 % slower at C = 96 / 192
-    int r;
-    if (C == 96) r = launch_mlp<96, true, 4>(xb, W1, b1, W2, b2, x, rows_pad, p.s);
-    else if (C == 192) r = launch_mlp<192, true, 4>(xb, W1, b1, W2, b2, x, rows_pad, p.s);
-    else r = launch_mlp<256, false, 4>(xb, W1, b1, W2, b2, x, rows_pad, p.s);
+    const int r = launch_mlp_c(C, xb, W(w1), b1, W(w2), b2, x, rows_pad, p.s);
     if (r != PT_OK) p.rc = r;
     return;
   }
@@ -740,7 +775,7 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
     const float* be = q.empty() ? nullptr : p.f32(q + ".b");
     if (p.rc != PT_OK) return;
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "cvit layernorm");
-    hipLaunchKernelGGL(cvit_ln_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, rows, C, g, be, eps, out, x3, mode, H, W, d_cmap);
+    launch_ln(x, rows, C, g, be, eps, out, x3, mode, H, W, d_cmap, s);
   };
   int H = 8;
   for (int st = 0; st < 4; ++st) {
@@ -759,12 +794,7 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
       if (p.rc != PT_OK) return p.rc;
       {
         PtProfScope ps(e, s, PT_PROF_OTHER, 0, "cvit dwconv7+ln");
-        const dim3 grid((CV_T + CV_TX - 1) / CV_TX, nchunks), block((C + 63) / 64 * 64);
-        const size_t lds = ((size_t)H * CV_TX * C + 2 * H * CV_TX) * sizeof(float);
-        if (H == 8) hipLaunchKernelGGL(cvit_dwconv_ln_kernel<8>, grid, block, lds, s, x, CV_T, C, w, b, g, be, xb, x3);
-        else if (H == 4) hipLaunchKernelGGL(cvit_dwconv_ln_kernel<4>, grid, block, lds, s, x, CV_T, C, w, b, g, be, xb, x3);
-        else if (H == 2) hipLaunchKernelGGL(cvit_dwconv_ln_kernel<2>, grid, block, lds, s, x, CV_T, C, w, b, g, be, xb, x3);
-        else hipLaunchKernelGGL(cvit_dwconv_ln_kernel<1>, grid, block, lds, s, x, CV_T, C, w, b, g, be, xb, x3);
+        launch_dwconv_ln(x, nchunks, H, CV_T, C, w, b, g, be, xb, x3, s);
       }
       mlp(p, xb, hb, x, rp, C, lq, "pw1", "pw2");
       if (p.rc != PT_OK) return p.rc;
@@ -787,8 +817,7 @@ int forward_batch(pt_engine* e, const PtModel& M, const float* gray, int pitch, 
     if (p.rc != PT_OK) return p.rc;
     {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "cvit attention");
-      if (x3) hipLaunchKernelGGL(cvit_attention_kernel<1>, dim3(3, 3, nchunks), dim3(64), 0, s, qkv, att);
-      else hipLaunchKernelGGL(cvit_attention_kernel<0>, dim3(3, 3, nchunks), dim3(64), 0, s, qkv, att);
+      launch_attention(qkv, nchunks, att, x3, s);
     }
     p.gemm(att, Tp, 192, lq + ".out", 192, 0, nullptr, x, 192, x);
     ln(lq + ".ln2", T, 192, 1e-12f, xb, 0, 1, 1);
@@ -853,5 +882,56 @@ int pt_cvit_forward_net(pt_engine* e, const float* gray, int layout, int n, int3
   }
   return PT_OK;
 }
+
+// ---- the kernels above one at a time (tests/test_gpu_cvit_ops.py): engine handle and stream only, no model loaded, the launch helpers of
+// forward_batch.  No allocation and no host synchronisation.
+namespace api {
+
+int pt_op_cvit_mlp(pt_engine* e, const uint16_t* d_xb, long long rows, int C, const uint16_t* d_w1, const float* d_b1, const uint16_t* d_w2p,
+                   const float* d_b2, float* d_x, pt_stream stream) {
+  PT_REQUIRE(e && d_xb && d_w1 && d_b1 && d_w2p && d_b2 && d_x, "pt_op_cvit_mlp: null argument");
+  PT_REQUIRE(!pt_split(e), "pt_op_cvit_mlp: the fused MLP kernel runs in the single-pass modes only (the (hi | lo) modes keep the two GEMMs)");
+  PT_REQUIRE(C == 96 || C == 192 || C == 256, "pt_op_cvit_mlp: C = %d (96, 192 or 256)", C);
+  PT_REQUIRE(rows >= 1 && rows < (1ll << 31), "pt_op_cvit_mlp: rows = %lld", rows);
+  PT_REQUIRE((((uintptr_t)d_xb | (uintptr_t)d_w1 | (uintptr_t)d_w2p | (uintptr_t)d_b2 | (uintptr_t)d_x) & 15) == 0, "pt_op_cvit_mlp: unaligned pointer");
+  return launch_mlp_c(C, d_xb, d_w1, d_b1, d_w2p, d_b2, d_x, rows, reinterpret_cast<hipStream_t>(stream));
+}
+
+int pt_op_cvit_attention(pt_engine* e, const uint16_t* d_qkv, int nchunks, uint16_t* d_out, int split, pt_stream stream) {
+  PT_REQUIRE(e && d_qkv && d_out, "pt_op_cvit_attention: null argument");
+  PT_REQUIRE(nchunks >= 1 && nchunks <= 65535, "pt_op_cvit_attention: nchunks = %d (1 .. 65535: the grid's z extent)", nchunks);
+  PT_REQUIRE(((uintptr_t)d_qkv & 15) == 0, "pt_op_cvit_attention: unaligned pointer");
+  launch_attention(d_qkv, nchunks, d_out, split ? 1 : 0, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_cvit_dwconv_ln(pt_engine* e, const float* d_x, int B, int H, int W, int C, const float* d_w49, const float* d_bias, const float* d_g,
+                         const float* d_beta, uint16_t* d_out, int split, pt_stream stream) {
+  PT_REQUIRE(e && d_x && d_w49 && d_bias && d_g && d_beta && d_out, "pt_op_cvit_dwconv_ln: null argument");
+  PT_REQUIRE(H == 1 || H == 2 || H == 4 || H == 8, "pt_op_cvit_dwconv_ln: H = %d (1, 2, 4 or 8: a workgroup owns every row of its columns)", H);
+  PT_REQUIRE(C >= 1 && C <= 512 && W >= 1 && B >= 1 && B <= 65535, "pt_op_cvit_dwconv_ln: B=%d W=%d C=%d (C <= 512, B <= 65535)", B, W, C);
+  PT_REQUIRE(((size_t)H * CV_TX * C + 2 * H * CV_TX) * sizeof(float) <= 65536,
+             "pt_op_cvit_dwconv_ln: H=%d C=%d: the LayerNorm tile of %d x 8 pixels exceeds 64 KB of LDS", H, C, H);
+  launch_dwconv_ln(d_x, B, H, W, C, d_w49, d_bias, d_g, d_beta, d_out, split ? 1 : 0, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_cvit_ln(pt_engine* e, const float* d_x, long long rows, int C, const float* d_g, const float* d_beta, float eps, uint16_t* d_out, int split,
+                  int mode, int H, int W, const int32_t* d_cmap, pt_stream stream) {
+  PT_REQUIRE(e && d_x && d_out, "pt_op_cvit_ln: null argument");
+  PT_REQUIRE((d_g == nullptr) == (d_beta == nullptr), "pt_op_cvit_ln: gamma and beta go together (both null: conversion only)");
+  PT_REQUIRE(C >= 1 && C <= 512 && rows >= 1 && rows < (1ll << 33), "pt_op_cvit_ln: rows=%lld C=%d (C <= 512)", rows, C);
+  PT_REQUIRE(mode >= 0 && mode <= 2, "pt_op_cvit_ln: mode = %d (0 rows, 1 down-sampler row pairs, 2 chunk stitching)", mode);
+  PT_REQUIRE(mode != 1 || (H >= 2 && H % 2 == 0 && W >= 1 && rows % ((long long)H * W) == 0),
+             "pt_op_cvit_ln: mode 1 pairs rows 2y and 2y + 1 of [B, H, W] maps: H = %d must be even, rows = %lld whole maps of W = %d", H, rows, W);
+  PT_REQUIRE(mode == 2 || !d_cmap, "pt_op_cvit_ln: a chunk map belongs to mode 2");
+  launch_ln(d_x, rows, C, d_g, d_beta, eps, d_out, split ? 1 : 0, mode, H, W, d_cmap, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+}  // namespace api
 
 }  // namespace PT_FMT_NS

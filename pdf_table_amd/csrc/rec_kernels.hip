@@ -1547,7 +1547,7 @@ __global__ __launch_bounds__(256) void argmax_reduce_kernel(const float2* __rest
 // MODE 1: the same streaming GEMM with a store epilogue instead (out bf16 [M][N] = A . W^T + bias, optional ReLU): a lane
 // writes its row's classes as 8-byte runs of four (the LSTM input projections and embeddings of the CRNN head).
 // GELU for the bf16 mode's row GEMM (ConvNextViT stage 3, cvit_model.hip): x * Phi(x), Phi - 1/2 = x * Q(x^2) with the degree-9
-// Q of a Chebyshev fit on [-4, 4] (the polynomial of cvit_model.hip's gelu_pair; |error| < 3e-6, clamped outside) -- the value
+// Q of a Chebyshev fit on [-4, 4] (the polynomial of cvit_model.hip's gelu_pair, error contract and measured figures there; clamped outside) -- the value
 // is rounded to bf16 right after
 __device__ __forceinline__ float gelu_poly(float x) {
   const float xp = fmaxf(x, -4.f), xc = fminf(xp, 4.f), t = xc * xc;

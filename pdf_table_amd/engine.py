@@ -1012,6 +1012,59 @@ class HipEngine:
                                          self._stream()), "pt_op_attention")
         return out
 
+    # ---- the ConvNextViT recogniser's kernels one at a time (csrc/cvit_model.hip; no model loaded) ---------------------
+    def op_cvit_mlp(self, xb: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2p: torch.Tensor, b2: torch.Tensor, x: torch.Tensor,
+                    rows: Optional[int] = None) -> torch.Tensor:
+        """x [>= rows, C] fp32 += W2 GELU(W1 xb + b1) + b2 IN PLACE over the first `rows` rows (default: all of xb's); w1 / w2p: the 16-bit
+        patterns of weights.pack_cvit_mlp on the device (any 2-byte dtype)."""
+        self._chk(xb, self.act_dtype, "xb")
+        for t, n in ((b1, "b1"), (b2, "b2"), (x, "x")):
+            self._chk(t, torch.float32, n)
+        Cc = xb.shape[-1]
+        rows = xb.shape[0] if rows is None else int(rows)
+        if (w1.element_size() != 2 or w2p.element_size() != 2 or w1.numel() != 4 * Cc * Cc or w2p.numel() != 4 * Cc * Cc or not w1.is_contiguous()
+                or not w2p.is_contiguous() or b1.numel() != 4 * Cc or b2.numel() != Cc or x.shape[-1] != Cc or rows > min(xb.shape[0], x.shape[0])):
+            raise ValueError(f"op_cvit_mlp: operands do not fit C = {Cc}, rows = {rows}")
+        L.check(self.lib.pt_op_cvit_mlp(self._h, _ptr(xb), rows, Cc, _ptr(w1), _ptr(b1), _ptr(w2p), _ptr(b2), _ptr(x), self._stream()), "pt_op_cvit_mlp")
+        return x
+
+    def op_cvit_attention(self, qkv: torch.Tensor, split: bool = False) -> torch.Tensor:
+        """qkv [nchunks * 75, 576] rows of [q | k | v], 3 heads of 64, q already scaled -> [nchunks * 75, 192]; split: [hi | lo] rows of twice the width"""
+        self._chk(qkv, self.act_dtype, "qkv")
+        m = 2 if split else 1
+        if qkv.dim() != 2 or qkv.shape[1] != 576 * m or qkv.shape[0] % 75:
+            raise ValueError(f"op_cvit_attention: qkv must be [nchunks * 75, {576 * m}], got {tuple(qkv.shape)}")
+        out = torch.zeros((qkv.shape[0], 192 * m), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_cvit_attention(self._h, _ptr(qkv), qkv.shape[0] // 75, _ptr(out), int(split), self._stream()), "pt_op_cvit_attention")
+        return out
+
+    def op_cvit_dwconv_ln(self, x: torch.Tensor, w49: torch.Tensor, bias: torch.Tensor, g: torch.Tensor, beta: torch.Tensor, split: bool = False) -> torch.Tensor:
+        """depthwise 7x7 (padding 3) + LayerNorm(C, 1e-6) of the fp32 map x [B, H, W, C] -> 16-bit [B, H, W, C] ([hi | lo] when split); w49 [49, C]"""
+        for t, n in ((x, "x"), (w49, "w49"), (bias, "bias"), (g, "g"), (beta, "beta")):
+            self._chk(t, torch.float32, n)
+        B, H, W, Cc = x.shape
+        if tuple(w49.shape) != (49, Cc) or bias.numel() != Cc or g.numel() != Cc or beta.numel() != Cc:
+            raise ValueError(f"op_cvit_dwconv_ln: parameters do not fit C = {Cc}")
+        out = torch.zeros((B, H, W, Cc * (2 if split else 1)), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_cvit_dwconv_ln(self._h, _ptr(x), B, H, W, Cc, _ptr(w49), _ptr(bias), _ptr(g), _ptr(beta), _ptr(out), int(split),
+                                              self._stream()), "pt_op_cvit_dwconv_ln")
+        return out
+
+    def op_cvit_ln(self, x: torch.Tensor, out: torch.Tensor, rows: int, g: Optional[torch.Tensor], beta: Optional[torch.Tensor], eps: float, mode: int = 0,
+                   H: int = 1, W: int = 1, cmap: Optional[torch.Tensor] = None, split: bool = False) -> torch.Tensor:
+        """cvit_ln_kernel over `rows` rows (mode 2: OUTPUT rows) of the fp32 rows x [.., C] into the caller's `out` (the caller sizes it for the mode:
+        pt_op_cvit_ln in include/pdftable_hip.h); g = beta = None: conversion only; cmap: int32 device tensor (mode 2)"""
+        self._chk(x, torch.float32, "x")
+        self._chk(out, self.act_dtype, "out")
+        for t, n in ((g, "g"), (beta, "beta")):
+            if t is not None:
+                self._chk(t, torch.float32, n)
+        if cmap is not None:
+            self._chk(cmap, torch.int32, "cmap")
+        L.check(self.lib.pt_op_cvit_ln(self._h, _ptr(x), int(rows), x.shape[-1], _ptr(g), _ptr(beta), float(eps), _ptr(out), int(split), int(mode), int(H),
+                                       int(W), _ptr(cmap), self._stream()), "pt_op_cvit_ln")
+        return out
+
     def op_lstm(self, pregates: torch.Tensor, r_packed: torch.Tensor, hidden: int, dirs: int, reverse: bool, out_c: int, split: bool = False) -> torch.Tensor:
         """The recurrence of an ONNX LSTM layer (pt_op_lstm; hidden <= 128, zero initial states).  pregates [B, 1, T, dirs * 4 * Hp] (x m halves
         when split) = X W^T + Wb + Rb, gates i, o, f, c per direction; r_packed: weights.pack_lstm_r(R) on the device -> token rows

@@ -29,7 +29,7 @@ import torch
 BN_EPS = 1e-5
 _DT = {"bf16": 0, "f32": 1, "i32": 2}
 
-__all__ = ["pack_db_resnet18", "pack_crnn", "pack_lore_dla34", "pack_centernet_dla34", "pack_lore_processor", "pack_picodet", "pack_lore_wireless", "pack_db_nas", "pack_pplcnet", "pack_convnext_vit", "pack_mtl_backbone", "pack_mtl_decoder", "write_blob", "fold_conv_bn", "to_bf16_bits"]
+__all__ = ["pack_db_resnet18", "pack_crnn", "pack_lore_dla34", "pack_centernet_dla34", "pack_lore_processor", "pack_picodet", "pack_lore_wireless", "pack_db_nas", "pack_pplcnet", "pack_convnext_vit", "pack_cvit_mlp", "pack_mtl_backbone", "pack_mtl_decoder", "write_blob", "fold_conv_bn", "to_bf16_bits"]
 
 
 FORMATS = {"bf16": torch.bfloat16, "f16": torch.float16}      # 16-bit storage formats of the engine (csrc/act16.h): PT_PRECISION_BF16* / PT_PRECISION_F16
@@ -791,6 +791,24 @@ _CVIT_V5_TO_V4 = [
 ]
 
 
+def cvit_mlp_slot_units() -> np.ndarray:
+    """hidden unit (within its 32-unit chunk) held by K slot (s2, half, j) of a W2 chunk for cvit_mlp_kernel: int64 [2, 2, 8]"""
+    s2, half, j = np.meshgrid(np.arange(2), np.arange(2), np.arange(8), indexing="ij")
+    return (j & 3) + 8 * (2 * s2 + (j >> 2)) + 4 * half
+
+
+def pack_cvit_mlp(w1: torch.Tensor, w2: torch.Tensor, fmt: str = "bf16") -> Tuple[np.ndarray, np.ndarray]:
+    """Weights of the fused MLP kernel (cvit_mlp_kernel, single-pass modes, C <= 256) as 16-bit patterns: W1 [4C, C] rows as they are (a 32-unit
+    chunk is contiguous); W2 [C, 4C] with the K order of every 32-unit chunk permuted to the MFMA accumulator layout the hidden values are
+    produced in -- slot (s2, half, j) of chunk hc holds hidden unit hc * 32 + (j & 3) + 8 * (2 * s2 + (j >> 2)) + 4 * half -- stored
+    [chunk][C][32]."""
+    c = w1.shape[1]
+    assert tuple(w1.shape) == (4 * c, c) and tuple(w2.shape) == (c, 4 * c) and c % 32 == 0, (tuple(w1.shape), tuple(w2.shape))
+    perm = torch.from_numpy(cvit_mlp_slot_units().reshape(-1))
+    w2c = w2.reshape(c, 4 * c // 32, 32)[:, :, perm].permute(1, 0, 2).contiguous()          # [chunk][C][32]
+    return to_bf16_bits(w1, fmt), to_bf16_bits(w2c, fmt)
+
+
 def pack_convnext_vit(sd: Dict[str, torch.Tensor], x3: bool = True, fmt: str = "bf16") -> bytes:
     """``ConvNextViT`` state_dict -> blob for PT_MODEL_CONVNEXT_VIT.  Key names of the reference's checkpoint era
     (transformers 4.x, ``vitstr.vit.encoder.layer.N.attention.attention.query`` ...) or of transformers 5.x
@@ -824,20 +842,12 @@ def pack_convnext_vit(sd: Dict[str, torch.Tensor], x3: bool = True, fmt: str = "
         n_to = n_to or w.shape[0]
         bl.add_conv(name, *_pad_conv(w.reshape(w.shape[0], w.shape[1], 1, 1), b, n_to, w.shape[1]))
 
-    # the fused MLP kernel (cvit_mlp_kernel, bf16 mode, C <= 256): W1 rows as they are ([4C][C]: a 32-unit chunk is
-    # contiguous); W2 [C][4C] with the K order of every 32-unit chunk permuted to the MFMA accumulator layout the hidden
-    # values are produced in: slot (s2, half, j) of chunk hc holds hidden unit hc * 32 + (j & 3) + 8 * (2 * s2 + (j >> 2)) +
-    # 4 * half; stored [chunk][C][32]
-    s2_, half_, j_ = np.meshgrid(np.arange(2), np.arange(2), np.arange(8), indexing="ij")
-    perm = torch.from_numpy(((j_ & 3) + 8 * (2 * s2_ + (j_ >> 2)) + 4 * half_).reshape(-1))
-
     def mlp(name, w1, w2):
-        c = w1.shape[1]
-        if c > 256:
+        if w1.shape[1] > 256:
             return
-        bl.add(name + ".mlp.w1", bl.bits(w1), "bf16")
-        w2c = w2.reshape(c, 4 * c // 32, 32)[:, :, perm].permute(1, 0, 2).contiguous()          # [chunk][C][32]
-        bl.add(name + ".mlp.w2p", bl.bits(w2c), "bf16")
+        w1b, w2pb = pack_cvit_mlp(w1, w2, bl.fmt)
+        bl.add(name + ".mlp.w1", w1b, "bf16")
+        bl.add(name + ".mlp.w2p", w2pb, "bf16")
 
     p = "cnn_model."
     f32("embed.w", sd[p + "embeddings.patch_embeddings.weight"].reshape(96, 16))
