@@ -574,6 +574,18 @@ int pt_op_dwconv_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, i
 int pt_op_pool_rect(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C, int kind, int kh, int kw, uint16_t* d_out, int split,
                     pt_stream stream);
 
+/* Dense convolutions with a kernel side of 5, 7 or 9 (csrc/large_conv.hip; added under ABI 19: one new entry point, no existing signature changed,
+ * so the version stays): the LKPAN neck of the PP-OCRv4 server detector.  kh, kw each 1, 3, 5, 7 or 9, independently, at least one of them >= 5;
+ * stride 1, no dilation, zero padding k / 2 per axis, so the output is [B, H, W, N].  Operands as pt_op_conv2d_rect: Cin a multiple of 32, N of 64;
+ * d_w_tiled [N/64][Cin/32][kh kw][64][32] (weights.tile_conv_weight; the three K sections of tile_conv_weight_x3 when split), d_bias fp32 [N]; fp32
+ * accumulate, bias, act 0 none / 1 ReLU / 2 hardswish, one rounding on store into channels [out_coff, out_coff + N) of pixels out_cstride wide (the
+ * lo half out_lo_off further when split; all three multiples of 4).  Padding reads as zero and never reaches into the neighbouring image; maps
+ * smaller than the kernel are a first-class case.  No residual operand.  No allocation and no host synchronisation (capturable), except that the
+ * first call with a given kw on a device may raise that kernel's LDS limit (a host-side setting): made inside a stream capture it returns
+ * PT_ERR_STATE, so call once before capturing. */
+int pt_op_conv2d_large(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Cin, const uint16_t* d_w_tiled, const float* d_bias, int N, int kh,
+                       int kw, uint16_t* d_out, int out_cstride, int out_coff, int act, int split, int out_lo_off, pt_stream stream);
+
 /* PP-OCRv4 mobile detector blocks (csrc/det_ops.hip; added under ABI 18: two new entry points, no existing signature changed, so the version stays).  No allocation and no host synchronisation (capturable).
  * pt_op_affine_act: y = s2[c] act(s1[c] x + b1[c]) + b2[c] over npix pixels of Cpad channels (a multiple of 8), 16-bit NHWC in the engine's storage
  * format; act 0 none / 1 ReLU / 2 hardswish; the four vectors are fp32 [Cpad]; channels C .. Cpad of the output are written as zeros whatever the

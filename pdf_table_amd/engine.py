@@ -862,6 +862,27 @@ class HipEngine:
                                            out_coff, int(act), int(split), out.shape[-1] // 2, self._stream()), "pt_op_conv2d_rect")
         return out
 
+    def op_conv2d_large(self, x: torch.Tensor, w_tiled: torch.Tensor, bias: torch.Tensor, kh: int, kw: int, act: int = 0,
+                        out: Optional[torch.Tensor] = None, out_coff: int = 0, split: int = 0) -> torch.Tensor:
+        """Dense stride-1 convolution with kh, kw in {1, 3, 5, 7, 9}, at least one of them >= 5, padding k // 2 per axis (csrc/large_conv.hip: the
+        9x9 / 7x7 / 5x5 / 7x1 / 1x7 / 5x1 / 1x5 layers of the PP-OCRv4 server detector's neck).  Operands, act, out / out_coff and split as
+        op_conv2d_rect."""
+        self._chk(x, self.act_dtype, "x")
+        self._chk(bias, torch.float32, "bias")
+        B, H, W, Cin = x.shape
+        m = 2 if split else 1
+        Cin //= m
+        N = bias.numel()
+        if out is None:
+            out = torch.empty((B, H, W, N * m), dtype=self.act_dtype, device=self._tdev)
+        else:
+            self._chk(out, self.act_dtype, "out")
+            if tuple(out.shape[:3]) != (B, H, W):
+                raise ValueError(f"op_conv2d_large: out must be [{B},{H},{W},C], got {tuple(out.shape)}")
+        L.check(self.lib.pt_op_conv2d_large(self._h, _ptr(x), B, H, W, Cin, _ptr(w_tiled), _ptr(bias), N, kh, kw, _ptr(out), out.shape[-1],
+                                            out_coff, int(act), int(split), out.shape[-1] // 2, self._stream()), "pt_op_conv2d_large")
+        return out
+
     def op_dwconv_rect(self, x: torch.Tensor, w_taps: torch.Tensor, bias: torch.Tensor, k: int, sh: int, sw: int, act: int = 0, split: bool = False) -> torch.Tensor:
         """depthwise k x k (3 / 5, pad k // 2) with a stride per axis; operands as op_dwconv"""
         self._chk(x, self.act_dtype, "x")

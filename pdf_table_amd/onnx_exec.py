@@ -29,7 +29,8 @@ Anything else raises.
 
 There is no CPU path: an operator outside this set raises ``UnsupportedOnnxGraph`` naming it (oracle/onnx_ref.py executes
 graphs on the CPU for the tests only).  Supported today: Conv (groups 1: kernels of 1 / 3 per axis -- 1x1, 3x3, 1x3, 3x1; depthwise: 3x3 / 5x5;
-stride 1 / 2 chosen per axis -- (2,1) and (1,2) included; padding k // 2 per axis), ConvTranspose 2x2 / stride 2, BatchNormalization (folded),
+stride 1 / 2 chosen per axis -- (2,1) and (1,2) included; group 1 at stride 1 on feature maps of more than 4 channels also kernels of 5 / 7 / 9 per axis -- 9x9, 7x7, 5x5, 7x1, 1x7, 5x1, 1x5:
+``pt_op_conv2d_large``, csrc/large_conv.hip; padding k // 2 per axis), ConvTranspose 2x2 / stride 2, BatchNormalization (folded),
 Relu / HardSwish / Sigmoid / HardSigmoid / Relu6, a BatchNormalization that stands alone, Add, Mul by a per-channel gate, Mul / Add / Sub / Div of a feature
 map with a constant scalar or [C, 1, 1] / [1, C, 1, 1] vector (x - c and x / c included; folded into the neighbouring convolution where that is exact, chains
 collapsed; c - x and c / x are refused), MaxPool(3, 2, 1),
@@ -341,7 +342,7 @@ class HipGraphExecutor:
         sh, sw = a["strides"]
         rect = self._is_rect(lay)
         if a["dilations"] != [1, 1] or sh not in (1, 2) or sw not in (1, 2):
-            raise UnsupportedOnnxGraph(f"{lay.name}: conv {a} (no dilation; stride 1 / 2 per axis; dense kernels of 1 / 3 per axis, depthwise 3x3 / 5x5)")
+            raise UnsupportedOnnxGraph(f"{lay.name}: conv {a} (no dilation; stride 1 / 2 per axis; dense kernels of 1 / 3 per axis at either stride and of 5 / 7 / 9 per axis at stride 1, depthwise 3x3 / 5x5)")
         if list(a["pads"]) != [kh // 2, kw // 2, kh // 2, kw // 2]:
             raise UnsupportedOnnxGraph(f"{lay.name}: conv padding {a['pads']} of a {kh}x{kw} kernel is not k // 2 on every side of each axis")
         fused = _ACT_CODE.get(lay.act, None) if lay.act in _ACT_CODE else 0
@@ -369,7 +370,28 @@ class HipGraphExecutor:
             x4 = self._zeros(x.t.shape[:-1], 4)           # NHWC4 image ([hi rgb0 | lo rgb0] in the tolerance mode)
             self._copy(x.t, x4, 3)
             return _Act(self.eng.op_stem7x7(x4, d["w"], d["b"], split=self.split), d["n"])
-        if a["group"] == 1 and rect:
+        if a["group"] == 1 and max(kh, kw) >= 5:
+            # a kernel side of 5 or more (the LKPAN neck of the PP-OCRv4 server detector: 9x9, and 7x7 / 7x1 / 1x7 / 5x5 / 5x1 / 1x5 in its IntraCL
+            # blocks): pt_op_conv2d_large, stride 1 only; same tiles as the other dense paths, with kh kw taps
+            if kh > 9 or kw > 9 or kh % 2 == 0 or kw % 2 == 0:
+                raise UnsupportedOnnxGraph(f"{lay.name}: dense {kh}x{kw} convolution (the large-kernel MFMA path covers odd sides up to 9: each of kh, kw "
+                                           "is 1, 3, 5, 7 or 9)")
+            if sh != 1 or sw != 1:
+                raise UnsupportedOnnxGraph(f"{lay.name}: dense {kh}x{kw} convolution with strides {a['strides']} (a kernel side of 5 or more is built at "
+                                           "stride 1 only; the 7x7 / stride-2 stem on a 3-channel image has its own kernel)")
+            if x.c <= 4:
+                # a large kernel straight on the image (an RGB / RGBA stem): the GEMM's K chunk is 32 channels, so at least 28 of every 32 products
+                # would be zeros, and the refusal of such stems is what callers have seen so far; image stems keep their own kernels
+                raise UnsupportedOnnxGraph(f"{lay.name}: dense {kh}x{kw} convolution on a {x.c}-channel image (the large-kernel MFMA path is built for "
+                                           "feature maps of more than 4 channels; the 7x7 / stride-2 stem has its own kernel)")
+            d = self._conv_operands(k, lay, self._cp(x), x.c)
+            y = _Act(self.eng.op_conv2d_large(x.t, d["w"], d["b"], kh, kw, act=fused if res is None else 0, split=int(self.split)), d["n"])
+            if res is not None:
+                # that kernel has no residual operand: conv -> pt_op_add -> the activation behind the Add, as the unfused layers run
+                y = _Act(self.eng.op_add(y.t, res.t, split=self.split), y.c)
+                if res_act:
+                    y = _Act(self.eng.op_act(y.t, res_act, 0.0, 0.0, split=self.split), y.c)
+        elif a["group"] == 1 and rect:
             # per-axis stride or a 1x3 / 3x1 kernel (the down-sampling blocks and the neck of a text-line recogniser): pt_op_conv2d_rect computes
             # only the kept outputs and multiplies only the existing taps; same tiles as the square path, with kh kw taps
             if kh not in (1, 3) or kw not in (1, 3):
@@ -402,7 +424,7 @@ class HipGraphExecutor:
             else:
                 y = _Act(self.eng.op_dwconv(x.t, d["w"], d["b"], kh, sh, fused, split=self.split), x.c)
         else:
-            raise UnsupportedOnnxGraph(f"{lay.name}: grouped convolution (group {a['group']} of {x.c} channels)")
+            raise UnsupportedOnnxGraph(f"{lay.name}: grouped {kh}x{kw} convolution (group {a['group']} of {x.c} channels; built: group 1 and depthwise)")
         return self._post_act(lay, y, post)
 
     @staticmethod
