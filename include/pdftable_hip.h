@@ -456,6 +456,18 @@ int pt_op_dcn_up_add(pt_engine* e, const uint16_t* d_in, const float* d_om, int 
                      const float* d_bias, int N, uint16_t* d_out, int relu, int split, const uint16_t* d_up_in, int up_h, int up_w,
                      const float* d_up_w, int up_f, pt_stream stream);
 
+/* Lore's heat-map head on a feature map d_in [B,H,W,64]: hm.0 (3x3 64 -> 256 + ReLU; d_w1_tiled [4][2][9][64][32], d_b1 fp32 [256]) and hm.2
+ * (1x1 256 -> 2 padded to 64 GEMM columns; d_w2_tiled [1][8][1][64][32] with rows 2 .. 63 zero, d_b2 fp32 [64]).  Single-pass modes only.
+ *   fused == 0: the two launches.  d_hid [B,H,W,256] receives the hidden map, d_logits fp32 [B,H,W,8] the 1x1 launch's eight stored channels.
+ *   fused == 1: one launch, the hidden map stays on chip (d_hid unused).  d_logits (may be NULL) as above: channels 0, 1 sum the same 256 exact
+ *               products in another fp32 order, channels 2 .. 7 are equal bits; d_sig (may be NULL) fp32 [B,H,W,2] = the sigmoid of the logits as the
+ *               decode's peak test reads it.  PT_ERR_INVALID when the fused head is switched off (PT_LORE_HM_FUSE=0).
+ *   d_sig_ref (may be NULL) fp32 [B,H,W,2]: the decode's own sigmoid launch run on d_logits afterwards.
+ * Added under ABI 19 (no existing signature changed). */
+int pt_op_lore_hm_head(pt_engine* e, const uint16_t* d_in, int B, int H, int W, const uint16_t* d_w1_tiled, const float* d_b1,
+                       const uint16_t* d_w2_tiled, const float* d_b2, int fused, uint16_t* d_hid, float* d_logits, float* d_sig, float* d_sig_ref,
+                       pt_stream stream);
+
 /* Stem of the ResNet-18 backbone: 7x7 s2 p3 conv (BN folded) + ReLU on a bf16 NHWC4 image (dbnet.py:272-275).
  * d_w is bf16 [64][7][8][4] (K padded: tap s=7 and channel 3 are zero), d_bias fp32 [64]; out bf16 [B,H/2,W/2,64]. */
 int pt_op_stem7x7(pt_engine* e, const uint16_t* d_in, int B, int H, int W, const uint16_t* d_w, const float* d_bias,

@@ -18,7 +18,7 @@ extern "C" {
 
 const char* pt_last_error(void) { return g_err; }
 
-// 19: pt_op_cvit_mlp / attention / dwconv_ln / ln (the ConvNextViT recogniser's kernels one at a time, for the op-level tests);
+// 19: pt_op_cvit_mlp / attention / dwconv_ln / ln (the ConvNextViT recogniser's kernels one at a time, for the op-level tests); also pt_op_lore_hm_head (added);
 // 18 also: pt_op_dwconvt_up_add / pt_op_dcn_up_add (IDAUp up-sampler alone and in the deformable conv's epilogue), added without a change of any existing signature;
 // 15: pt_page_line_mask / line_angles / warp_cubic / quarter_turn / pre_tables (image-page straightening); 14: PT_PRECISION_F16 (every kernel instantiated for IEEE-half storage; blobs carry their format); 13: pt_engine_set_dcn_mfma; 12: pt_op_dcn (the fused
 // modulated deformable convolution as a single operator); 11: pt_engine_set_mtl_kv_fp8; 10: pt_tsr_mtl_preprocess / decoder_config / structure / cells

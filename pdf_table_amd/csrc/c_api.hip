@@ -1038,6 +1038,34 @@ int pt_op_dcn_up_add(pt_engine* e, const uint16_t* d_in, const float* d_om, int 
                              d_up_in, d_up_w, up_f);
 }
 
+int pt_op_lore_hm_head(pt_engine* e, const uint16_t* d_in, int B, int H, int W, const uint16_t* d_w1_tiled, const float* d_b1, const uint16_t* d_w2_tiled,
+                       const float* d_b2, int fused, uint16_t* d_hid, float* d_logits, float* d_sig, float* d_sig_ref, pt_stream stream) {
+  PT_REQUIRE(e && d_in && d_w1_tiled && d_b1 && d_w2_tiled && d_b2, "pt_op_lore_hm_head: null argument");
+  PT_REQUIRE(B > 0 && H > 0 && W > 0, "pt_op_lore_hm_head: empty map (B=%d H=%d W=%d)", B, H, W);
+  PT_REQUIRE(!pt_split(e), "pt_op_lore_hm_head: single-pass modes only");
+  PT_REQUIRE(d_logits || (fused && d_sig), "pt_op_lore_hm_head: no output");
+  PT_REQUIRE(!d_sig_ref || d_logits, "pt_op_lore_hm_head: d_sig_ref is computed from d_logits");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  ConvDesc d;
+  d.in = d_in; d.B = B; d.H = H; d.W = W; d.Cin = 64; d.w = d_w1_tiled; d.bias = d_b1; d.N = 256; d.ks = 3; d.stride = 1; d.relu = 1;
+  int rc;
+  if (fused) {
+    PT_REQUIRE(pt_conv_fuses_hm(e), "pt_op_lore_hm_head: the fused head is switched off (PT_LORE_HM_FUSE / PT_CONV_PIPE / PT_CONV_DMA / PT_CONV_VARIANT)");
+    d.hm_w2 = d_w2_tiled; d.hm_b2 = d_b2; d.hm_logits = d_logits; d.hm_sig = d_sig;
+    if ((rc = pt_launch_conv(e, d, s)) != PT_OK) return rc;
+  } else {
+    PT_REQUIRE(d_hid && d_logits && !d_sig, "pt_op_lore_hm_head: the two launches write d_hid and d_logits (scores: d_sig_ref)");
+    d.out = d_hid; d.out_cstride = 256;
+    if ((rc = pt_launch_conv(e, d, s)) != PT_OK) return rc;
+    ConvDesc d2;      // hm.2 as lore_dla_run launches it
+    d2.in = d_hid; d2.B = B; d2.H = H; d2.W = W; d2.Cin = 256; d2.w = d_w2_tiled; d2.bias = d_b2; d2.N = 64; d2.ks = 1; d2.stride = 1;
+    d2.n_valid = 8; d2.out_f32 = d_logits; d2.out_cstride = 8; d2.alg_n = 2;
+    if ((rc = pt_launch_conv(e, d2, s)) != PT_OK) return rc;
+  }
+  if (d_sig_ref) return pt_launch_heat_sigmoid(d_logits, d_sig_ref, (long long)B * H * W, s);
+  return PT_OK;
+}
+
 // ---- profiling ---------------------------------------------------------------------------------------
 int pt_profile_enable(pt_engine* e, int on) {
   PT_REQUIRE(e != nullptr, "pt_profile_enable: null engine");

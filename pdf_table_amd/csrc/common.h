@@ -302,8 +302,18 @@ struct ConvDesc {
   int xp_store = 0;
   int alg_n = 0;
   double alg_scale = 1.0;
+  // fused heat-map head (allowed when pt_conv_fuses_hm): this 3x3 64 -> 256 + ReLU layer is the hidden layer of a 1x1 256 -> 2 layer that runs in its
+  // epilogue; the hidden map is not stored (`out` unused).  hm_w2: that layer's 16-bit tiles [1][8][1][64][32], rows 2 .. 63 zero padding; hm_b2: its
+  // fp32 bias [64]; hm_logits: fp32 [pixel][8] as the 1x1 launch with n_valid = 8 writes it; hm_sig: fp32 [pixel][2] = pt_heat_sigmoid(logit), the
+  // score map of pt_heat_peaks_topk.  Either output may be null, not both.
+  const bf16_t* hm_w2 = nullptr;
+  const float* hm_b2 = nullptr;
+  float* hm_logits = nullptr;
+  float* hm_sig = nullptr;
 };
 int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s);
+// single-pass storage and the default kernel family (no PT_CONV_PIPE below 4); PT_LORE_HM_FUSE=0 (A/B switch, read per call): the two launches
+bool pt_conv_fuses_hm(const pt_engine* e);
 // CRNN conv0 + pool + conv1 + pool in one launch (conv_igemm.hip: crnn_conv01_kernel), single-pass modes
 int pt_launch_crnn_conv01(pt_engine* e, const bf16_t* gray, int n, const float* w64x9, const float* b0, const bf16_t* w1, const float* b1, bf16_t* p1,
                           const int* xlimit, const int* xlimit_cols, hipStream_t s);
@@ -458,7 +468,15 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
                     int use_2dpe, float* d_logic, float* d_stacked, hipStream_t s);
 int pt_lore_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* hm, float* st, float* wh, float* ax,
                         float* cr, float* reg, hipStream_t s);
+// the score of a heat-map logit: ONE definition for lore_sigmoid_kernel and for the conv epilogue that writes the score map itself
+// (conv3x3_pipe_persist_hm_kernel), so that the same logit gives the same bits in both
+__device__ __forceinline__ float pt_heat_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+// lore_sigmoid_kernel alone: hm fp32 [npix][8] -> sig fp32 [npix][2]
+int pt_launch_heat_sigmoid(const float* hm, float* sig, long long npix, hipStream_t s);
+// where pt_lore_decode_peaks(hm = nullptr) expects the score map [B][H][W][2] of its next call with the same (B, H, W) on this engine
+int pt_lore_decode_sig_map(pt_engine* e, int B, int H, int W, float** d_sig);
 constexpr int PT_HEAT_CAP = 16384;      // peak candidates per (table, class) list of pt_heat_peaks_topk
+// hm == nullptr: `sig` already holds the scores (no sigmoid launch)
 int pt_heat_peaks_topk(const float* hm, int B, int H, int W, float thr0, float thr1, int k0, int k1, float* sig, unsigned long long* keys,
                        int* cnt, unsigned long long* sorted, int* kept, hipStream_t s);
 int pt_centernet_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* hm, float* v2c, float* c2v, float* reg, hipStream_t s);

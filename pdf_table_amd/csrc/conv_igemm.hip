@@ -51,6 +51,9 @@ struct ConvK {
   // fused DB head (dbnet.py:537-539): this conv is ConvTranspose2d(64,64,2,2)+BN+ReLU as a pixel-shuffle GEMM and
   // the epilogue applies the last ConvTranspose2d(64->1,2,2) + Sigmoid on the rounded activations, so the
   // 64-channel 1/2-resolution tensor never goes to HBM.  head_w: [4][64] bf16 (fp32 in split mode).
+  // The same four fields carry Lore's fused heat-map head (conv3x3_pipe_persist_hm_kernel, ConvDesc.hm_w2): this layer's 256 outputs feed a 1x1
+  // 256 -> 2 layer in the epilogue and are not stored.  head_w: that layer's 16-bit tiles [1][8][1][64][32] (rows 0 and 1 are read), head_b: its fp32
+  // bias [>= 8], head_logits: fp32 [pixel][8] (may be null; channels 2 .. 7 = 0 + head_b[c]), head_prob: fp32 [pixel][2] scores (may be null).
   const void* head_w;
   const float* head_b;
   float* head_prob;
@@ -1544,13 +1547,32 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_kernel(ConvK p, cons
 // fragments are read behind it, and the epilogue of tile i (registers -> global, nothing staged) runs while that slice is already in LDS.
 // Per tile the per-lane DMA offsets are eight integer operations per slot from the slot's (row, column, half) in the patch, kept packed in a register.
 // Same tiles, same K order, same epilogue: every output bit equals conv3x3_pipe_kernel's (tests/test_gpu_det.py).
+//
+// HM (conv3x3_pipe_persist_hm_kernel: Lore's heat-map head, hm.0 3x3 64 -> 256 + ReLU followed by hm.2 1x1 256 -> 2): the 256-channel hidden map is
+// consumed where it is made and never stored.  The epilogue forms each hidden value as epilogue_direct_row stores it (bias, ReLU, rounding to the 16-bit
+// format -- saturating in the half format --, widened back to fp32) and multiplies it into two fp32 partial sums per pixel with the 1x1 layer's weights
+// (16-bit values widened to fp32: every product is exact).  Order of the sum, fixed: a lane's 32 channels in register order; the two q lanes of a pixel
+// by one v_permlane32_swap (lane q then holds output q); the tile's 128-channel half 0 + half 1 (the two halves of a pixel tile are consecutive tiles of
+// the same workgroup: runs are cut in pixel tiles, the half-0 sum waits in four registers); the wave pair's 64-channel halves wn = 0 + wn = 1 through
+// LDS; + bias.  One store per pixel and output, no atomics.  The layer's bias and the 1x1 weights are read from LDS (3 KB behind the two slice buffers,
+// filled once per workgroup): broadcast reads, no per-lane global load in the epilogue.
 // ---------------------------------------------------------------------------------------------------
 template <int NT, int NWV, int S>
-__global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_persist_kernel(ConvK p) {
+struct PersistHm {
+  using C = PipeCfg<NT, NWV, 0, S>;
+  static constexpr int PAR_FLOATS = 3 * 256 + 8;                              // hm.0 bias [256] | hm.2 row 0 [256] | row 1 [256] | hm.2 bias [8]
+  static constexpr int PAR_BYTES = (PAR_FLOATS * 4 + 255) & ~255;
+  static constexpr int XCH_BYTES = (NWV / 2) * C::MT * 64 * 4;                // wn = 1 -> wn = 0: one value per lane and row
+  static constexpr int SMEM = 2 * C::BUF_BYTES + PAR_BYTES + XCH_BYTES;
+  static_assert(SMEM <= 163840, "LDS budget");
+};
+
 #if defined(__HIP_DEVICE_COMPILE__)      // (buffer-resource builtins: device pass only, see conv3x3_pipe_kernel)
-  a16_kernel_enter();
+template <int NT, int NWV, int S, bool HM>
+__device__ __forceinline__ void conv3x3_pipe_persist_body(const ConvK& p) {
   using C = PipeCfg<NT, NWV, 0, S>;
   static_assert(C::NBLK == 1, "ordinary tiles");
+  static_assert(!HM || (NT == 2 && S == 1), "fused head: the 128-channel stride-1 tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1560,8 +1582,26 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_persist_kernel(ConvK
   const int wn = NT == 1 ? 0 : (wave & 1);       // which 64-channel half
   const int G = gridDim.x;
   const int Lw = xcd_remap(blockIdx.x, G);
-  const int t0 = (int)((long long)Lw * p.total_tiles / G), t1 = (int)((long long)(Lw + 1) * p.total_tiles / G);
+  // HM: a run is whole pixel tiles (n_tiles == 2 consecutive tiles each)
+  const int cut = HM ? 2 : 1, units = p.total_tiles / cut;
+  const int t0 = cut * (int)((long long)Lw * units / G), t1 = cut * (int)((long long)(Lw + 1) * units / G);
   if (t0 >= t1) return;
+  float* const hm_par = reinterpret_cast<float*>(smem + 2 * C::BUF_BYTES);
+  float* const hm_xch = reinterpret_cast<float*>(smem + 2 * C::BUF_BYTES + PersistHm<NT, NWV, S>::PAR_BYTES);
+  float hm_carry[C::MT];
+  if constexpr (HM) {
+    // (visible to every wave behind the first barrier below)
+    const bf16_t* hm_w2 = static_cast<const bf16_t*>(p.head_w);
+    if (tid < 256) {
+      hm_par[tid] = p.bias[tid];
+      hm_par[256 + tid] = bf16_to_f32(hm_w2[((tid >> 5) * 64 + 0) * 32 + (tid & 31)]);
+      hm_par[512 + tid] = bf16_to_f32(hm_w2[((tid >> 5) * 64 + 1) * 32 + (tid & 31)]);
+    } else if (tid < 264) {
+      hm_par[768 + tid - 256] = p.head_b[tid - 256];
+    }
+#pragma unroll
+    for (int m = 0; m < C::MT; ++m) hm_carry[m] = 0.f;
+  }
   const int in_cs = p.Cin;
   const int nch32 = p.Cin >> 5, nslices = nch32 * 2;
 
@@ -1716,7 +1756,74 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_persist_kernel(ConvK
     }
     skew_slice(nslices - 1, std::integral_constant<int, 1>{}, std::true_type{}, 0, 0);
     // epilogue from the accumulators; the next tile's first slice is in LDS
-    {
+    if constexpr (HM) {
+      const int n0 = (done.nb * 2 + wn) * 64;
+      float part[C::MT][2];
+#pragma unroll
+      for (int m = 0; m < C::MT; ++m) part[m][0] = part[m][1] = 0.f;
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int ch = n0 + nb * 32 + 8 * g + 4 * qh;      // registers 4 g .. 4 g + 3 of block nb: channels ch .. ch + 3
+          const f32x4 bv = *reinterpret_cast<const f32x4*>(hm_par + ch);
+          const f32x4 w0 = *reinterpret_cast<const f32x4*>(hm_par + 256 + ch);
+          const f32x4 w1 = *reinterpret_cast<const f32x4*>(hm_par + 512 + ch);
+#pragma unroll
+          for (int m = 0; m < C::MT; ++m) {
+            const uint32_t d0 = pack_bf16x2(fmaxf(acc[m][nb][4 * g + 0] + bv.x, 0.f), fmaxf(acc[m][nb][4 * g + 1] + bv.y, 0.f));
+            const uint32_t d1 = pack_bf16x2(fmaxf(acc[m][nb][4 * g + 2] + bv.z, 0.f), fmaxf(acc[m][nb][4 * g + 3] + bv.w, 0.f));
+            const float h0 = bf16lo_f32(d0), h1 = bf16hi_f32(d0), h2 = bf16lo_f32(d1), h3 = bf16hi_f32(d1);      // the hidden values as they would be stored
+            part[m][0] = fmaf(h0, w0.x, part[m][0]); part[m][1] = fmaf(h0, w1.x, part[m][1]);
+            part[m][0] = fmaf(h1, w0.y, part[m][0]); part[m][1] = fmaf(h1, w1.y, part[m][1]);
+            part[m][0] = fmaf(h2, w0.z, part[m][0]); part[m][1] = fmaf(h2, w1.z, part[m][1]);
+            part[m][0] = fmaf(h3, w0.w, part[m][0]); part[m][1] = fmaf(h3, w1.w, part[m][1]);
+          }
+        }
+#pragma unroll
+      for (int m = 0; m < C::MT; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
+      // the q halves: x = {output 0 of q = 0 | output 1 of q = 0}, y = {output 0 of q = 1 | output 1 of q = 1} -- lane q gets output q
+      float cur[C::MT];
+#pragma unroll
+      for (int m = 0; m < C::MT; ++m) {
+        const u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(part[m][0]), __float_as_uint(part[m][1]), false, false);
+        cur[m] = __uint_as_float(sw.x) + __uint_as_float(sw.y);
+      }
+      if (done.nb == 0) {      // (workgroup-uniform) channels 0 .. 127: wait for the other half
+#pragma unroll
+        for (int m = 0; m < C::MT; ++m) hm_carry[m] = cur[m];
+      } else {
+#pragma unroll
+        for (int m = 0; m < C::MT; ++m) {
+          cur[m] = hm_carry[m] + cur[m];
+          if (wn == 1) hm_xch[(wm * C::MT + m) * 64 + lane] = cur[m];
+        }
+        __syncthreads();      // (the next write of hm_xch is a pixel tile -- eight slice barriers -- away)
+        if (wn == 0) {
+          const float b2 = hm_par[768 + qh];
+#pragma unroll
+          for (int m = 0; m < C::MT; ++m) {
+            const float lg = (cur[m] + hm_xch[(wm * C::MT + m) * 64 + lane]) + b2;
+            const int oy = done.oy0 + C::MT * wm + m, ox = done.ox0 + lx;
+            const bool inside = oy < p.Ho && ox < p.Wo;
+            const size_t pix = ((size_t)done.b * p.Ho + oy) * p.Wo + ox;
+            if (p.head_prob && inside) p.head_prob[2 * pix + qh] = pt_heat_sigmoid(lg);
+            if (p.head_logits) {
+              // both logits to both lanes of the pixel: q = 0 stores channels 0 .. 3, q = 1 channels 4 .. 7
+              const u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(lg), __float_as_uint(lg), false, false);
+              const f32x4 pad = *reinterpret_cast<const f32x4*>(hm_par + 768 + 4 * qh);
+              f32x4 o = {0.f + pad.x, 0.f + pad.y, 0.f + pad.z, 0.f + pad.w};      // a padded output channel of the 1x1 launch: zero weights, then the bias
+              if (qh == 0) { o.x = __uint_as_float(sw.x); o.y = __uint_as_float(sw.y); }
+              if (inside) *reinterpret_cast<f32x4*>(p.head_logits + 8 * pix + 4 * qh) = o;
+            }
+          }
+        }
+      }
+    } else {
       const int n0 = (NT == 1 ? done.nb : done.nb * 2 + wn) * 64;
       const DirectBias bs = direct_bias<2>(p, n0, qh);
 #pragma unroll
@@ -1730,6 +1837,22 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_persist_kernel(ConvK
     }
     load_frags(smem, 0, 0);
   }
+}
+#endif
+
+template <int NT, int NWV, int S>
+__global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_persist_kernel(ConvK p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  a16_kernel_enter();
+  conv3x3_pipe_persist_body<NT, NWV, S, false>(p);
+#endif
+}
+
+template <int NT, int NWV, int S>
+__global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pipe_persist_hm_kernel(ConvK p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  a16_kernel_enter();
+  conv3x3_pipe_persist_body<NT, NWV, S, true>(p);
 #endif
 }
 
@@ -3369,6 +3492,37 @@ static int launch_pipe_persist(pt_engine* e, ConvK& k, hipStream_t s, double flo
   return PT_OK;
 }
 
+// the heat-map head in one launch (conv3x3_pipe_persist_hm_kernel): always the persistent form, a workgroup's run is whole pixel tiles
+static int launch_pipe_persist_hm(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
+  using C = PipeCfg<2, 8, 0, 1>;
+  using HM = PersistHm<2, 8, 1>;
+  static bool attr_done = false;
+  if (!attr_done) {
+    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pipe_persist_hm_kernel<2, 8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, HM::SMEM));
+    attr_done = true;
+  }
+  k.n_tiles = k.N / C::NW;
+  k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
+  k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
+  const long long ptiles = (long long)k.B * k.tiles_x * k.tiles_y, total = ptiles * k.n_tiles;
+  PT_REQUIRE(k.n_tiles == 2 && total > 0 && total < (1ll << 31), "conv grid out of range (%lld tiles)", total);
+  k.total_tiles = (int)total;
+  long long grid = e->num_cu;      // (one workgroup's LDS per CU)
+  if (const char* gv = getenv("PT_CONV_PERSIST_GRID")) {          // tests: fewer workgroups, longer runs
+    const int gg = atoi(gv);
+    if (gg > 0) grid = gg;
+  }
+  if (grid > ptiles) grid = ptiles;
+  char label[48];
+  snprintf(label, sizeof(label), "conv3x3 v5+hm %d->%d->2 @%dx%d", k.Cin, k.N, k.Ho, k.Wo);
+  {
+    PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, label);
+    hipLaunchKernelGGL((conv3x3_pipe_persist_hm_kernel<2, 8, 1>), dim3((unsigned)grid), dim3(C::NTHR), HM::SMEM, s, k);
+  }
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
 // 1x1 stride-1 plain layers with K >= 256, N % 128 == 0, M % 32 == 0 in the single-pass modes: the pipelined GEMM (gemm_pipe_kernel)
 static int launch_gemm_pipe(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
   using C = GemmPipeCfg;
@@ -3452,8 +3606,14 @@ static int conv_variant() {
   return v;
 }
 
+bool pt_conv_fuses_hm(const pt_engine* e) {
+  const char* ev = getenv("PT_LORE_HM_FUSE");      // 0: hm.0 and hm.2 as two launches (A/B switch, read per call)
+  const char* pv = getenv("PT_CONV_PIPE");         // below 4: the kernel families before the persistent tile, which the fused head is a form of
+  return !pt_split(e) && use_dma_kernel() && conv_variant() == 3 && !(pv && atoi(pv) < 4) && !(ev && atoi(ev) == 0);
+}
+
 int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
-  PT_REQUIRE(d.in && d.w && d.bias && (d.out || d.out_f32 || d.head_w || d.argmax_part), "conv: null pointer");
+  PT_REQUIRE(d.in && d.w && d.bias && (d.out || d.out_f32 || d.head_w || d.argmax_part || d.hm_w2), "conv: null pointer");
   PT_REQUIRE(d.Cin % 32 == 0 && d.Cin > 0, "conv: Cin=%d must be a positive multiple of 32", d.Cin);
   PT_REQUIRE(d.N % 64 == 0 && d.N > 0, "conv: N=%d must be a positive multiple of 64", d.N);
   PT_REQUIRE((d.ks == 1 || d.ks == 3) && (d.stride == 1 || d.stride == 2), "conv: ks=%d stride=%d unsupported", d.ks,
@@ -3523,6 +3683,19 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
     if (d.res || d.res_f32) by += (double)k.B * k.Ho * k.Wo * nstore * (d.res_f32 ? 4.0 : 2.0 * mact) / (d.res_mode == 2 ? 4.0 : 1.0);
     by += (double)d.N * d.Cin * d.ks * d.ks * 2.0 * (d.split == 2 ? 2 : (d.split ? 3 : 1));
     e->prof.next_bytes = by;
+  }
+  if (d.hm_w2) {
+    // hm.0 + hm.2 in one launch: the caller asked pt_conv_fuses_hm; anything but the plain 64 -> 256 + ReLU layer is a mistake, not a fall-back
+    PT_REQUIRE(pt_conv_fuses_hm(e) && d.ks == 3 && d.stride == 1 && d.Cin == 64 && d.N == 256 && d.relu == 1 && !d.res && !d.res_f32 && !d.split && d.nseg <= 1 &&
+                   !d.n_valid && !d.out_f32 && !d.head_w && !d.argmax_part && !d.ylimit && !d.xlimit && !d.xlimit_rows && !d.pool && d.rep == 1 && !d.shuffle_cout,
+               "conv: the fused heat-map head is the plain 3x3 64 -> 256 + ReLU layer in a single-pass mode");
+    PT_REQUIRE(d.hm_b2 && (d.hm_logits || d.hm_sig), "conv: fused heat-map head without bias or output");
+    for (int i = 0; i < 8; ++i) PT_REQUIRE(d.tap_mask[i] == 0, "conv: fused heat-map head with a tap mask");
+    k.head_w = d.hm_w2; k.head_b = d.hm_b2; k.head_logits = d.hm_logits; k.head_prob = d.hm_sig;
+    const double px = (double)k.B * k.Ho * k.Wo;
+    // feat once, the stored map(s) once, both layers' weights once
+    e->prof.next_bytes = px * d.Cin * 2.0 + px * ((d.hm_logits ? 8 : 0) + (d.hm_sig ? 2 : 0)) * 4.0 + (double)d.N * d.Cin * 9 * 2.0 + 2.0 * d.N * 2.0;
+    return launch_pipe_persist_hm(e, k, s, flop + 2.0 * px * d.N * 2.0);
   }
   // stride-2 3x3 layers with 128-wide output blocks (ResNet-18 / DLA-34 down-sampling convs): the 16-channel-slice DMA kernel on an 8 x 32 x 128 tile
   // (PT_CONV_S2_DMA=0: the register-staged 4 x 32 x 64 tile, A/B switch)

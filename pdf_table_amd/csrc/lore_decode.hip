@@ -30,8 +30,8 @@ __global__ __launch_bounds__(256) void lore_sigmoid_kernel(const float* __restri
   a16_kernel_enter();
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= npix) return;
-  sig[2 * i] = 1.f / (1.f + expf(-hm[8 * i]));
-  sig[2 * i + 1] = 1.f / (1.f + expf(-hm[8 * i + 1]));
+  sig[2 * i] = pt_heat_sigmoid(hm[8 * i]);
+  sig[2 * i + 1] = pt_heat_sigmoid(hm[8 * i + 1]);
 }
 
 // 3x3 max-pool equality (-inf padding) + threshold at pixel (y, x) of one table's score map sb [H][W][2]; s: the score there
@@ -510,7 +510,7 @@ __global__ __launch_bounds__(256) void lore_gather_kernel(const float* __restric
 // extra launch, no host synchronisation; lists within the capacity take the path they always took).
 int pt_heat_peaks_topk(const float* hm, int B, int H, int W, float thr0, float thr1, int k0, int k1, float* sig, unsigned long long* keys,
                        int* cnt, unsigned long long* sorted, int* kept, hipStream_t s) {
-  PT_REQUIRE(hm && sig && keys && cnt && sorted && kept && B > 0 && k0 <= CAP && k1 <= CAP, "heat peaks: bad arguments");
+  PT_REQUIRE(sig && keys && cnt && sorted && kept && B > 0 && k0 <= CAP && k1 <= CAP, "heat peaks: bad arguments");
   PT_REQUIRE((long long)H * W < (1ll << 31), "heat peaks: map too large");
   static bool attr_done = false;
   if (!attr_done) {
@@ -520,10 +520,17 @@ int pt_heat_peaks_topk(const float* hm, int B, int H, int W, float thr0, float t
     attr_done = true;
   }
   const size_t npix = (size_t)B * H * W;
-  hipLaunchKernelGGL(lore_sigmoid_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, hm, sig, (long long)npix);
+  if (hm) hipLaunchKernelGGL(lore_sigmoid_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, hm, sig, (long long)npix);
   hipLaunchKernelGGL(lore_peaks_kernel<1024>, dim3((unsigned)((npix + 1023) / 1024)), dim3(1024), 0, s, sig, B, H, W, thr0, thr1, keys, cnt);
   hipLaunchKernelGGL(lore_sort_kernel, dim3(2 * B), dim3(1024), CAP * 8, s, keys, cnt, 1, CAP, k0, k1, sorted, CAP, kept,
                      (const float*)sig, H, W, thr0, thr1);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_launch_heat_sigmoid(const float* hm, float* sig, long long npix, hipStream_t s) {
+  PT_REQUIRE(hm && sig && npix > 0, "heat sigmoid: bad arguments");
+  hipLaunchKernelGGL(lore_sigmoid_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, hm, sig, npix);
   PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }
@@ -539,23 +546,53 @@ struct DecodeState {
   int wiz_rev;
 };
 
-// sigmoid, peak test, first sort: the kept cells / corners of every table in score order
-static int decode_peaks(pt_engine* e, const float* hm, int B, int H, int W, int wiz_rev, float vis_thresh, int* d_counts,
-                        DecodeState* ds, hipStream_t s) {
-  PT_REQUIRE((long long)H * W < (1ll << 31), "tsr decode: map too large");
+// the engine's decode scratch for B maps of H x W, grown when it is too small
+struct DecodeCarve {
+  size_t o_sig, o_cnt, o_keys, o_sorted, o_boxes, o_rev, o_keys2, o_sorted2, o_sp, total;
+};
+static DecodeCarve decode_carve(int B, int H, int W) {
   const size_t npix = (size_t)B * H * W;
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
-  const size_t o_sig = carve(npix * 2 * 4), o_cnt = carve((size_t)B * 5 * 4), o_keys = carve((size_t)2 * B * CAP * 8),
-               o_sorted = carve((size_t)2 * B * CAP * 8), o_boxes = carve((size_t)2 * B * CAP * 12 * 4),
-               o_rev = carve((size_t)B * CAP * 12 * 4), o_keys2 = carve((size_t)B * CAP * 8),
-               o_sorted2 = carve((size_t)B * CAP * 8), o_sp = carve((size_t)(3 * B + 4) * 4);
-  if (off > e->tsr_scratch_cap) {
+  DecodeCarve c;
+  c.o_sig = carve(npix * 2 * 4); c.o_cnt = carve((size_t)B * 5 * 4); c.o_keys = carve((size_t)2 * B * CAP * 8);
+  c.o_sorted = carve((size_t)2 * B * CAP * 8); c.o_boxes = carve((size_t)2 * B * CAP * 12 * 4);
+  c.o_rev = carve((size_t)B * CAP * 12 * 4); c.o_keys2 = carve((size_t)B * CAP * 8);
+  c.o_sorted2 = carve((size_t)B * CAP * 8); c.o_sp = carve((size_t)(3 * B + 4) * 4);
+  c.total = off;
+  return c;
+}
+static int decode_scratch(pt_engine* e, const DecodeCarve& c) {
+  if (c.total > e->tsr_scratch_cap) {
     PT_HIP_CHECK(hipDeviceSynchronize());
     if (e->tsr_scratch) PT_HIP_CHECK(hipFree(e->tsr_scratch));
     e->tsr_scratch = nullptr; e->tsr_scratch_cap = 0;
-    PT_HIP_CHECK(hipMalloc(&e->tsr_scratch, off));
-    e->tsr_scratch_cap = off;
+    PT_HIP_CHECK(hipMalloc(&e->tsr_scratch, c.total));
+    e->tsr_scratch_cap = c.total;
+  }
+  return PT_OK;
+}
+
+int pt_lore_decode_sig_map(pt_engine* e, int B, int H, int W, float** d_sig) {
+  PT_REQUIRE(e && d_sig && B > 0 && H > 0 && W > 0, "tsr decode score map: bad arguments");
+  const DecodeCarve c = decode_carve(B, H, W);
+  const int rc = decode_scratch(e, c);
+  if (rc != PT_OK) return rc;
+  *d_sig = reinterpret_cast<float*>(reinterpret_cast<char*>(e->tsr_scratch) + c.o_sig);
+  return PT_OK;
+}
+
+// sigmoid, peak test, first sort: the kept cells / corners of every table in score order
+// hm == nullptr: the scores are already at pt_lore_decode_sig_map's address
+static int decode_peaks(pt_engine* e, const float* hm, int B, int H, int W, int wiz_rev, float vis_thresh, int* d_counts,
+                        DecodeState* ds, hipStream_t s) {
+  PT_REQUIRE((long long)H * W < (1ll << 31), "tsr decode: map too large");
+  const DecodeCarve c = decode_carve(B, H, W);
+  const size_t o_sig = c.o_sig, o_cnt = c.o_cnt, o_keys = c.o_keys, o_sorted = c.o_sorted, o_boxes = c.o_boxes, o_rev = c.o_rev, o_keys2 = c.o_keys2,
+               o_sorted2 = c.o_sorted2, o_sp = c.o_sp;
+  {
+    const int rc = decode_scratch(e, c);
+    if (rc != PT_OK) return rc;
   }
   char* base = reinterpret_cast<char*>(e->tsr_scratch);
   float* sig = reinterpret_cast<float*>(base + o_sig);
@@ -636,7 +673,7 @@ static_assert(sizeof(DecodeState) <= sizeof(pt_engine::tsr_decode_state), "Decod
 
 int pt_lore_decode_peaks(pt_engine* e, const float* hm, int B, int H, int W, int wiz_rev, float vis_thresh, int* d_counts,
                          const int** d_lim_cell, const int** d_lim_corner, hipStream_t s) {
-  PT_REQUIRE(hm && d_counts && B > 0, "tsr decode peaks: null pointer");
+  PT_REQUIRE(d_counts && B > 0, "tsr decode peaks: null pointer");
   PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr decode");
   int rc = decode_peaks(e, hm, B, H, W, wiz_rev, vis_thresh, d_counts, &g_ds, s);
   if (rc != PT_OK) return rc;

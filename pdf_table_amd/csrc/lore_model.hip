@@ -157,11 +157,30 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
     std::vector<T> y = {out[0], out[1], out[2]};
     c.ida("ida_up", y, 0, 3, 64, f24, true, nullptr, t2.f ? &y[0] : nullptr);
     const T feat = y[2];
-    T hid = c.alloc(feat.H, feat.W, 256);
+    // hm.0 + hm.2 in one launch (conv3x3_pipe_persist_hm_kernel): the 256-channel hidden map is never stored; PT_LORE_HM_FUSE=0: the two launches
+    const bool hm_fused = pt_conv_fuses_hm(e);
+    // sparse: with the fused head nobody needs `hid`, nor the logit map -- the launch writes the scores where the peak test reads them
+    T hid;
+    if (!(sp && hm_fused)) hid = c.alloc(feat.H, feat.W, 256);
     // only `hm` is needed everywhere: the other five heads run on patch mosaics (lore_decode.hip)
-    if (sp) heads[0] = c.take<float>((size_t)n * feat.H * feat.W * 8 * sizeof(float));
+    if (sp && !hm_fused) heads[0] = c.take<float>((size_t)n * feat.H * feat.W * 8 * sizeof(float));
     for (int h = 0; h < 6; ++h) {
       if (sp && h != 0) continue;
+      if (h == 0 && hm_fused) {
+        const PtTensor* w2 = c.get("hm.2.w");
+        const PtTensor* b2 = c.get("hm.2.b");
+        ConvDesc d;
+        if (!c.conv_desc(d, feat, "hm.0", 256, 3, 1, 1)) continue;
+        d.hm_w2 = c.W(w2); d.hm_b2 = c.F(b2);
+        if (sp) {
+          const int r = pt_lore_decode_sig_map(e, n, feat.H, feat.W, &d.hm_sig);
+          if (r != PT_OK) return r;
+        } else {
+          d.hm_logits = heads[0];
+        }
+        c.launch(d);
+        continue;
+      }
       c.conv(feat, std::string(hname[h]) + ".0", 256, 3, 1, hid, 1);
       c.conv(hid, std::string(hname[h]) + ".2", hcs[h] < 64 ? 64 : hcs[h], 1, 1, T(), 0, nullptr, hcs[h], heads[h], hcs[h], 0, hreal[h]);
     }

@@ -802,6 +802,27 @@ class HipEngine:
                 "pt_op_dcn_up_add")
         return out
 
+    def op_lore_hm_head(self, feat: torch.Tensor, w1_tiled: torch.Tensor, b1: torch.Tensor, w2_tiled: torch.Tensor, b2: torch.Tensor,
+                        fused: bool, want_sig: bool = False, want_sig_ref: bool = False, logits_fill: float = 0.0):
+        """Lore's heat-map head (pt_op_lore_hm_head) on feat [B,H,W,64]: hm.0 3x3 64 -> 256 + ReLU, hm.2 1x1 256 -> 2 (64 GEMM columns, rows 2.. zero).
+        Returns dict(logits fp32 [B,H,W,8] (pre-filled with logits_fill), hid [B,H,W,256] (two launches only), sig [B,H,W,2] (fused, want_sig),
+        sig_ref [B,H,W,2] (want_sig_ref: the decode's sigmoid launch on `logits`))."""
+        self._chk(feat, self.act_dtype, "feat")
+        self._chk(b1, torch.float32, "b1")
+        self._chk(b2, torch.float32, "b2")
+        B, H, W, Cc = feat.shape
+        if Cc != 64 or b1.numel() != 256 or b2.numel() != 64:
+            raise ValueError(f"op_lore_hm_head: feat [B,H,W,64], b1 [256], b2 [64]; got {tuple(feat.shape)}, {b1.numel()}, {b2.numel()}")
+        if want_sig and not fused:
+            raise ValueError("op_lore_hm_head: the two launches have no score output of their own (want_sig_ref)")
+        logits = torch.full((B, H, W, 8), float(logits_fill), dtype=torch.float32, device=self._tdev)
+        hid = None if fused else torch.empty((B, H, W, 256), dtype=self.act_dtype, device=self._tdev)
+        sig = torch.zeros((B, H, W, 2), dtype=torch.float32, device=self._tdev) if want_sig else None
+        sig_ref = torch.zeros((B, H, W, 2), dtype=torch.float32, device=self._tdev) if want_sig_ref else None
+        L.check(self.lib.pt_op_lore_hm_head(self._h, _ptr(feat), B, H, W, _ptr(w1_tiled), _ptr(b1), _ptr(w2_tiled), _ptr(b2), int(bool(fused)), _ptr(hid),
+                                            _ptr(logits), _ptr(sig), _ptr(sig_ref), self._stream()), "pt_op_lore_hm_head")
+        return dict(logits=logits, hid=hid, sig=sig, sig_ref=sig_ref)
+
     # ---- single operators of the generic ONNX executor (pdf_table_amd/onnx_exec.py); bf16 NHWC, C a multiple of 8 -------
     # (split=True: the tolerance mode's (hi | lo) tensors -- the last dimension holds [hi(C) | lo(C)], C = shape[-1] // 2)
     def op_dwconv(self, x: torch.Tensor, w_taps: torch.Tensor, bias: torch.Tensor, k: int, stride: int = 1, act: int = 0, split: bool = False) -> torch.Tensor:

@@ -44,7 +44,7 @@ PT_REC_H, PT_REC_W, PT_REC_T, PT_REC_NCLS = 32, 640, 160, 7644
 PT_PROF_CLASSES = ("conv3x3", "conv1x1", "stem", "other")
 EXPECTED_ABI = 19         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h).  19: pt_op_cvit_*.  pt_op_affine_act /
 #                           pt_op_db_tail were ADDED under 18: no existing signature changed, and a library without them fails to bind by name (_proto);
-#                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large under 19
+#                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large / pt_op_lore_hm_head under 19
 
 _lib = None
 
@@ -123,6 +123,7 @@ def _proto(lib):
         "pt_op_dcn": (i, [vp, vp, vp, i, i, i, i, vp, vp, i, vp, i, i, vp]),
         "pt_op_dwconvt_up_add": (i, [vp, vp, vp, vp, vp, i, i, i, i, i, i, vp]),
         "pt_op_dcn_up_add": (i, [vp, vp, vp, i, i, i, i, vp, vp, i, vp, i, i, vp, i, i, vp, i, vp]),
+        "pt_op_lore_hm_head": (i, [vp, vp, i, i, i, vp, vp, vp, vp, i, vp, vp, vp, vp, vp]),
         "pt_op_stem7x7": (i, [vp, vp, i, i, i, vp, vp, vp, i, vp]),
         "pt_op_maxpool3x3s2": (i, [vp, vp, i, i, i, i, vp, i, vp]),
         "pt_op_db_head_final": (i, [vp, vp, i, i, i, vp, vp, vp, vp, i, vp]),
