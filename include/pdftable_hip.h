@@ -615,6 +615,14 @@ int pt_op_affine_act(pt_engine* e, const uint16_t* d_in, long long npix, int Cpa
 int pt_op_db_tail(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int Cpad, int C, int C1, const float* d_w1, const float* d_b1,
                   const float* d_w2, const float* d_b2, float* d_out, int split, pt_stream stream);
 
+/* The tail of a CTC recognition head in one pass (csrc/ctc_ops.hip; added under ABI 19: one new entry point, no existing signature changed, so the
+ * version stays).  Input as pt_op_softmax: token rows of 16-bit logits [rows, c_pad] in the engine's storage format, the first c channels real
+ * ([hi(c_pad) | lo(c_pad)] when split, value = hi + lo in fp32).  Per row: d_ids[row] = the LOWEST index of the largest of the first c logits (numpy's
+ * argmax), d_conf[row] = that class's soft-max probability 1 / sum_k exp(l_k - l_max) in fp32 -- what CTCLabelDecode reads out of the probabilities
+ * (preds.argmax(axis=2), preds.max(axis=2)).  Every logit is read once; channels c .. c_pad - 1 are never read.  16-byte loads when c_pad is a
+ * multiple of 8 and d_in is 16-byte aligned, 2-byte loads otherwise; any rows >= 1 and c >= 1.  No allocation, no host synchronisation (capturable). */
+int pt_op_ctc_greedy(pt_engine* e, const uint16_t* d_in, long long rows, int c_pad, int c, int32_t* d_ids, float* d_conf, int split, pt_stream stream);
+
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------
  * Replaces ClsImagePulcTask._preprocess/_run_model (ocr_pdf/cls_image_pulc_task.py:48-84): PPLCNetImageProcessor

@@ -1043,6 +1043,17 @@ class HipEngine:
             L.check(self.lib.pt_op_softmax(self._h, _ptr(x), rows, cp, int(c), None, _ptr(out), int(split), self._stream()), "pt_op_softmax")
         return out
 
+    def op_ctc_greedy(self, x: torch.Tensor, c: int, split: bool = False):
+        """token rows of 16-bit logits [.., Cp] ([hi | lo] when split), the first c channels real -> (ids int32 [rows], conf float32 [rows]): per
+        row the lowest index of the largest logit and its soft-max probability (csrc/ctc_ops.hip: one pass, channels c .. Cp - 1 never read)"""
+        self._chk(x, self.act_dtype, "x")
+        rows = x.numel() // x.shape[-1]
+        cp = x.shape[-1] // 2 if split else x.shape[-1]
+        ids = torch.empty((rows,), dtype=torch.int32, device=self._tdev)
+        conf = torch.empty((rows,), dtype=torch.float32, device=self._tdev)
+        L.check(self.lib.pt_op_ctc_greedy(self._h, _ptr(x), rows, cp, int(c), _ptr(ids), _ptr(conf), int(split), self._stream()), "pt_op_ctc_greedy")
+        return ids, conf
+
     def op_attention(self, qkv: torch.Tensor, heads: int, d: int, scale: float, out_c: int, split: bool = False) -> torch.Tensor:
         """qkv bf16 [B, 1, T, >= 3 heads d] rows of [q | k | v] -> bf16 [B, 1, T, out_c] (channels heads * d .. out_c are zero); split: both tensors
         carry [hi | lo] halves of that width"""

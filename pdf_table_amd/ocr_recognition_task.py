@@ -16,7 +16,10 @@ Two ways in:
     ``OcrSystemTask.text_recognition`` passes it (ocr_system_task.py:309-320); all crops of the call go through one
     ``pt_rec_forward_crops`` (ragged batch);
   * batched: ``task.recognize_quads(pages_gpu, boxes_per_page)`` -- quads are cut out of the resident pages on the
-    device (no host crop at all); this is what ``OcrTablePipeline`` and ``bench.py`` use.
+    device (no host crop at all); this is what ``OcrTablePipeline`` uses for every recogniser (``RecStage`` for the in-tree ones,
+    ``PPRecStage`` -- pprec_stage.py -- for the PP-OCR ONNX recognisers, whose per-line scores it keeps in ``_stage.last_scores``) and what
+    ``bench.py`` measures with the in-tree CRNN.  ``rec_batch_num`` (default 6, the reference's) and ``rec_width_bucket`` (default None: the
+    reference's per-mini-batch width; an integer rounds it up to a multiple, zero padding only) shape the PP-OCR mini-batches of both doors.
 """
 from __future__ import annotations
 
@@ -81,7 +84,8 @@ class OcrRecognitionTask(BaseInferTask):
         shp = list(getattr(self._exec.inputs[0], "shape", []) or [])
         static = len(shp) == 4 and all(isinstance(d, int) and d > 0 for d in shp[1:])
         self._batch1 = len(shp) == 4 and isinstance(shp[0], int) and shp[0] == 1       # batch size baked in: one walk per line
-        cfg = PPOcrRecConfig(rec_image_shape=f"{shp[1]}, {shp[2]}, {shp[3]}", limited_max_width=int(shp[3])) if static else PPOcrRecConfig()
+        knobs = {"rec_batch_num": int(self.kwargs.get("rec_batch_num", 6)), "rec_width_bucket": self.kwargs.get("rec_width_bucket")}
+        cfg = PPOcrRecConfig(rec_image_shape=f"{shp[1]}, {shp[2]}, {shp[3]}", limited_max_width=int(shp[3]), **knobs) if static else PPOcrRecConfig(**knobs)
         self._pp = PPOcrRecPreProcessor(cfg, engine=self._engine)
         d = self.kwargs.get("character_dict_path")
         if d is None:
@@ -90,6 +94,10 @@ class OcrRecognitionTask(BaseInferTask):
         self._ctc = CTCLabelDecode(d, use_space_char=bool(self.kwargs.get("use_space_char", True)))
         self._vocab = None
         self.last_scores: List[float] = []
+        # the batched door's executor: same graph, its walk ends in pt_op_ctc_greedy (ids and probability per token) where the graph ends in a
+        # Softmax nothing else reads; operands are uploaded on first use, so a task used through one door only holds one set of weights
+        self._exec_tail = HipGraphExecutor(self._exec.graph, engine=self._engine, precision=self._exec_precision,
+                                           ctc_tail=bool(self.kwargs.get("ctc_tail", True)))
         self._model = self._predict_pp
 
     def _predict_pp(self, crops):
@@ -165,7 +173,8 @@ class OcrRecognitionTask(BaseInferTask):
 
     def _build_processor(self):
         if self.model in ("PP-OCRv4", "PP-OCRv3", "PP-Table"):
-            self._stage = None
+            from .pprec_stage import PPRecStage
+            self._stage = PPRecStage(self._engine, self._pp, self._exec_tail, self._ctc, batch1=self._batch1)
             return
         self._stage = RecStage(self._engine, self._vocab, recognizer=self._config.recognizer)
 

@@ -110,6 +110,17 @@ class _View:
 
 
 @dataclass
+class _CtcOut:
+    """what a planned CTC tail returns in place of the probabilities [B, T, c] (ctc_tail=True): per token the class id and its probability"""
+    ids: torch.Tensor       # int32 [B, T]: the lowest index of the largest logit (numpy's argmax)
+    conf: torch.Tensor      # float32 [B, T]: that class's soft-max probability
+    c: int                  # classes
+
+    def shape(self):
+        return tuple(self.ids.shape) + (self.c,)
+
+
+@dataclass
 class _Scores:
     """q k^T of a recognised fused-qkv attention (never materialised): soft-max and the product with v follow"""
     base: _Act
@@ -141,10 +152,14 @@ _CAPTURE_LOCK = threading.Lock()      # graph capture is serialised across execu
 
 
 class HipGraphExecutor:
-    def __init__(self, src, engine: Optional[HipEngine] = None, device: int = 0, precision: str = "bf16", fuse_db_tail: bool = False):
+    def __init__(self, src, engine: Optional[HipEngine] = None, device: int = 0, precision: str = "bf16", fuse_db_tail: bool = False,
+                 ctc_tail: bool = False):
         """fuse_db_tail: run a DB head's tail -- convT 2x2 / 2 + ReLU -> convT 2x2 / 2 to one channel + Sigmoid, the graph's output -- as ONE
         pt_op_db_tail launch with an fp32 result (see _plan_db_tail).  Off by default: the fused launch keeps the intermediate in fp32 where the layered
-        route rounds it to 16 bits, so its bits differ from the layered route's."""
+        route rounds it to 16 bits, so its bits differ from the layered route's.
+        ctc_tail: end a CTC recogniser's walk in ONE pt_op_ctc_greedy launch on the logits (see _plan_ctc_tail): the graph's single output is then a
+        _CtcOut (class id and probability per token) instead of the fp32 probabilities.  Off by default: every caller that reads probabilities keeps
+        getting them."""
         if precision not in ("bf16", "bf16x3", "f16"):
             raise ValueError(f"precision '{precision}': 'bf16' (throughput), 'f16' (single-pass IEEE half, the reference's fp16) or 'bf16x3' "
                              "(tolerance mode, (hi | lo) activations)")
@@ -177,6 +192,7 @@ class HipGraphExecutor:
         self._bad: set = set()                                  # shapes whose capture raised: eager from then on
         self._fuse = self._plan_add_fusion()
         self._tail = self._plan_db_tail() if fuse_db_tail else {}
+        self.ctc_tail_layer: Optional[int] = self._plan_ctc_tail() if ctc_tail else None      # None: the layered route, probabilities out
         # every tensor some layer reads (constants included): an LSTM's Y_h / Y_c are supported only when nothing does
         self._read = {nm for l in self.layers for nm in list(l.inputs) + list(l.attrs.get("all_inputs", ())) if nm} | set(self.outputs)
 
@@ -245,6 +261,20 @@ class HipGraphExecutor:
                 continue
             plan[k] = j
         return plan
+
+    def _plan_ctc_tail(self) -> Optional[int]:
+        """A Softmax over the last axis whose output is the graph's ONLY output and is read by no layer -> its index: the walk ends there in
+        pt_op_ctc_greedy on the Softmax's input (csrc/ctc_ops.hip).  Anything else -- logits out, a second output, a Softmax something else reads --
+        -> None: the layered route, unchanged.  Whether the Softmax's input is token rows is known only during the walk (run_device checks)."""
+        if len(self.outputs) != 1:
+            return None
+        hit = None
+        for j, lay in enumerate(self.layers):
+            if self.outputs[0] in lay.inputs or self.outputs[0] in lay.attrs.get("all_inputs", ()):
+                return None
+            if lay.op == "act" and lay.attrs.get("kind") == "softmax" and list(lay.outputs) == [self.outputs[0]]:
+                hit = j
+        return hit
 
     def _db_tail(self, k: int, x: _Act) -> _Act:
         lay, nx = self.layers[k], self.layers[self._tail[k]]
@@ -570,6 +600,9 @@ class HipGraphExecutor:
         outs = []
         nhwc = xt.permute(0, 2, 3, 1).to(self.eng._tdev)
         for a in self.run_device(nhwc if self.split else nhwc.to(self.adt), xt.shape[1]):
+            if isinstance(a, _CtcOut):                   # ctc_tail=True: ids int32 [B, T] and probabilities float32 [B, T]
+                outs += [a.ids.cpu().numpy(), a.conf.cpu().numpy()]
+                continue
             v = self.values(a)
             if a.seq:                                    # token rows: [B, T, C] ([T, B, C] for a time-major output: a host-side transpose)
                 rows = v[:, 0].transpose(0, 1) if a.tm else v[:, 0]
@@ -990,6 +1023,12 @@ class HipGraphExecutor:
                     x = ins[0]
                     if not (x.seq or x.flat) or lay.attrs.get("axis", -1) not in (-1, len(x.shape()) - 1):
                         raise UnsupportedOnnxGraph(f"{lay.name}: Softmax over axis {lay.attrs.get('axis')} of a {x.shape()} tensor (the channel axis of token rows is built)")
+                    if k == self.ctc_tail_layer and x.seq and tmaj is None:
+                        # the planned CTC tail: id and probability per token straight from the logits, the probabilities are never written
+                        ids, conf = self.eng.op_ctc_greedy(x.t, x.c, split=self.split)
+                        Bn, T = x.t.shape[0], x.t.shape[2]
+                        env[lay.outputs[0]] = _CtcOut(ids.view(Bn, T), conf.view(Bn, T), x.c)
+                        continue
                     # a Softmax that IS a graph output (the probabilities a CTC decoder / classifier reads) stays fp32 [.., c]: bf16 probabilities have 8
                     # significant bits, so near-equal classes tie and the arg-max / confidence would differ from onnxruntime's fp32 ones
                     y = _Act(self.eng.op_softmax(x.t, x.c, f32=lay.outputs[0] in self.outputs, split=self.split), x.c, x.flat, x.seq)
@@ -1038,6 +1077,9 @@ class HipGraphExecutor:
                 raise UnsupportedOnnxGraph(f"graph output '{name}' was not produced")
         res = []
         for name in self.outputs:
+            if isinstance(env[name], _CtcOut):
+                res.append(env[name])
+                continue
             try:
                 res.append(R(env[name], f"graph output '{name}'"))
             except UnsupportedOnnxGraph:

@@ -72,7 +72,7 @@ class OcrTablePipeline:
                  precision: str = "bf16", layout_precision: Optional[str] = None, deskew: bool = False,
                  sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
                  table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
-                 **kwargs):
+                 rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, **kwargs):
         self.engine = HipEngine(device)
         # image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-468; page_pre_stage.py):
         # deskew=True warps a page back by the angle of its long horizontal rules; page_orientation=True classifies the page with
@@ -116,6 +116,11 @@ class OcrTablePipeline:
             dk["task_path"] = det_task_path
         if rec_task_path:
             rk["task_path"] = rec_task_path
+        if recognizer in ("PP-OCRv4", "PP-OCRv3", "PP-Table"):
+            # mini-batches of the PP-OCR recognisers (PPRecStage): the reference's 6 lines and per-mini-batch width unless asked otherwise
+            rk["rec_batch_num"], rk["rec_width_bucket"] = rec_batch_num, rec_width_bucket
+            if rec_task_path:      # these recognisers have no seeded weights: the file is served, beside seeded stages of the same pipeline
+                rk.pop("synthetic_seed", None)
         self.text_detector = OcrDetectionTask(model=detect_model, thresh=thresh, engine=self.engine, **dk)
         self.text_recognizer = OcrRecognitionTask(model=recognizer, engine=self.engine, **rk)
         self.layout_task = None
@@ -317,6 +322,7 @@ class OcrTablePipeline:
             if side is not None:
                 with stage_range("text_recognition"):
                     texts = finish_rec()
+            rec_scores = getattr(rec_stage, "last_scores", None)      # per page, per line: the PP-OCR recognisers' stage keeps them (PPRecStage)
             if tsr is not None and self.table_html:
                 self._attach_html(tsr, tb, boxes, texts)
             d_ = time.time()
@@ -326,7 +332,7 @@ class OcrTablePipeline:
             for k, i in enumerate(idxs):
                 # bbox = OcrCommonUtils.order_point(det_result[j]) (ocr_system_task.py:311-320), what OcrCell.parse consumes
                 pts = order_points(boxes[k]) if len(boxes[k]) else np.zeros((0, 4, 2), np.float32)
-                ocr = [{"index": j + 1, "text": t, "bbox": pts[j]} for j, t in enumerate(texts[k])]
+                ocr = self._ocr_entries(pts, texts[k], None if rec_scores is None else rec_scores[k])
                 results[i] = PageResult(rotated_180=rotated[k], skew_angle=skew[i], rotated_90=turned[i], image_shape=tuple(shape),
                                         page_orientation=page_ori[i], table_attribute=page_attr[i],
                                         det_result=boxes[k], ocr_result=ocr, layout_result=None if lay is None else lay[k],
@@ -676,6 +682,7 @@ class OcrTablePipeline:
             nonlocal total_lines
             t0 = time.perf_counter()
             texts = self._finish_rec(rec_stage, st["pages"], st["boxes"], st["rec"], rec_s)
+            rec_scores = getattr(rec_stage, "last_scores", None)      # of THIS finish(): the next batch's start() does not touch them
             t1 = time.perf_counter()
             host["collect.texts"] = host.get("collect.texts", 0.0) + t1 - t0
             tsr = None
@@ -718,7 +725,7 @@ class OcrTablePipeline:
             for k in range(st["n"]):
                 boxes = st["boxes"][k]
                 pts = order_points(boxes) if len(boxes) else np.zeros((0, 4, 2), np.float32)
-                ocr = [{"index": j + 1, "text": t, "bbox": pts[j]} for j, t in enumerate(texts[k])]
+                ocr = self._ocr_entries(pts, texts[k], None if rec_scores is None else rec_scores[k])
                 total_lines += len(ocr)
                 out.append(PageResult(det_result=boxes, ocr_result=ocr, layout_result=None if st["layout"] is None else st["layout"][k],
                                       table_structure_result=None if tsr is None else tsr[k],
@@ -831,6 +838,16 @@ class OcrTablePipeline:
                 table["table_html"], table["db_table_html"] = page_table_html(
                     table["polygons"], table["logi"], tb[k][ti], boxes[k], texts[k])
 
+    @staticmethod
+    def _ocr_entries(pts, texts, scores) -> List[Dict]:
+        """[{"index", "text", "bbox"}] like modeling_ocr_pdf.py:286-291; with a recogniser whose stage keeps per-line scores (the PP-OCR ones:
+        CTCLabelDecode's mean of the kept per-step maxima) a "score" key as well"""
+        ocr = [{"index": j + 1, "text": t, "bbox": pts[j]} for j, t in enumerate(texts)]
+        if scores is not None:
+            for e, sc in zip(ocr, scores):
+                e["score"] = sc
+        return ocr
+
     def _finish_rec(self, rec_stage, pages_t, boxes, state, stream) -> List[List[str]]:
         """-> texts; a device-side failure (PtError from pt_engine_check: the engine has switched to the streaming LSTM and
         cleared the flag) is logged and the batch is run once more; only then the reference's containment (empty strings,
@@ -850,4 +867,6 @@ class OcrTablePipeline:
                 logger.warning("text recognition failed: %r", e)
                 break
         logger.error("text recognition of %d lines yields empty strings", sum(len(b) for b in boxes))
+        if hasattr(rec_stage, "last_scores"):      # not the scores of an earlier batch
+            rec_stage.last_scores = [[0.0] * len(b) for b in boxes]
         return [[""] * len(b) for b in boxes]

@@ -30,16 +30,23 @@ class PPOcrRecConfig:
     """the four fields of PPOcrRecognitionConfig (configuration_ocr_recognition_pp.py:43-58) the pre-processor reads"""
 
     def __init__(self, rec_image_shape: str = "3, 48, 320", limited_max_width: int = 1280, limited_min_width: int = 16,
-                 rec_batch_num: int = 6):
+                 rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None):
         self.rec_image_shape = [int(v.strip()) for v in rec_image_shape.split(",")]
         self.limited_max_width = limited_max_width
         self.limited_min_width = limited_min_width
         self.rec_batch_num = rec_batch_num
+        # not a field of the reference: None keeps its per-mini-batch width; an integer rounds every mini-batch's width up to a multiple of it
+        # (capped at limited_max_width), which only adds zero padding on the right and bounds the number of distinct network input shapes
+        if rec_width_bucket is not None and int(rec_width_bucket) < 1:
+            raise ValueError(f"rec_width_bucket={rec_width_bucket!r}: None or a positive integer")
+        self.rec_width_bucket = None if rec_width_bucket is None else int(rec_width_bucket)
 
 
 def rec_pp_plan(crop_w: Sequence[int], crop_h: Sequence[int], config: Optional[PPOcrRecConfig] = None):
     """-> (items REC_PP_ITEM_DTYPE in processing order, batches [(batch_beg_img_no, n, img_w, float offset)], total floats).
-    The arithmetic of PPOcrRecPreProcessor.__call__ (:100-126) and resize_norm_img (:43-58), in Python floats as there."""
+    The arithmetic of PPOcrRecPreProcessor.__call__ (:100-126) and resize_norm_img (:43-58), in Python floats as there.  With
+    config.rec_width_bucket the padded width of a mini-batch is rounded up to a multiple of it (never beyond limited_max_width); every crop's
+    resized width stays what the unrounded plan gives, so the pixels are the same and only the zero padding on the right grows."""
     cfg = config or PPOcrRecConfig()
     imgC, imgH, imgW0 = cfg.rec_image_shape
     n = len(crop_w)
@@ -57,13 +64,17 @@ def rec_pp_plan(crop_w: Sequence[int], crop_h: Sequence[int], config: Optional[P
         max_wh_ratio = max(max_wh_ratio, imgW0 / imgH)
         img_w = int((imgH * max_wh_ratio))
         img_w = max(min(img_w, cfg.limited_max_width), cfg.limited_min_width)
-        batches.append((beg, end - beg, img_w, off))
+        pad_w = img_w
+        bucket = getattr(cfg, "rec_width_bucket", None)
+        if bucket:
+            pad_w = max(img_w, min(-(-img_w // bucket) * bucket, cfg.limited_max_width))
+        batches.append((beg, end - beg, pad_w, off))
         for ino in range(beg, end):
             i = indices[ino]
             ratio = int(crop_w[i]) / float(int(crop_h[i]))
             ratio_img_h = max(math.ceil(imgH * ratio), cfg.limited_min_width)
-            items[ino] = (i, img_w if ratio_img_h > img_w else int(ratio_img_h), img_w, 0, off)
-            off += imgC * imgH * img_w
+            items[ino] = (i, img_w if ratio_img_h > img_w else int(ratio_img_h), pad_w, 0, off)
+            off += imgC * imgH * pad_w
     return items, batches, off
 
 
@@ -110,12 +121,18 @@ class PPOcrRecPreProcessor:
     def lines(self, pages: torch.Tensor, boxes_per_page: Sequence[np.ndarray]) -> List[Dict]:
         """batched form: every detected box of a page batch (boxes [k,8] per page, source pixels) is cut out of the resident
         pages on the device (order_point + crop_image, as the recognition stage does) and pre-processed in one call"""
+        return self.lines_kept(pages, boxes_per_page)[0]
+
+    def lines_kept(self, pages: torch.Tensor, boxes_per_page: Sequence[np.ndarray]):
+        """lines() and which lines it kept: -> (mini-batches, kept bool [lines of the page batch, page by page]).  A quad whose crop is zero pixels
+        wide or high has no image (cv2.resize raises in the reference and the system path turns that into ''); `indices` of the mini-batches count
+        the KEPT lines, so np.nonzero(kept)[0][indices[..]] is a line's position in the page batch."""
         from .rec_stage import build_lines
         lines = build_lines(boxes_per_page)
         keep = (lines["crop_w"] > 0) & (lines["crop_h"] > 0)
         if not keep.any():
-            return []
+            return [], keep
         lines = lines[keep]
         items, batches, total = rec_pp_plan(lines["crop_w"], lines["crop_h"], self.config)
         flat = self.engine.rec_pp_preprocess(pages, lines, items, total, self.rec_image_shape[1])
-        return self._batches(flat, items, batches)
+        return self._batches(flat, items, batches), keep
