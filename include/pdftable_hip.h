@@ -623,6 +623,40 @@ int pt_op_db_tail(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C
  * multiple of 8 and d_in is 16-byte aligned, 2-byte loads otherwise; any rows >= 1 and c >= 1.  No allocation, no host synchronisation (capturable). */
 int pt_op_ctc_greedy(pt_engine* e, const uint16_t* d_in, long long rows, int c_pad, int c, int32_t* d_ids, float* d_conf, int split, pt_stream stream);
 
+/* PaddleOCR's SLAHead, the table-structure head of SLANet, as one launch (csrc/sla_head.hip; added under ABI 19: three new entry points, no existing
+ * signature changed, so the version stays).  The head is an ONNX Loop in the exported graph: an attention-GRU cell walked T times with the arg-max of
+ * step t fed back as the one-hot input of step t + 1 (SLAHead.forward in eval mode + AttentionGRUCell).
+ * d_fea: token rows 16-bit [B, N, c_pad] in the engine's storage format, the first C channels real ([hi(c_pad) | lo(c_pad)] when split); channels
+ * C .. c_pad - 1 may hold anything.  State: h = 0 [H], previous id p = 0.  Once per table P = fea W_i2h^T [N, H] (no bias).  Per step t = 0 .. T - 1:
+ *   q = W_h2h h + b_h2h;  e_n = w_score . tanh(P_n + q);  alpha = softmax_n(e);  ctx = sum_n alpha_n fea_n [C];  x = [ctx, onehot_V(p)]
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr);  z = sigmoid(W_iz x + b_iz + W_hz h + b_hz);  c = tanh(W_ic x + b_ic + r (W_hc h + b_hc))
+ *   h <- (h - c) z + c   (the one-hot part of W_i* x is a column read of W_i*[:, C + p])
+ *   s = W_s2 (W_s1 h + b_s1) + b_s2 [V];  d_probs[b, t] = softmax(s);  d_ids[b, t] = the LOWEST index of max(s);  p <- d_ids[b, t]
+ *   d_loc[b, t] = sigmoid(W_l2 (W_l1 h + b_l1) + b_l2) [L]
+ * h, the gate sums, both soft-maxes, c and P are fp32 for the whole walk; only the weights and d_fea are 16-bit.
+ * eos_id >= 0: a table stops after the first step t > 0 whose id is eos_id; that row is written, the rows after it are written as zeros (d_ids too),
+ * d_steps[b] = rows written.  eos_id < 0: every table walks all T steps (what the exported graph does).
+ * d_force_ids ([B, T] or NULL): when given, p for step t + 1 is d_force_ids[b, t] (clamped into [0, V)) instead of the step's own arg-max; d_ids still
+ * reports the arg-max.  For comparing a 16-bit walk step by step against a reference; products pass NULL.
+ * d_w16 / d_f32: the images of pdf_table_amd/weights.py::pack_sla_head, n16 16-bit values (twice that when split: the hi image, then the lo image) and
+ * n32 floats as pt_op_sla_packed_elems reports.  d_scratch: pt_op_sla_scratch_bytes(B, N, H) bytes, 16-byte aligned like every pointer here.
+ * Outputs: d_probs fp32 [B, T, V], d_loc fp32 [B, T, L], d_ids int32 [B, T], d_steps int32 [B].
+ * Built range: H a multiple of 32 up to 256, 1 <= C <= c_pad <= 128 (c_pad a multiple of 8), 1 <= V <= 64, L 4 or 8, 1 <= N <= 256, B >= 1, T >= 1;
+ * anything else is PT_ERR_INVALID with a message.  One workgroup per table, no cross-workgroup synchronisation, the step loop bounded by T; one
+ * launch, no allocation and no host synchronisation (capturable). */
+int pt_op_sla_decode(pt_engine* e, const uint16_t* d_fea, int B, int N, int c_pad, int C, int H, int V, int L, int T, const uint16_t* d_w16,
+                     const float* d_f32, void* d_scratch, long long scratch_bytes, int eos_id, const int32_t* d_force_ids, float* d_probs, float* d_loc,
+                     int32_t* d_ids, int32_t* d_steps, int split, pt_stream stream);
+int pt_op_sla_packed_elems(int H, int C, int V, int L, long long* n16, long long* n32);
+int pt_op_sla_scratch_bytes(int B, int N, int H, long long* bytes);
+/* SLANetPreprocessor for n table crops of resident pages (csrc/sla_head.hip; model/slanet/processor_slanet.py:32-53): the integer crop read as BGR,
+ * ratio = size / max(h, w), cv2.resize (8-bit bilinear) to (int(w ratio), int(h ratio)), (v / 255 - mean) / std with DB's constants indexed in that BGR
+ * order, zero padding to size x size at the top-left.  d_pages_rgb uint8 [n_pages, ph, pw, 3]; d_tables / h_tables: the same n pt_tsr_table records on
+ * the device and on the host (page, x0, y0, crop_w, crop_h are read; the host copy is checked against the page, so no crop is read out of bounds);
+ * d_out fp32 NHWC [n, size, size, 3], channels B, G, R.  No allocation, no host synchronisation (capturable). */
+int pt_slanet_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* d_tables, const pt_tsr_table* h_tables,
+                         int n, int size, float* d_out, pt_stream stream);
+
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------
  * Replaces ClsImagePulcTask._preprocess/_run_model (ocr_pdf/cls_image_pulc_task.py:48-84): PPLCNetImageProcessor

@@ -1054,6 +1054,61 @@ class HipEngine:
         L.check(self.lib.pt_op_ctc_greedy(self._h, _ptr(x), rows, cp, int(c), _ptr(ids), _ptr(conf), int(split), self._stream()), "pt_op_ctc_greedy")
         return ids, conf
 
+    def slanet_preprocess(self, pages: torch.Tensor, tables: np.ndarray, size: int = 488) -> torch.Tensor:
+        """SLANetPreprocessor on resident pages (pt_slanet_preprocess): pages uint8 [n_pages, h, w, 3], tables TSR_TABLE_DTYPE records (page, x0, y0,
+        crop_w, crop_h) -> float32 NHWC [n, size, size, 3] in B, G, R order, zero-padded at the bottom and the right"""
+        self._chk(pages, torch.uint8, "pages")
+        assert tables.dtype == TSR_TABLE_DTYPE
+        n = len(tables)
+        host = np.ascontiguousarray(tables)
+        d_tab = _upload(host.view(np.uint8).reshape(-1), self._tdev)
+        out = torch.empty((n, int(size), int(size), 3), dtype=torch.float32, device=self._tdev)
+        L.check(self.lib.pt_slanet_preprocess(self._h, _ptr(pages), pages.shape[0], pages.shape[1], pages.shape[2], _ptr(d_tab), C.c_void_p(host.ctypes.data), n,
+                                              int(size), _ptr(out), self._stream()), "pt_slanet_preprocess")
+        return out
+
+    def op_sla_scratch_bytes(self, B: int, N: int, hidden: int) -> int:
+        n = C.c_longlong(0)
+        L.check(self.lib.pt_op_sla_scratch_bytes(int(B), int(N), int(hidden), C.byref(n)), "pt_op_sla_scratch_bytes")
+        return int(n.value)
+
+    def op_sla_decode(self, fea: torch.Tensor, c: int, w16: torch.Tensor, f32: torch.Tensor, hidden: int, n_cls: int, n_loc: int, steps: int,
+                      eos_id: int = -1, force_ids: Optional[torch.Tensor] = None, split: bool = False, scratch: Optional[torch.Tensor] = None):
+        """The whole greedy walk of SLANet's head in one launch (pt_op_sla_decode, csrc/sla_head.hip).  fea: token rows [B, N, c_pad] ([hi | lo] of
+        that width when split), the first c channels real; w16 / f32: the images of weights.pack_sla_head on the device (w16 any 2-byte dtype,
+        [halves, n16]); scratch: a uint8 tensor of op_sla_scratch_bytes(B, N, hidden) bytes (allocated here when None) ->
+        (probs float32 [B, T, V], loc float32 [B, T, L], ids int32 [B, T], steps int32 [B]).  eos_id >= 0: a table stops after the first step
+        t > 0 whose id is eos_id, the rows after it are zeros; force_ids int32 [B, T]: the id fed to step t + 1 (ids still report the arg-max)."""
+        self._chk(fea, self.act_dtype, "fea")
+        self._chk(f32, torch.float32, "f32")
+        if fea.dim() != 3:
+            raise ValueError(f"op_sla_decode: fea must be [B, N, c_pad], got {tuple(fea.shape)}")
+        B, N = fea.shape[0], fea.shape[1]
+        m = 2 if split else 1
+        cp = fea.shape[2] // m
+        n16, n32 = C.c_longlong(0), C.c_longlong(0)
+        L.check(self.lib.pt_op_sla_packed_elems(int(hidden), int(c), int(n_cls), int(n_loc), C.byref(n16), C.byref(n32)), "pt_op_sla_packed_elems")
+        if not (w16.is_cuda and w16.is_contiguous() and w16.element_size() == 2 and w16.numel() == m * n16.value and f32.numel() == n32.value):
+            raise ValueError(f"op_sla_decode: packed images of {w16.numel()} / {f32.numel()} values, {m * n16.value} / {n32.value} expected "
+                             f"(weights.pack_sla_head, split={bool(split)})")
+        T = int(steps)
+        if force_ids is not None:
+            self._chk(force_ids, torch.int32, "force_ids")
+            if tuple(force_ids.shape) != (B, T):
+                raise ValueError(f"op_sla_decode: force_ids must be [{B}, {T}], got {tuple(force_ids.shape)}")
+        need = self.op_sla_scratch_bytes(B, N, hidden)
+        if scratch is None:
+            scratch = torch.empty((need,), dtype=torch.uint8, device=self._tdev)
+        self._chk(scratch, torch.uint8, "scratch")
+        probs = torch.empty((B, T, int(n_cls)), dtype=torch.float32, device=self._tdev)
+        loc = torch.empty((B, T, int(n_loc)), dtype=torch.float32, device=self._tdev)
+        ids = torch.empty((B, T), dtype=torch.int32, device=self._tdev)
+        nsteps = torch.empty((B,), dtype=torch.int32, device=self._tdev)
+        L.check(self.lib.pt_op_sla_decode(self._h, _ptr(fea), B, N, cp, int(c), int(hidden), int(n_cls), int(n_loc), T, _ptr(w16), _ptr(f32), _ptr(scratch),
+                                          scratch.numel(), int(eos_id), _ptr(force_ids), _ptr(probs), _ptr(loc), _ptr(ids), _ptr(nsteps), int(split),
+                                          self._stream()), "pt_op_sla_decode")
+        return probs, loc, ids, nsteps
+
     def op_attention(self, qkv: torch.Tensor, heads: int, d: int, scale: float, out_c: int, split: bool = False) -> torch.Tensor:
         """qkv bf16 [B, 1, T, >= 3 heads d] rows of [q | k | v] -> bf16 [B, 1, T, out_c] (channels heads * d .. out_c are zero); split: both tensors
         carry [hi | lo] halves of that width"""

@@ -1,5 +1,5 @@
 """``OcrTableStructureTask`` on the HIP engine -- drop-in for the reference's stage-4 plug-in (model="CenterNet" -- the default --, "Lore",
-"MtlTabNet", "TableMaster").
+"MtlTabNet", "TableMaster", and "SLANet" through its ONNX door).
 
 Reference: src/pdftable/model/ocr_pdf/ocr_table_structure_task.py:47-271.  Same constructor (``task, model, task_type``,
 ``assert`` on the model name :53-54, ``PubTabNet`` -> ``ptn`` :66-67), same result list: one dict per input image with
@@ -12,8 +12,14 @@ section 8f-4: ResNet-GC backbone + three KV-cached decoders on the engine, label
 ``TableMasterDecoder`` master_decoder.py:532-645): the same backbone, layers and host half without the cell-content decoder (the blob says "0 cell
 classes"; ``TableMasterConvertor``).  ``model="CenterNet"`` (the reference's default: Cycle-CenterNet, ``TableStructureRec``,
 center_net/modeling_table_structure.py:22-47; ``pdf_table_amd/centernet_stage.py``) returns ``polygons`` float32 [n, 8] (shape (0,) when
-empty) and ``inputs`` (OCRTableCenterNetPostProcessor.__call__, processer_centernet.py:170-205) -- no logical locations.  The other
-structure models the reference lists fail loudly.
+empty) and ``inputs`` (OCRTableCenterNetPostProcessor.__call__, processer_centernet.py:170-205) -- no logical locations.
+``model="SLANet"`` (ocr_table_structure_task.py:60-64,139-141,243-247; the one structure model the reference serves through onnxruntime) needs
+``task_path=<dir with model.onnx and table_structure_dict[_ch].txt>``: the graph's feed-forward part runs on the generic executor, its ``Loop`` head as
+one ``pt_op_sla_decode`` launch (``pdf_table_amd/slanet_stage.py``); ``lang`` outside ch / en falls back to en; it returns what
+``SLANetPostProcessor.__call__`` returns (model/slanet/processor_slanet.py:123-148): ``polygons`` (8 values per cell), ``structure_str_list`` (the
+tokens inside the html / body / table tags) and ``inputs``.  Tested on a stand-in graph (tools/onnx_export_slanet.py): the shipped PaddleOCR files
+are not available offline.  There are no in-tree weights for this ONNX-only model, so ``synthetic_seed=`` without a ``task_path`` raises.
+The other structure models the reference lists fail loudly.
 
 Two ways in:
   * reference-shaped: ``task(image_or_list)`` -- path / PIL / ndarray, one table image each;
@@ -47,10 +53,21 @@ class OcrTableStructureTask(BaseInferTask):
     def __init__(self, task="ocr_table_structure", model="CenterNet", engine: HipEngine = None, **kwargs):
         super().__init__(task=task, model=model, **kwargs)
         assert model in _MODELS
-        if model not in ("CenterNet", "Lore", "MtlTabNet", "TableMaster"):
-            raise RuntimeError(f"table-structure model '{model}' is not built on the HIP engine; 'CenterNet', 'Lore', 'MtlTabNet' and "
-                               "'TableMaster' are (SURVEY.md section 8a stage 4, 8f-4)")
+        if model not in ("CenterNet", "SLANet", "Lore", "MtlTabNet", "TableMaster"):
+            raise RuntimeError(f"table-structure model '{model}' is not built on the HIP engine; 'CenterNet', 'Lore', 'MtlTabNet', "
+                               "'TableMaster' and 'SLANet' (ONNX door) are (SURVEY.md section 8a stage 4, 8f-4)")
         self._engine = engine
+        if model == "SLANet":
+            # SLANetConfig (slanet/configuration_slanet.py): lang ch / en (anything else is en), table_max_len 488, merge_no_span_structure True
+            if self.lang not in ("ch", "en"):
+                self.lang = "en"
+            self.model_provider = "PaddleOCR"
+            self._table_max_len = int(kwargs.get("table_max_len", 488))
+            if self._onnx_file() is None:
+                raise RuntimeError("table-structure model 'SLANet' is ONNX-only: there are no in-tree (seeded) weights for it; pass "
+                                   "task_path=<dir with model.onnx and table_structure_dict[_ch].txt> (synthetic_seed= does not apply)")
+            self._get_inference_model()
+            return
         if model == "CenterNet":
             # TableCenterNetConfig / TableStructureRec (center_net/modeling_table_structure.py:22-47): one network, no task types
             self._config = LoreConfig(task_type="wtw")
@@ -82,6 +99,8 @@ class OcrTableStructureTask(BaseInferTask):
             return self._construct_mtl()
         if model == "CenterNet":
             return self._construct_centernet()
+        if model == "SLANet":
+            return self._construct_slanet()
         if self.synthetic_seed is not None:
             from .synth_weights import lore_dla34_state_dict, lore_processor_state_dict, lore_wireless_state_dict
             det_sd = (lore_wireless_state_dict if cfg.backbone == "ResNet-18" else lore_dla34_state_dict)(seed=int(self.synthetic_seed))
@@ -130,6 +149,23 @@ class OcrTableStructureTask(BaseInferTask):
             ck = ck["state_dict"] if "state_dict" in ck else ck
             sd = {str(k).replace("recognizer.", ""): v for k, v in ck.items()}
         self._engine.load_weights(L.PT_MODEL_CENTERNET_DLA34, pack_centernet_dla34(sd, fmt=self._engine.weight_fmt))
+        self._model = self._predict
+
+    def _construct_slanet(self):
+        """model.onnx -> (feed-forward prefix on the generic executor, the Loop head's parameters by data flow); the dictionary next to it"""
+        from .onnx_exec import HipGraphExecutor
+        from .onnx_import import OnnxGraph, split_sla_head
+        from .onnx_proto import parse_model
+        from .rec_postprocess import TableLabelDecode
+        f = self._onnx_file()
+        with open(f, "rb") as fh:
+            prefix, self._sla_head = split_sla_head(parse_model(fh.read()))
+        mp = f if os.path.isdir(f) else os.path.dirname(f)
+        vocab = os.path.join(mp, "table_structure_dict%s.txt" % ("_ch" if self.lang == "ch" else ""))      # SLANetConfig.get_vocab_file
+        if not os.path.exists(vocab):
+            raise RuntimeError(f"no {os.path.basename(vocab)} next to {f}: the SLANet dictionary ships inside the model directory")
+        self._sla_decode = TableLabelDecode(vocab, merge_no_span_structure=True)
+        self._sla_exec = HipGraphExecutor(OnnxGraph(prefix), engine=self._engine, precision=self._exec_precision)
         self._model = self._predict
 
     def _construct_mtl(self):
@@ -181,6 +217,11 @@ class OcrTableStructureTask(BaseInferTask):
             return
         if self.model == "CenterNet":
             self._stage = CenterNetStage(self._engine, micro_batch=int(os.environ.get("PT_TSR_MICROBATCH", "8")))
+            return
+        if self.model == "SLANet":
+            from .slanet_stage import SlaNetStage
+            self._stage = SlaNetStage(self._engine, self._sla_exec, self._sla_head, self._sla_decode, size=self._table_max_len,
+                                      micro_batch=int(os.environ.get("PT_TSR_MICROBATCH", "16")))
             return
         # tables per DLA-34 launch chain: 8-table launches leave most of the 256 CUs idle in the coarse levels (measured
         # with the bench's 80); TsrStage balances the last micro-batch (87 tables -> 44 + 43)
@@ -238,6 +279,10 @@ class OcrTableStructureTask(BaseInferTask):
         if self.model == "CenterNet":
             # OCRTableCenterNetPostProcessor.__call__ (processer_centernet.py:199-205): the polygons and the inputs, no logical locations
             return [{"polygons": r["results"]["polygons"], "inputs": r["inputs"]} for r in inputs["results"]]
+        if self.model == "SLANet":
+            # SLANetPostProcessor.__call__ (slanet/processor_slanet.py:143-148)
+            return [{"polygons": r["results"]["polygons"], "structure_str_list": r["results"]["structure_str_list"], "inputs": r["inputs"]}
+                    for r in inputs["results"]]
         for r in inputs["results"]:
             d = {"polygons": r["results"]["polygons"], "logi": r["results"]["logi"]}
             if r["inputs"] is not None:

@@ -33,9 +33,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from .onnx_proto import OnnxModel, OnnxNode, parse_model
+from .onnx_proto import OnnxModel, OnnxNode, OnnxValueInfo, parse_model
 
-__all__ = ["OnnxGraph", "Layer", "UnsupportedOnnxGraph", "load_onnx", "recognise", "HipOnnxSession", "ENGINE_OPS"]
+__all__ = ["OnnxGraph", "Layer", "UnsupportedOnnxGraph", "load_onnx", "recognise", "HipOnnxSession", "ENGINE_OPS", "split_sla_head", "SlaHeadParams"]
 
 # operators the engine has kernels for (conv_igemm / dwconv / stem / pool / epilogue fusions / lstm / gemm rows ...)
 ENGINE_OPS = {"Conv", "ConvTranspose", "BatchNormalization", "Relu", "Sigmoid", "HardSwish", "HardSigmoid", "PRelu", "Clip",
@@ -513,6 +513,272 @@ def load_onnx(src: Union[str, bytes, os.PathLike]) -> OnnxGraph:
         with open(p, "rb") as f:
             data = f.read()
     return OnnxGraph(parse_model(data))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SLANet: the graph is a feed-forward prefix + ONE Loop (PaddleOCR's SLAHead); the loop runs as pt_op_sla_decode, not node by node
+# ---------------------------------------------------------------------------------------------------------------------
+@dataclass
+class SlaHeadParams:
+    """what split_sla_head reads out of the Loop: the head's parameters by role (pdf_table_amd.weights.SLA_HEAD_ROLES, float32, every matrix
+    [out, in], GRU gates r, z, c), its sizes, the trip count, and the prefix tensor the body reads"""
+    weights: Dict[str, np.ndarray]
+    hidden: int
+    channels: int
+    n_cls: int
+    n_loc: int
+    steps: int
+    feature: str                 # the [B, C, h, w] map the prefix model ends in
+    outputs: Tuple[str, str]     # the graph's output names: (boxes, class probabilities)
+
+
+class _Body:
+    """data-flow view of a Loop body: producer of every tensor, constants, and the small pattern steps the matcher is made of; every failed step
+    raises UnsupportedOnnxGraph naming the node (or tensor) where it failed"""
+
+    def __init__(self, body: OnnxModel):
+        g = OnnxGraph(body)                          # Constant nodes become initializers, Identity nodes are short-circuited
+        self.init, self.nodes = g.init, g.nodes
+        self.outputs = g.graph_outputs
+        self.inputs = [vi.name for vi in body.inputs]
+        self.prod: Dict[str, OnnxNode] = {o: n for n in self.nodes for o in n.outputs}
+
+    def fail(self, what: str, at):
+        where = f"node '{at.name}' ({at.op_type} -> {at.outputs})" if isinstance(at, OnnxNode) else f"tensor '{at}'"
+        raise UnsupportedOnnxGraph(f"SLANet head: {what} at {where}; the accepted Loop body is documented at onnx_import.split_sla_head")
+
+    def node(self, tensor: str, op: Union[str, Tuple[str, ...]], what: str) -> OnnxNode:
+        n = self.prod.get(tensor)
+        ops = (op,) if isinstance(op, str) else op
+        if n is None or n.op_type not in ops:
+            self.fail(f"expected {' / '.join(ops)} producing {what}", n if n is not None else tensor)
+        return n
+
+    def skip(self, tensor: str, ops: Tuple[str, ...]) -> str:
+        """walk back through shape-only / cast nodes"""
+        while tensor in self.prod and self.prod[tensor].op_type in ops:
+            tensor = self.prod[tensor].inputs[0]
+        return tensor
+
+    def linear(self, tensor: str, what: str, bias: bool = True):
+        """tensor = x W^T (+ b) -> (x, W [out, in], b or None): MatMul with a constant [in, out] operand, optionally + Add of a constant; or Gemm with
+        alpha = beta = 1 ([out, in] when transB = 1)"""
+        n = self.prod.get(tensor)
+        b = None
+        if n is not None and n.op_type == "Add":
+            const = [i for i in n.inputs if i in self.init]
+            other = [i for i in n.inputs if i not in self.init]
+            if len(const) != 1 or len(other) != 1:
+                self.fail(f"expected MatMul + constant bias producing {what}", n)
+            b, n = np.asarray(self.init[const[0]], np.float32).reshape(-1), self.prod.get(other[0])
+        if n is None or n.op_type not in ("MatMul", "Gemm"):
+            self.fail(f"expected MatMul / Gemm producing {what}", n if n is not None else tensor)
+        if n.inputs[1] not in self.init or n.inputs[0] in self.init:
+            self.fail(f"expected a constant weight operand producing {what}", n)
+        w = np.asarray(self.init[n.inputs[1]], np.float32)
+        if n.op_type == "Gemm":
+            if float(n.attrs.get("alpha", 1.0)) != 1.0 or float(n.attrs.get("beta", 1.0)) != 1.0 or int(n.attrs.get("transA", 0)) != 0 or b is not None:
+                self.fail(f"Gemm with alpha / beta / transA or a second bias producing {what}", n)
+            w = w if int(n.attrs.get("transB", 0)) else w.T
+            if len(n.inputs) > 2 and n.inputs[2]:
+                if n.inputs[2] not in self.init:
+                    self.fail(f"Gemm with a computed bias producing {what}", n)
+                b = np.asarray(self.init[n.inputs[2]], np.float32).reshape(-1)
+        else:
+            if w.ndim != 2:
+                self.fail(f"MatMul with a {w.ndim}-d weight producing {what}", n)
+            w = w.T
+        if bias and b is None:
+            self.fail(f"expected a bias behind the product producing {what}", n)
+        if not bias and b is not None:
+            self.fail(f"unexpected bias behind the product producing {what}", n)
+        if b is not None and b.size != w.shape[0]:
+            self.fail(f"bias of {b.size} values for {w.shape[0]} outputs producing {what}", n)
+        return n.inputs[0], np.ascontiguousarray(w), b
+
+
+_SHAPE_OPS = ("Unsqueeze", "Squeeze", "Reshape", "Flatten", "Cast")
+
+
+def split_sla_head(model: OnnxModel) -> Tuple[OnnxModel, SlaHeadParams]:
+    """An exported SLANet (PaddleOCR ``SLAHead`` behind a convolutional backbone and neck) -> (prefix_model, SlaHeadParams).
+
+    ``prefix_model`` is the plain feed-forward graph for HipGraphExecutor, ending in the [B, C, h, w] map whose flattened, transposed token rows
+    [B, h w, C] the loop body reads; the head itself runs as ONE pt_op_sla_decode launch (csrc/sla_head.hip).  The body's initialisers are assigned to
+    their roles BY DATA FLOW -- not by name, and not by shape (three matrices are [H, H]).  Accepted pattern (``lin`` = MatMul with a constant
+    [in, out] operand, + Add of a constant where a bias is named; or Gemm with alpha = beta = 1, [out, in] when transB = 1; Identity, Cast, Unsqueeze,
+    Squeeze are looked through where noted):
+
+      outer   exactly one Loop(trip count constant T, cond, h0, prev0): two loop-carried values, two scan outputs
+              tokens = Transpose(perm 0 2 1)(Reshape | Flatten (map [B, C, h, w]))        -- the outer-scope tensor the body reads
+              graph outputs: Transpose(perm 1 0 2) of the Sigmoid scan output (boxes), and Softmax(last axis) of Transpose(perm 1 0 2) of the other
+      body    prev_out = ArgMax(axis 1)(s)                                                 -- the feedback: identifies the id carry and the logits
+              s = lin_b(lin_b(h_out))   [V]   ->  s2, s1                                    -- one scan output (through Identity)
+              loc = Sigmoid(lin_b(lin_b(h_out)))   [L]   ->  l2, l1                         -- the other scan output
+              h_out = Add(Mul(Sub(h_in, c), z), c)                                           -- the hidden carry: h <- (h - c) z + c
+              r = Sigmoid(Add(i_0, h_0)),  z = Sigmoid(Add(i_1, h_1)),  c = Tanh(Add(i_2, Mul(r, h_2)))
+              i_0, i_1, i_2 = Split(axis 1)(lin_b(x))  ->  w_ih, b_ih;   h_0, h_1, h_2 = Split(axis 1)(lin_b(h_in))  ->  w_hh, b_hh
+              x = Concat(axis 1)(ctx, onehot);  onehot = [Cast](OneHot(prev_in, depth V, values (0, 1)))
+              ctx = [Squeeze](MatMul([Transpose(perm 0 2 1)](alpha), tokens));  alpha = Softmax(axis 1)(e)   -- the body's ONLY Softmax
+              e = lin(Tanh(Add(lin(tokens), [Unsqueeze](lin_b(h_in)))))  ->  score_w [1, H] (no bias), i2h_w (no bias), h2h_w, h2h_b
+
+    Raises UnsupportedOnnxGraph naming the node where the match failed."""
+    from .weights import sla_head_dims
+    og = OnnxGraph(model)
+    loops = [n for n in og.nodes if n.op_type == "Loop"]
+    if len(loops) != 1:
+        raise UnsupportedOnnxGraph(f"SLANet head: expected exactly one Loop node, found {len(loops)}")
+    loop = loops[0]
+    body = loop.attrs.get("body")
+    if not isinstance(body, OnnxModel):
+        raise UnsupportedOnnxGraph(f"SLANet head: Loop node '{loop.name}' has no body graph")
+    b = _Body(body)
+    if len(loop.inputs) != 4 or len(b.inputs) != 4 or len(b.outputs) != 5 or len(loop.outputs) != 4:
+        b.fail("expected two loop-carried values and two scan outputs (Loop(M, cond, h0, prev0) -> h, prev, scan, scan)", loop)
+    if loop.inputs[0] not in og.init:
+        b.fail("expected a constant trip count", loop)
+    steps = int(np.asarray(og.init[loop.inputs[0]]).reshape(-1)[0])
+    carried_in, carried_out, scans = b.inputs[2:], b.outputs[1:3], b.outputs[3:]
+    # the feedback: one carried output is an ArgMax
+    amax = [k for k in range(2) if b.prod.get(b.skip(carried_out[k], ("Cast", "Squeeze", "Unsqueeze", "Reshape")), OnnxNode("", [], [])).op_type == "ArgMax"]
+    if len(amax) != 1:
+        b.fail("expected exactly one loop-carried value produced by ArgMax (the id fed back to the next step)", b.prod.get(carried_out[1], carried_out[1]))
+    kp, kh = amax[0], 1 - amax[0]
+    h_in, prev_in, h_out = carried_in[kh], carried_in[kp], carried_out[kh]
+    an = b.prod[b.skip(carried_out[kp], ("Cast", "Squeeze", "Unsqueeze", "Reshape"))]
+    if int(an.attrs.get("axis", 0)) not in (1, -1):
+        b.fail("expected ArgMax over the class axis", an)
+    s = an.inputs[0]
+    P: Dict[str, np.ndarray] = {}
+    x1, P["s2_w"], P["s2_b"] = b.linear(s, "the class logits")
+    x0, P["s1_w"], P["s1_b"] = b.linear(x1, "the structure generator's hidden layer")
+    if x0 != h_out:
+        b.fail("the structure generator does not read the new hidden state", b.prod.get(x1, x1))
+    if s not in scans:
+        b.fail("the logits the ArgMax reads are not a scan output", an)
+    loc = [t for t in scans if t != s][0]
+    sg = b.node(loc, "Sigmoid", "the box scan output")
+    x1, P["l2_w"], P["l2_b"] = b.linear(sg.inputs[0], "the box pre-activations")
+    x0, P["l1_w"], P["l1_b"] = b.linear(x1, "the box generator's hidden layer")
+    if x0 != h_out:
+        b.fail("the box generator does not read the new hidden state", b.prod.get(x1, x1))
+    # h_out = (h_in - c) z + c
+    add = b.node(h_out, "Add", "the new hidden state")
+    mul = [i for i in add.inputs if b.prod.get(i) is not None and b.prod[i].op_type == "Mul"]
+    if len(mul) != 1:
+        b.fail("expected Add(Mul(Sub(h, c), z), c)", add)
+    c = [i for i in add.inputs if i != mul[0]][0]
+    mn = b.prod[mul[0]]
+    sub = [i for i in mn.inputs if b.prod.get(i) is not None and b.prod[i].op_type == "Sub"]
+    if len(sub) != 1 or b.prod[sub[0]].inputs != [h_in, c]:
+        b.fail("expected Mul(Sub(h_in, c), z)", mn)
+    z = [i for i in mn.inputs if i != sub[0]][0]
+    cn = b.node(c, "Tanh", "the candidate state c")
+    ca = b.node(cn.inputs[0], "Add", "the candidate's pre-activation")
+    rm = [i for i in ca.inputs if b.prod.get(i) is not None and b.prod[i].op_type == "Mul"]
+    if len(rm) != 1:
+        b.fail("expected Add(i_c, Mul(r, h_c))", ca)
+    i_c = [i for i in ca.inputs if i != rm[0]][0]
+    rn = b.prod[rm[0]]
+    r = [i for i in rn.inputs if b.prod.get(i) is not None and b.prod[i].op_type == "Sigmoid"]
+    if len(r) != 1:
+        b.fail("expected Mul(r, h_c) with r a Sigmoid", rn)
+    h_c = [i for i in rn.inputs if i != r[0]][0]
+    gates = {}
+    for name, t in (("r", r[0]), ("z", z)):
+        ga = b.node(b.node(t, "Sigmoid", f"gate {name}").inputs[0], "Add", f"the pre-activation of gate {name}")
+        gates[name] = ga
+    splits = [n for n in b.nodes if n.op_type == "Split" and len(n.outputs) == 3]
+    owner = {o: (n, k) for n in splits for k, o in enumerate(n.outputs)}
+    if i_c not in owner or h_c not in owner or owner[i_c][1] != 2 or owner[h_c][1] != 2 or owner[i_c][0] is owner[h_c][0]:
+        b.fail("expected the candidate's two terms to be output 2 of the two three-way gate Splits", ca)
+    isp, hsp = owner[i_c][0], owner[h_c][0]
+    for k, name in ((0, "r"), (1, "z")):
+        if sorted(gates[name].inputs) != sorted([isp.outputs[k], hsp.outputs[k]]):
+            b.fail(f"gate {name} does not add output {k} of the two gate Splits (gate order r, z, c)", gates[name])
+    x, P["w_ih"], P["b_ih"] = b.linear(isp.inputs[0], "the GRU's input gate sums")
+    hx, P["w_hh"], P["b_hh"] = b.linear(hsp.inputs[0], "the GRU's hidden gate sums")
+    if hx != h_in:
+        b.fail("the GRU's hidden projection does not read the carried hidden state", hsp)
+    cat = b.node(x, "Concat", "the GRU input [ctx, onehot]")
+    if len(cat.inputs) != 2:
+        b.fail("expected Concat(ctx, onehot)", cat)
+    oh = b.node(b.skip(cat.inputs[1], ("Cast",)), "OneHot", "the one-hot of the previous id")
+    if b.skip(oh.inputs[0], _SHAPE_OPS) != prev_in:
+        b.fail("the OneHot does not read the carried id", oh)
+    cm = b.node(b.skip(cat.inputs[0], ("Squeeze", "Reshape")), "MatMul", "the attention context")
+    tokens = cm.inputs[1]
+    if tokens in b.prod or tokens in b.init or tokens in b.inputs:
+        b.fail("the context product's second operand is not an outer-scope tensor (the token rows)", cm)
+    softmaxes = [n for n in b.nodes if n.op_type == "Softmax"]
+    sm = b.node(b.skip(cm.inputs[0], ("Transpose", "Reshape", "Squeeze", "Unsqueeze")), "Softmax", "the attention weights")
+    if len(softmaxes) != 1:
+        b.fail(f"expected the attention soft-max to be the body's only Softmax, found {len(softmaxes)}", softmaxes[-1])
+    if int(sm.attrs.get("axis", -1)) != 1:
+        b.fail("expected the attention Softmax over the token axis (1)", sm)
+    tx, sw, _ = b.linear(sm.inputs[0], "the attention scores", bias=False)
+    if sw.shape[0] != 1:
+        b.fail("expected the score product to have one output", sm)
+    P["score_w"] = sw.reshape(-1)
+    pq = b.node(b.node(tx, "Tanh", "the attention hidden layer").inputs[0], "Add", "P + q")
+    side = {}
+    for i in pq.inputs:
+        src = b.skip(i, ("Unsqueeze", "Reshape"))
+        pn = b.prod.get(src)
+        if pn is not None and pn.op_type == "MatMul" and pn.inputs[0] == tokens:
+            side["p"] = src
+        else:
+            side["q"] = src
+    if set(side) != {"p", "q"}:
+        b.fail("expected Add(lin(tokens), lin_b(h_in))", pq)
+    _, P["i2h_w"], _ = b.linear(side["p"], "the token projection P", bias=False)
+    qx, P["h2h_w"], P["h2h_b"] = b.linear(side["q"], "the hidden projection q")
+    if qx != h_in:
+        b.fail("the attention's hidden projection does not read the carried hidden state", b.prod.get(side["q"], side["q"]))
+    try:
+        hidden, channels, n_cls, n_loc = sla_head_dims(P)
+    except ValueError as e:
+        raise UnsupportedOnnxGraph(f"SLANet head: {e}") from None
+    depth = og.init.get(oh.inputs[1], b.init.get(oh.inputs[1]))
+    if depth is None or int(np.asarray(depth).reshape(-1)[0]) != n_cls:
+        b.fail(f"expected a OneHot of depth {n_cls}", oh)
+    # ---- outer graph: tokens <- Transpose <- Reshape / Flatten <- map; outputs
+    prod = {o: n for n in og.nodes for o in n.outputs}
+    tn = prod.get(tokens)
+    if tn is None or tn.op_type != "Transpose" or list(tn.attrs.get("perm", [])) != [0, 2, 1]:
+        b.fail("expected the token rows to be Transpose(perm 0 2 1) of the flattened feature map", tn if tn is not None else tokens)
+    fn = prod.get(tn.inputs[0])
+    if fn is None or fn.op_type not in ("Reshape", "Flatten"):
+        b.fail("expected Reshape / Flatten of the [B, C, h, w] feature map in front of the token Transpose", fn if fn is not None else tn.inputs[0])
+    feature = fn.inputs[0]
+    outs = {}
+    for gi, scan in zip(loop.outputs[2:], scans):
+        cons = [n for n in og.nodes if gi in n.inputs]
+        if len(cons) != 1 or cons[0].op_type != "Transpose" or list(cons[0].attrs.get("perm", [])) != [1, 0, 2]:
+            b.fail("expected each scan output to be made batch-major by Transpose(perm 1 0 2)", cons[0] if cons else loop)
+        t = cons[0].outputs[0]
+        if scan == s:
+            nxt = [n for n in og.nodes if t in n.inputs]
+            if len(nxt) != 1 or nxt[0].op_type != "Softmax" or int(nxt[0].attrs.get("axis", -1)) not in (2, -1):
+                b.fail("expected Softmax over the classes behind the logits scan output", nxt[0] if nxt else cons[0])
+            t = nxt[0].outputs[0]
+        if t not in og.graph_outputs:
+            b.fail("expected the scan output to be a graph output", cons[0])
+        outs[scan] = t
+    # ---- the prefix: every node the feature map depends on
+    need, keep = {feature}, []
+    for n in reversed(model.nodes):
+        if any(o in need for o in n.outputs):
+            keep.append(n)
+            need.update(i for i in n.inputs if i)
+    keep.reverse()
+    if not keep:
+        raise UnsupportedOnnxGraph(f"SLANet head: the feature map '{feature}' is not computed by the graph")
+    prefix = OnnxModel(nodes=keep, initializers={k: v for k, v in model.initializers.items() if k in need}, inputs=list(model.inputs),
+                       outputs=[OnnxValueInfo(feature, 1, ())], opset=model.opset, ir_version=model.ir_version, producer=model.producer,
+                       graph_name=model.graph_name + "_prefix")
+    return prefix, SlaHeadParams(weights={k: np.ascontiguousarray(v, np.float32) for k, v in P.items()}, hidden=hidden, channels=channels, n_cls=n_cls,
+                                 n_loc=n_loc, steps=steps, feature=feature, outputs=(outs[loc], outs[s]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

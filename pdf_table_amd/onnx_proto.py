@@ -11,7 +11,8 @@ Field numbers follow onnx/onnx.proto3 (public schema, ONNX IR version 8):
   ModelProto      1 ir_version, 2 producer_name, 7 graph, 8 opset_import{1 domain, 2 version}
   GraphProto      1 node, 2 name, 5 initializer, 11 input, 12 output
   NodeProto       1 input, 2 output, 3 name, 4 op_type, 5 attribute
-  AttributeProto  1 name, 2 f, 3 i, 4 s, 5 t, 7 floats, 8 ints, 20 type
+  AttributeProto  1 name, 2 f, 3 i, 4 s, 5 t, 6 g, 7 floats, 8 ints, 20 type   (g: a GraphProto -- the body of a Loop / If -- read into a nested
+                  OnnxModel that shares the outer model's opset and ir_version)
   TensorProto     1 dims, 2 data_type, 4 float_data, 5 int32_data, 7 int64_data, 8 name, 9 raw_data
   ValueInfoProto  1 name, 2 type{1 tensor_type{1 elem_type, 2 shape{1 dim{1 dim_value, 2 dim_param}}}}
 """
@@ -30,7 +31,7 @@ DTYPES = {1: np.float32, 2: np.uint8, 3: np.int8, 5: np.int16, 6: np.int32, 7: n
           11: np.float64}
 _DTYPE_ID = {np.dtype(v): k for k, v in DTYPES.items()}
 # AttributeProto.AttributeType
-_AT_FLOAT, _AT_INT, _AT_STRING, _AT_TENSOR, _AT_FLOATS, _AT_INTS = 1, 2, 3, 4, 6, 7
+_AT_FLOAT, _AT_INT, _AT_STRING, _AT_TENSOR, _AT_GRAPH, _AT_FLOATS, _AT_INTS = 1, 2, 3, 4, 5, 6, 7
 
 
 @dataclass
@@ -152,7 +153,7 @@ def _tensor(buf) -> Tuple[str, np.ndarray]:
 
 def _attribute(buf) -> Tuple[str, object]:
     name, atype = "", 0
-    f = i = s = t = None
+    f = i = s = t = g = None
     floats: List[float] = []
     ints: List[int] = []
     for fn, wt, v in _fields(bytes(buf)):
@@ -166,6 +167,8 @@ def _attribute(buf) -> Tuple[str, object]:
             s = bytes(v)
         elif fn == 5:
             t = _tensor(v)[1]
+        elif fn == 6:
+            g = _graph(bytes(v), OnnxModel())
         elif fn == 7:
             floats.extend(np.frombuffer(bytes(v), "<f4").tolist() if wt == 2 else [struct.unpack("<f", struct.pack("<I", v))[0]])
         elif fn == 8:
@@ -180,6 +183,8 @@ def _attribute(buf) -> Tuple[str, object]:
         return name, s.decode("utf-8", "replace")
     if atype == _AT_TENSOR or (atype == 0 and t is not None):
         return name, t
+    if atype == _AT_GRAPH or (atype == 0 and g is not None):
+        return name, g
     if atype == _AT_FLOATS or (atype == 0 and floats):
         return name, [float(x) for x in floats]
     return name, [int(x) for x in ints]
@@ -230,6 +235,33 @@ def _value_info(buf) -> OnnxValueInfo:
     return vi
 
 
+def _graph(buf: bytes, m: OnnxModel) -> OnnxModel:
+    """the fields of a GraphProto into m (the model's own graph, or the nested model of a graph-valued attribute)"""
+    for fn, wt, v in _fields(buf):
+        if fn == 1:
+            m.nodes.append(_node(v))
+        elif fn == 2:
+            m.graph_name = bytes(v).decode()
+        elif fn == 5:
+            k, a = _tensor(v)
+            m.initializers[k] = a
+        elif fn == 11:
+            m.inputs.append(_value_info(v))
+        elif fn == 12:
+            m.outputs.append(_value_info(v))
+    m.inputs = [vi for vi in m.inputs if vi.name not in m.initializers]     # old exporters list initializers as inputs too
+    return m
+
+
+def _subgraphs(m: OnnxModel):
+    """every nested graph of m, depth first"""
+    for n in m.nodes:
+        for a in n.attrs.values():
+            if isinstance(a, OnnxModel):
+                yield a
+                yield from _subgraphs(a)
+
+
 def parse_model(data: bytes) -> OnnxModel:
     """bytes of a ModelProto -> OnnxModel; raises ValueError on anything that is not one"""
     m = OnnxModel()
@@ -253,21 +285,11 @@ def parse_model(data: bytes) -> OnnxModel:
                     m.opset = ver
         if graph is None:
             raise ValueError("no GraphProto (field 7)")
-        for fn, wt, v in _fields(graph):
-            if fn == 1:
-                m.nodes.append(_node(v))
-            elif fn == 2:
-                m.graph_name = bytes(v).decode()
-            elif fn == 5:
-                k, a = _tensor(v)
-                m.initializers[k] = a
-            elif fn == 11:
-                m.inputs.append(_value_info(v))
-            elif fn == 12:
-                m.outputs.append(_value_info(v))
+        _graph(graph, m)
     except (IndexError, struct.error) as e:
         raise ValueError(f"not an ONNX ModelProto: truncated or malformed ({e})") from None
-    m.inputs = [vi for vi in m.inputs if vi.name not in m.initializers]     # old exporters list initializers as inputs too
+    for sub in _subgraphs(m):
+        sub.opset, sub.ir_version = m.opset, m.ir_version
     return m
 
 
@@ -320,6 +342,8 @@ def _enc_attr(name: str, v) -> bytes:
         out += _ld(4, v.encode()) + _key(20, 0) + _enc_varint(_AT_STRING)
     elif isinstance(v, np.ndarray):
         out += _ld(5, _enc_tensor("", v)) + _key(20, 0) + _enc_varint(_AT_TENSOR)
+    elif isinstance(v, OnnxModel):
+        out += _ld(6, _enc_graph(v)) + _key(20, 0) + _enc_varint(_AT_GRAPH)
     elif isinstance(v, (list, tuple)) and v and isinstance(v[0], float):
         out += _ld(7, b"".join(struct.pack("<f", x) for x in v)) + _key(20, 0) + _enc_varint(_AT_FLOATS)
     elif isinstance(v, (list, tuple)):
@@ -337,7 +361,7 @@ def _enc_value_info(vi: OnnxValueInfo) -> bytes:
     return _ld(1, vi.name.encode()) + _ld(2, _ld(1, tensor_type))
 
 
-def serialize_model(m: OnnxModel) -> bytes:
+def _enc_graph(m: OnnxModel) -> bytes:
     g = b""
     for n in m.nodes:
         nb = b"".join(_ld(1, s.encode()) for s in n.inputs) + b"".join(_ld(2, s.encode()) for s in n.outputs)
@@ -349,6 +373,11 @@ def serialize_model(m: OnnxModel) -> bytes:
         g += _ld(5, _enc_tensor(k, a))
     g += b"".join(_ld(11, _enc_value_info(vi)) for vi in m.inputs)
     g += b"".join(_ld(12, _enc_value_info(vi)) for vi in m.outputs)
+    return g
+
+
+def serialize_model(m: OnnxModel) -> bytes:
+    g = _enc_graph(m)
     out = _key(1, 0) + _enc_varint(m.ir_version) + _ld(2, m.producer.encode()) + _ld(7, g)
     out += _ld(8, _ld(1, b"") + _key(2, 0) + _enc_varint(m.opset))
     return out

@@ -73,6 +73,11 @@ class OcrTablePipeline:
                  sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
                  table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
                  rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, **kwargs):
+        if table_structure_model == "SLANet":
+            # served by OcrTableStructureTask(model="SLANet", task_path=...) alone: its result is structure tokens + one box per cell, which the
+            # pipeline's cell / text matching (logical locations) has no route for yet.  Refused here, not on the first page
+            raise ValueError("table_structure_model='SLANet' is out of scope for OcrTablePipeline: use OcrTableStructureTask(model='SLANet', "
+                             "task_path=...) (recognize_tables for resident pages)")
         self.engine = HipEngine(device)
         # image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-468; page_pre_stage.py):
         # deskew=True warps a page back by the angle of its long horizontal rules; page_orientation=True classifies the page with

@@ -29,7 +29,7 @@ import torch
 BN_EPS = 1e-5
 _DT = {"bf16": 0, "f32": 1, "i32": 2}
 
-__all__ = ["pack_db_resnet18", "pack_crnn", "pack_lore_dla34", "pack_centernet_dla34", "pack_lore_processor", "pack_picodet", "pack_lore_wireless", "pack_db_nas", "pack_pplcnet", "pack_convnext_vit", "pack_cvit_mlp", "pack_mtl_backbone", "pack_mtl_decoder", "write_blob", "fold_conv_bn", "to_bf16_bits"]
+__all__ = ["pack_db_resnet18", "pack_crnn", "pack_lore_dla34", "pack_centernet_dla34", "pack_lore_processor", "pack_picodet", "pack_lore_wireless", "pack_db_nas", "pack_pplcnet", "pack_convnext_vit", "pack_cvit_mlp", "pack_mtl_backbone", "pack_mtl_decoder", "pack_sla_head", "write_blob", "fold_conv_bn", "to_bf16_bits"]
 
 
 FORMATS = {"bf16": torch.bfloat16, "f16": torch.float16}      # 16-bit storage formats of the engine (csrc/act16.h): PT_PRECISION_BF16* / PT_PRECISION_F16
@@ -119,6 +119,59 @@ def unpack_lstm_r(packed: np.ndarray, hidden: int, fmt: str = "bf16") -> np.ndar
     out = np.zeros((p.shape[0], 4 * hidden, hidden), np.float32)
     out[:, row[real], col[real]] = vals[:, real]
     return out
+
+
+SLA_HEAD_ROLES = ("i2h_w", "h2h_w", "h2h_b", "score_w", "w_ih", "b_ih", "w_hh", "b_hh", "s1_w", "s1_b", "s2_w", "s2_b", "l1_w", "l1_b", "l2_w", "l2_b")
+
+
+def sla_head_dims(p: Dict[str, np.ndarray]) -> Tuple[int, int, int, int]:
+    """(H, C, V, L) of an SLAHead parameter set (the roles of SLA_HEAD_ROLES, every matrix [out, in]); raises ValueError when the shapes disagree"""
+    missing = [k for k in SLA_HEAD_ROLES if k not in p]
+    if missing:
+        raise ValueError(f"SLAHead parameters without {missing}")
+    s = {k: tuple(np.shape(p[k])) for k in SLA_HEAD_ROLES}
+    hid, c = s["i2h_w"]
+    v, l = s["s2_w"][0], s["l2_w"][0]
+    want = {"i2h_w": (hid, c), "h2h_w": (hid, hid), "h2h_b": (hid,), "score_w": (hid,), "w_ih": (3 * hid, c + v), "b_ih": (3 * hid,), "w_hh": (3 * hid, hid),
+            "b_hh": (3 * hid,), "s1_w": (hid, hid), "s1_b": (hid,), "s2_w": (v, hid), "s2_b": (v,), "l1_w": (hid, hid), "l1_b": (hid,), "l2_w": (l, hid), "l2_b": (l,)}
+    bad = {k: (s[k], want[k]) for k in SLA_HEAD_ROLES if s[k] != want[k]}
+    if bad:
+        raise ValueError(f"SLAHead parameter shapes (have, want): {bad}")
+    return hid, c, v, l
+
+
+def pack_sla_head(p: Dict[str, np.ndarray], fmt: str = "bf16", split: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """SLAHead parameters (SLA_HEAD_ROLES: fp32, every matrix [out, in], GRU gates in the order r, z, c, ``w_ih`` over [ctx(C) | onehot(V)]) -> the two
+    operand images of pt_op_sla_decode (csrc/sla_head.hip):
+      w16  uint16 [halves][n16]: sections, each k-chunk-major [K8 / 8][rows][8] unless stated, K zero-padded to a multiple of 8 --
+           A  [h2h_w ; w_hh ; s1_w ; l1_w]  (6H rows, K = H: everything that multiplies h),  I  w_ih[:, :C]  (3H rows, K = C),
+           COL  w_ih[:, C:]^T as [V][3H]  (the one-hot input is a column read),  P  i2h_w  (H rows, K = C),  S2  s2_w [V][H] and L2  l2_w [L][H] row-major;
+           halves = 2 when ``split``: round16(w) and round16(w - hi)
+      f32  float32 [10H + 72]: [h2h_b ; b_hh ; s1_b ; l1_b] (6H), b_ih (3H), score_w (H), s2_b padded to 64, l2_b padded to 8."""
+    hid, c, v, l = sla_head_dims(p)
+    if hid % 32 or not (32 <= hid <= 256) or not (1 <= c <= 128) or not (1 <= v <= 64) or l not in (4, 8):
+        raise ValueError(f"pack_sla_head: H={hid} C={c} V={v} L={l} is outside the built range of pt_op_sla_decode (H % 32 == 0 up to 256, C <= 128, V <= 64, L 4 or 8)")
+    f = {k: np.asarray(p[k], np.float32) for k in SLA_HEAD_ROLES}
+
+    def kchunk(w):
+        r, k = w.shape
+        k8 = (k + 7) // 8 * 8
+        wp = np.zeros((r, k8), np.float32)
+        wp[:, :k] = w
+        return wp.reshape(r, k8 // 8, 8).transpose(1, 0, 2).reshape(-1)
+
+    full = np.concatenate([kchunk(np.concatenate([f["h2h_w"], f["w_hh"], f["s1_w"], f["l1_w"]], 0)), kchunk(f["w_ih"][:, :c]),
+                           np.ascontiguousarray(f["w_ih"][:, c:].T).reshape(-1), kchunk(f["i2h_w"]), f["s2_w"].reshape(-1), f["l2_w"].reshape(-1)])
+    t = torch.from_numpy(full)
+    halves = split_bf16(t, fmt) if split else (t,)
+    w16 = np.stack([to_bf16_bits(x, fmt) for x in halves], 0)
+    vec = np.zeros(10 * hid + 72, np.float32)
+    vec[:6 * hid] = np.concatenate([f["h2h_b"], f["b_hh"], f["s1_b"], f["l1_b"]])
+    vec[6 * hid:9 * hid] = f["b_ih"]
+    vec[9 * hid:10 * hid] = f["score_w"]
+    vec[10 * hid:10 * hid + v] = f["s2_b"]
+    vec[10 * hid + 64:10 * hid + 64 + l] = f["l2_b"]
+    return w16, vec
 
 
 def tile_conv_weight_f16x2(w: torch.Tensor) -> np.ndarray:
