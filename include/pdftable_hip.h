@@ -656,6 +656,19 @@ int pt_op_sla_scratch_bytes(int B, int N, int H, long long* bytes);
  * d_out fp32 NHWC [n, size, size, 3], channels B, G, R.  No allocation, no host synchronisation (capturable). */
 int pt_slanet_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* d_tables, const pt_tsr_table* h_tables,
                          int n, int size, float* d_out, pt_stream stream);
+/* Text lines -> cells of the tables a pt_op_sla_decode call walked (csrc/table_match.hip, compiled once, engine-free; added under ABI 19: one new entry
+ * point, no existing signature changed, so the version stays): PP-Structure's TableMatch(filter_ocr_result=True).match_result on the device.
+ * d_loc fp32 [B, T, L] (L = 4 or 8), d_ids int32 [B, T], d_steps int32 [B] (NULL: every table has T rows) as the head wrote them; d_cell_flags uint8 [V],
+ * 1 at the cell tokens (TableLabelDecode.td_token).  Row t of table b is a CELL ROW when t < d_steps[b] and its id is flagged.  d_frames fp32 [B, 4] =
+ * (w, h, x0, y0) per table: a cell coordinate is fl32(fl32(loc * w) + x0) at even positions, h and y0 at odd ones (the decode's scaling, then the shift
+ * into page pixels); the cell box is the min / max over the row's points.  d_lines fp32 [M, 4] (min x, min y, max x, max y; 16-byte aligned), grouped by
+ * table: table b owns lines d_offsets[b] .. d_offsets[b + 1] - 1 (int32 [B + 1], non-decreasing, from 0 to M; a line outside every range is not
+ * written, and no index outside [0, M) is ever touched).  d_out int32 [M]: the step index t of the cell row with the smallest (1 - iou, distance, t) --
+ * distance and iou in matcher.py's mixed float32 / float64 arithmetic, the line widened to double (see the kernel's header) -- or -1 when the line's
+ * max(y1, y2) is strictly below the smallest cell y of its table, or the table has no cell row.  1 <= T <= 2048, 1 <= B <= 65535, M >= 0 (0: nothing
+ * is launched).  One launch, no allocation, no host synchronisation (capturable). */
+int pt_op_table_match(const float* d_loc, const int32_t* d_ids, const int32_t* d_steps, int B, int T, int L, const uint8_t* d_cell_flags, int V,
+                      const float* d_frames, const float* d_lines, const int32_t* d_offsets, int M, int32_t* d_out, pt_stream stream);
 
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------

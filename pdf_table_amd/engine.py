@@ -1109,6 +1109,33 @@ class HipEngine:
                                           self._stream()), "pt_op_sla_decode")
         return probs, loc, ids, nsteps
 
+    def op_table_match(self, loc: torch.Tensor, ids: torch.Tensor, steps: Optional[torch.Tensor], cell_flags: torch.Tensor, frames: torch.Tensor,
+                       lines: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        """Text lines -> cell rows of the tables op_sla_decode walked, in one launch (pt_op_table_match, csrc/table_match.hip): TableMatch's
+        _filter_ocr_result + match_result on the device.  loc float32 [B, T, L] / ids int32 [B, T] / steps int32 [B] or None (all T rows): the head's
+        outputs; cell_flags uint8 [V], 1 at the cell tokens; frames float32 [B, 4] = (w, h, x0, y0) per table; lines float32 [M, 4] grouped by table
+        and offsets int32 [B + 1] (0 .. M, non-decreasing) -> int32 [M]: per line the step index t of its cell row, -1 for a line the y filter drops
+        or a table without a cell row.  Everything stays on the device; nothing synchronises."""
+        self._chk(loc, torch.float32, "loc")
+        self._chk(ids, torch.int32, "ids")
+        self._chk(cell_flags, torch.uint8, "cell_flags")
+        self._chk(frames, torch.float32, "frames")
+        self._chk(lines, torch.float32, "lines")
+        self._chk(offsets, torch.int32, "offsets")
+        if steps is not None:
+            self._chk(steps, torch.int32, "steps")
+        if loc.dim() != 3 or tuple(ids.shape) != tuple(loc.shape[:2]):
+            raise ValueError(f"op_table_match: loc must be [B, T, L] and ids [B, T], got {tuple(loc.shape)} and {tuple(ids.shape)}")
+        B, T, L_ = loc.shape
+        M = lines.numel() // 4
+        if lines.numel() != 4 * M or frames.numel() != 4 * B or offsets.numel() != B + 1 or (steps is not None and steps.numel() != B):
+            raise ValueError(f"op_table_match: {B} tables need frames [B, 4], offsets [B + 1], steps [B] and lines [M, 4]; got {tuple(frames.shape)}, "
+                             f"{tuple(offsets.shape)}, {None if steps is None else tuple(steps.shape)}, {tuple(lines.shape)}")
+        out = torch.empty((M,), dtype=torch.int32, device=self._tdev)
+        L.check(self.lib.pt_op_table_match(_ptr(loc), _ptr(ids), _ptr(steps), B, T, L_, _ptr(cell_flags), cell_flags.numel(), _ptr(frames), _ptr(lines),
+                                           _ptr(offsets), M, _ptr(out), self._stream()), "pt_op_table_match")
+        return out
+
     def op_attention(self, qkv: torch.Tensor, heads: int, d: int, scale: float, out_c: int, split: bool = False) -> torch.Tensor:
         """qkv bf16 [B, 1, T, >= 3 heads d] rows of [q | k | v] -> bf16 [B, 1, T, out_c] (channels heads * d .. out_c are zero); split: both tensors
         carry [hi | lo] halves of that width"""

@@ -73,11 +73,14 @@ class OcrTablePipeline:
                  sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
                  table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
                  rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, **kwargs):
-        if table_structure_model == "SLANet":
-            # served by OcrTableStructureTask(model="SLANet", task_path=...) alone: its result is structure tokens + one box per cell, which the
-            # pipeline's cell / text matching (logical locations) has no route for yet.  Refused here, not on the first page
-            raise ValueError("table_structure_model='SLANet' is out of scope for OcrTablePipeline: use OcrTableStructureTask(model='SLANet', "
-                             "task_path=...) (recognize_tables for resident pages)")
+        if table_structure_model == "SLANet" and not tsr_task_path:
+            # the ONNX-only model has no in-tree (seeded) weights: without its directory there is nothing to serve.  Refused here, before any
+            # engine exists, not on the first page
+            raise ValueError("table_structure_model='SLANet' without tsr_task_path=<dir with model.onnx and table_structure_dict[_ch].txt> is out "
+                             "of scope for OcrTablePipeline: the model is ONNX-only, there are no seeded weights for it")
+        # which route _attach_html takes for results without logical locations (tokens + one box per cell): SLANet's lines are matched on the
+        # device by its stage, MtlTabNet / TableMaster on the host with use_master (tsr_match_need_use_master)
+        self.table_structure_model = table_structure_model
         self.engine = HipEngine(device)
         # image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-468; page_pre_stage.py):
         # deskew=True warps a page back by the angle of its long horizontal rules; page_orientation=True classifies the page with
@@ -171,6 +174,8 @@ class OcrTablePipeline:
                 tk["synthetic_seed"] = synthetic_seed + 2
             if tsr_task_path:
                 tk["task_path"] = tsr_task_path
+            if table_structure_model == "SLANet":      # no seeded weights: the file is served, beside seeded stages of the same pipeline (``lang`` rides in kwargs)
+                tk.pop("synthetic_seed", None)
             self.table_structure_task = OcrTableStructureTask(model=table_structure_model, engine=self.engine,
                                                               task_type=table_structure_task_type, **tk)
 
@@ -193,7 +198,10 @@ class OcrTablePipeline:
         self.text_recognizer = types.SimpleNamespace(_stage=rec_stage)
         self.layout_task = None if layout_stage is None else types.SimpleNamespace(_stage=layout_stage, detect_pages=layout_stage)
         self.table_structure_task = None if tsr_stage is None else types.SimpleNamespace(
-            _stage=tsr_stage, recognize_tables=lambda pages, boxes, page_frame=True: tsr_stage(pages, boxes, page_frame=page_frame))
+            _stage=tsr_stage, recognize_tables=lambda pages, boxes, page_frame=True, **kw: tsr_stage(pages, boxes, page_frame=page_frame, **kw))
+        # the token route's model name (_attach_html): SLANet by its stage; a stage with a label convertor is MtlTabNet / TableMaster
+        from .slanet_stage import SlaNetStage
+        self.table_structure_model = "SLANet" if isinstance(tsr_stage, SlaNetStage) else "MtlTabNet" if hasattr(tsr_stage, "convertor") else None
         if orientation_stage is not None:
             def lines(pages, quads_per_page, st=orientation_stage):       # ClsImagePulcTask.lines
                 res = st.lines(pages, build_lines(quads_per_page))
@@ -323,7 +331,7 @@ class OcrTablePipeline:
                 else:
                     tb = self._layout_table_boxes(lay)
                 with stage_range("table_structure"):
-                    tsr = self.table_structure_task.recognize_tables(batch, tb)
+                    tsr = self.table_structure_task.recognize_tables(batch, tb, **self._match_on_device(boxes))
             if side is not None:
                 with stage_range("text_recognition"):
                     texts = finish_rec()
@@ -663,7 +671,9 @@ class OcrTablePipeline:
                     # synchronisation) for its successor (measured: 443-462 -> pages/s of the private loop)
                 st["tsr"] = (pending, metas, offs, ev)
 
-        staged_tsr = tsr_stage is not None and hasattr(tsr_stage, "start")      # Lore: start / process / collect; MtlTabNet: one synchronous call
+        # Lore / CenterNet: start / process / collect; MtlTabNet: one synchronous call; SLANet (start / finish only) goes the synchronous way too, in
+        # collect(), where the batch's text boxes are known and its lines can be matched on the device
+        staged_tsr = tsr_stage is not None and hasattr(tsr_stage, "start") and hasattr(tsr_stage, "process")
         tsr_on_aux = bool(getattr(self, "tsr_on_aux", False))
 
         def process_tables(st):
@@ -703,7 +713,7 @@ class OcrTablePipeline:
                 ts = self._table_stream
                 with torch.cuda.stream(ts):
                     ts.wait_event(st["uploaded"])
-                    tsr = tsr_stage(st["pages"], tb, page_frame=True)
+                    tsr = tsr_stage(st["pages"], tb, page_frame=True, **self._match_on_device(st["boxes"]))
                 st["pages"].record_stream(ts)
             elif tsr_stage is not None:
                 pending, metas, offs, ev = st["tsr"]
@@ -832,11 +842,40 @@ class OcrTablePipeline:
             self.metric["gpu_ms_inside_phases"] = busy         # device time between the first and the last launch of a phase
             self.metric["gpu_ms_between_phases"] = idle        # device time between two phases' launches: the queue was empty (or copies ran)
 
+    def _match_on_device(self, boxes) -> dict:
+        """table_html with SLANet: the stage matches every table's lines to its cells on the device (SlaNetStage, pt_op_table_match) and needs
+        the pages' text boxes for it; every other model: nothing more to pass"""
+        if not (self.table_html and getattr(self, "table_structure_model", None) == "SLANet"):
+            return {}
+        from .table_text_match import text_boxes
+        return {"text_boxes": [text_boxes(b) if len(b) else np.zeros((0, 4)) for b in boxes]}
+
     def _attach_html(self, tsr, tb, boxes, texts):
-        """cells (page pixels since the stage shifts them) x the page's text lines (page pixels) -> HTML per table"""
-        from .table_text_match import page_table_html
+        """cells (page pixels since the stage shifts them) x the page's text lines (page pixels) -> HTML per table.  The reference's two routes
+        (ocr_table_to_html_task.py:139-156): a result with logical locations (Lore) goes through the cell / text matching of table_text_match.py; a
+        result of structure tokens + one box per cell ("not_spit_text": SLANet, MtlTabNet, TableMaster) through TableMatch
+        (table_structure_match.py) -- SLANet with the match map its stage computed on the device and use_master False, MtlTabNet / TableMaster
+        (polygons made on the host) with the numpy match and use_master True; table_html is then a one-string list and db_table_html equal to it"""
+        from .table_text_match import page_table_html, text_boxes, texts_in_table
+        from .table_structure_match import structure_table_html, use_master_for
+        model = getattr(self, "table_structure_model", None)
         for k in range(len(tsr)):
+            tbx = None
             for ti, table in enumerate(tsr[k]):
+                if "structure_str_list" in table and "logi" not in table:
+                    if model == "SLANet":
+                        if "matched" not in table:
+                            raise RuntimeError("table_html with SLANet needs the stage's 'matched' map (SlaNetStage(..., text_boxes=...)): there is no "
+                                               "host route for it")
+                        html = structure_table_html(table["structure_str_list"], table["polygons"], None, texts[k], False, matched=table["matched"])
+                    else:
+                        if tbx is None:
+                            tbx = text_boxes(boxes[k]) if len(boxes[k]) else np.zeros((0, 4))
+                        inside = texts_in_table([float(v) for v in tb[k][ti]], tbx, diff=2) if len(tbx) else np.zeros(0, np.int64)
+                        html = structure_table_html(table["structure_str_list"], table["polygons"], tbx[inside], [texts[k][i] for i in inside],
+                                                    use_master_for(model))
+                    table["table_html"], table["db_table_html"] = html, html
+                    continue
                 if len(table.get("scores", [])) == 0:
                     table["table_html"], table["db_table_html"] = [], []
                     continue

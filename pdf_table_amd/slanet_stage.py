@@ -14,10 +14,13 @@ Replaces, for a batch of table crops of resident pages, the reference's per-tabl
   * host: ``TableLabelDecode.decode_ids`` and ``slanet_shape_result`` (pdf_table_amd/rec_postprocess.py).
 
 Stage contract as ``CenterNetStage``: ``stage(pages, boxes_per_page, page_frame=...)`` -> per page, per table the reference's dict
-(``polygons``, ``structure_str_list``, plus ``score``)."""
+(``polygons``, ``structure_str_list``, plus ``score``).  With ``text_boxes=`` (the pages' recognised lines, page pixels) every table also gets
+``"matched"``: {cell ordinal: [indices of the page's lines, in page order]} -- ``TableMatch(filter_ocr_result=True)``'s filter and ``match_result`` over
+the table's candidate lines, computed by ONE ``pt_op_table_match`` launch per micro-batch on the head's outputs while they are still on the device
+(csrc/table_match.hip; pdf_table_amd/table_structure_match.py is the same arithmetic in numpy and what the tests compare with)."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -25,6 +28,7 @@ import torch
 from .engine import TSR_TABLE_DTYPE, HipEngine
 from .onnx_import import SlaHeadParams, UnsupportedOnnxGraph
 from .rec_postprocess import TableLabelDecode, slanet_shape_result
+from .table_text_match import texts_in_table
 from .weights import pack_sla_head
 
 __all__ = ["SlaNetStage", "slanet_resized_size", "slanet_shape_list"]
@@ -55,6 +59,10 @@ class SlaNetStage:
         w16, vec = pack_sla_head(head.weights, fmt=executor.fmt, split=executor.split)
         self._w16 = torch.from_numpy(w16.view(np.int16)).to(eng._tdev)
         self._f32 = torch.from_numpy(vec).to(eng._tdev)
+        # 1 at the tokens that own a box (TableLabelDecode.td_token): what pt_op_table_match calls a cell row
+        self._cell_flags_host = np.zeros(len(decode.character), np.uint8)
+        self._cell_flags_host[[decode.dict[t] for t in decode.td_token if t in decode.dict]] = 1
+        self._cell_flags = torch.from_numpy(self._cell_flags_host).to(eng._tdev)
 
     def tables(self, page_shape: Tuple[int, int], boxes_per_page: Sequence[np.ndarray]) -> np.ndarray:
         """integer table boxes [k, 4] (x1, y1, x2, y2) per page, cropped like crop_image_by_box (img[y1:y2, x1:x2]) -> pt_tsr_table records"""
@@ -71,10 +79,24 @@ class SlaNetStage:
                 recs.append(r)
         return np.array(recs, dtype=TSR_TABLE_DTYPE) if recs else np.zeros(0, dtype=TSR_TABLE_DTYPE)
 
-    def start(self, pages: torch.Tensor, tables: np.ndarray):
-        """device half, nothing synchronises: per micro-batch pre-process -> prefix graph -> one head launch -> one copy to pinned memory"""
+    def candidate_lines(self, tables: np.ndarray, text_boxes: Sequence[np.ndarray]) -> List[np.ndarray]:
+        """per table the indices (ascending = page order) of its page's text lines whose rounded centre lies in the crop grown by 2 pixels
+        (get_text_in_table_bbox, diff = 2): the lines the reference hands to TableMatch"""
+        out = []
+        for r in tables:
+            tb = np.asarray(text_boxes[int(r["page"])], np.float64).reshape(-1, 4)
+            x0, y0 = float(r["x0"]), float(r["y0"])
+            out.append(texts_in_table((x0, y0, x0 + float(r["crop_w"]), y0 + float(r["crop_h"])), tb, diff=2) if len(tb) else np.zeros(0, np.int64))
+        return out
+
+    def start(self, pages: torch.Tensor, tables: np.ndarray, text_boxes: Optional[Sequence[np.ndarray]] = None):
+        """device half, nothing synchronises: per micro-batch pre-process -> prefix graph -> one head launch -> one copy to pinned memory.
+        text_boxes (per page [t, 4] = (min x, min y, max x, max y) in page pixels, table_text_match.text_boxes): the lines of every table are
+        matched to its cells on the device as well -- candidates chosen here on the host, their boxes, the per-table offsets and frames uploaded in ONE
+        pinned non-blocking copy, one pt_op_table_match launch behind the head, its [lines] int32 riding on the same copy back"""
         hd, ex = self.head, self.exec
         T, L = hd.steps, hd.n_loc
+        cand = self.candidate_lines(tables, text_boxes) if text_boxes is not None else None
         pending = []
         for i in range(0, len(tables), self.micro_batch):
             tb = tables[i:i + self.micro_batch]
@@ -89,27 +111,45 @@ class SlaNetStage:
             probs, loc, ids, steps = self.eng.op_sla_decode(fea, hd.channels, self._w16, self._f32, hd.hidden, hd.n_cls, hd.n_loc, T,
                                                             eos_id=self.decode.end_idx, split=ex.split)
             chosen = probs.gather(2, ids.long().unsqueeze(-1)).squeeze(-1)
-            dev = torch.cat([ids.reshape(-1), steps, chosen.reshape(-1).view(torch.int32), loc.reshape(-1).view(torch.int32)])
+            parts = [ids.reshape(-1), steps, chosen.reshape(-1).view(torch.int32), loc.reshape(-1).view(torch.int32)]
+            lines_of = up = None
+            if cand is not None:
+                lines_of = cand[i:i + n]
+                offs = np.zeros(n + 1, np.int32)
+                offs[1:] = np.cumsum([len(c) for c in lines_of])
+                m = int(offs[-1])
+                # the decode's scaling (x times the crop's width, y times its height) and the page-frame shift, per table
+                frames = np.stack([tb["crop_w"], tb["crop_h"], tb["x0"], tb["y0"]], 1).astype(np.float32)
+                boxes = [np.asarray(text_boxes[int(r["page"])], np.float64).reshape(-1, 4)[c] for r, c in zip(tb, lines_of)]
+                buf = np.concatenate([np.concatenate(boxes).astype(np.float32).reshape(-1).view(np.int32), offs, frames.reshape(-1).view(np.int32)])
+                up = torch.from_numpy(buf).pin_memory().to(self.eng._tdev, non_blocking=True)
+                parts.append(self.eng.op_table_match(loc, ids, steps, self._cell_flags, up[4 * m + n + 1:].view(torch.float32).reshape(n, 4),
+                                                     up[:4 * m].view(torch.float32).reshape(m, 4), up[4 * m:4 * m + n + 1]))
+            dev = torch.cat(parts)
             host = torch.empty(dev.shape, dtype=torch.int32, pin_memory=True)
             host.copy_(dev, non_blocking=True)
             done = torch.cuda.Event()
             done.record()
-            pending.append((i, n, host, done, dev))            # dev: alive until finish() has seen the copy
+            pending.append((i, n, host, done, (dev, up), lines_of))      # dev, up: alive until finish() has seen the copy
         return pending
 
     def finish(self, pending, tables: np.ndarray, page_frame: bool = False) -> List[Dict]:
         T, L = self.head.steps, self.head.n_loc
         out: List[Dict] = []
-        for (i, n, host, done, _dev) in pending:
+        for (i, n, host, done, _dev, lines_of) in pending:
+            if lines_of is not None and not page_frame:
+                raise ValueError("SlaNetStage: text lines are matched in page pixels: text_boxes needs page_frame=True")
             done.synchronize()                                 # THAT copy, not whatever has been queued on the stream since
             h = host.numpy()
             ids, steps = h[:n * T].reshape(n, T), h[n * T:n * T + n]
             o = n * T + n
             chosen = h[o:o + n * T].view(np.float32).reshape(n, T)
-            loc = h[o + n * T:].view(np.float32).reshape(n, T, L)
+            loc = h[o + n * T:o + n * T + n * T * L].view(np.float32).reshape(n, T, L)
+            match = h[o + n * T + n * T * L:]
             tb = tables[i:i + n]
             shapes = np.stack([slanet_shape_list(int(r["crop_h"]), int(r["crop_w"]), self.size) for r in tb])
             res = self.decode.decode_ids(ids, chosen, loc, shapes, steps)
+            m0 = 0
             for k in range(n):
                 toks, score = res["structure_batch_list"][k]
                 d = slanet_shape_result(toks, res["bbox_batch_list"][k])
@@ -118,13 +158,23 @@ class SlaNetStage:
                 if page_frame and len(d["polygons"]):
                     off = np.tile(np.array([tb[k]["x0"], tb[k]["y0"]], d["polygons"].dtype), d["polygons"].shape[1] // 2)
                     d["polygons"] = d["polygons"] + off[None]
+                if lines_of is not None:
+                    # step index -> cell ordinal (the k-th cell row is the k-th polygon), line position -> index of the line on its page
+                    ordinal = np.cumsum(self._cell_flags_host[ids[k, :int(steps[k])]]) - 1
+                    matched: Dict[int, List[int]] = {}
+                    for line, t in zip(lines_of[k].tolist(), match[m0:m0 + len(lines_of[k])].tolist()):
+                        if t >= 0:
+                            matched.setdefault(int(ordinal[t]), []).append(line)
+                    m0 += len(lines_of[k])
+                    d["matched"] = matched
                 out.append(d)
         self.eng.check()                                       # the batch has executed: surface device-side failures of it
         return out
 
-    def __call__(self, pages: torch.Tensor, boxes_per_page: Sequence[np.ndarray], page_frame: bool = False) -> List[List[Dict]]:
+    def __call__(self, pages: torch.Tensor, boxes_per_page: Sequence[np.ndarray], page_frame: bool = False,
+                 text_boxes: Optional[Sequence[np.ndarray]] = None) -> List[List[Dict]]:
         tables = self.tables(tuple(pages.shape[1:3]), boxes_per_page)
-        flat = self.finish(self.start(pages, tables), tables, page_frame) if len(tables) else []
+        flat = self.finish(self.start(pages, tables, text_boxes), tables, page_frame) if len(tables) else []
         res, o = [], 0
         for b in boxes_per_page:
             k = len(np.asarray(b).reshape(-1, 4))
