@@ -623,6 +623,22 @@ int pt_op_db_tail(pt_engine* e, const uint16_t* d_in, int B, int H, int W, int C
  * multiple of 8 and d_in is 16-byte aligned, 2-byte loads otherwise; any rows >= 1 and c >= 1.  No allocation, no host synchronisation (capturable). */
 int pt_op_ctc_greedy(pt_engine* e, const uint16_t* d_in, long long rows, int c_pad, int c, int32_t* d_ids, float* d_conf, int split, pt_stream stream);
 
+/* The tail of a PicoDet ONNX export in one launch (csrc/layout_ops.hip; added under ABI 19: one new entry point, no existing signature changed, so the
+ * version stays).  Input: the 2 L output activations of the graph as the ONNX executor holds them, 1 <= levels <= 4: h_scores[l] token rows of 16-bit class
+ * PROBABILITIES [B, h_anchors[l], c_pad_s] with the first ncls channels real, h_dists[l] box-distribution logits [B, h_anchors[l], c_pad_d] with the first
+ * 32 channels real ([hi(c_pad) | lo(c_pad)] rows of twice that width when split, value = hi + lo as one fp32 add; float(hi) otherwise).  h_scores,
+ * h_dists and h_anchors are HOST arrays of `levels` device pointers / anchor counts; they are read before the call returns.  Padding channels may hold
+ * anything and are never loaded.  An anchor is a candidate when the fp32 maximum of its ncls values is > thr_lo (strict).  Output, as pt_layout_candidates:
+ *   d_counts : int32 [B]       candidates of each page -- every one, also beyond max_cands (zeroed here on the stream: calls do not accumulate)
+ *   d_cands  : float32 [B, max_cands, PT_LAYOUT_CAND_FLOATS]   the first max_cands arrivals of a page, in no defined order: (int32 level, int32 anchor,
+ *              ncls class probabilities, 32 distribution logits, zeros up to 48); nothing is written outside a page's slab or past its stored records
+ * ncls + 32 <= PT_LAYOUT_CAND_FLOATS - 2, i.e. ncls <= 14 (PT_ERR_INVALID otherwise, nothing is launched); B <= 65535.  The values are converted and
+ * copied only: sigmoid, soft-max and box arithmetic stay with the caller.  One atomic per wave and page, records written 48 floats at a time by the wave;
+ * one launch for all levels and pages, no allocation and no host synchronisation (capturable). */
+int pt_op_pico_candidates(pt_engine* e, const uint16_t* const* h_scores, const uint16_t* const* h_dists, const int32_t* h_anchors, int levels, int B,
+                          int c_pad_s, int c_pad_d, int ncls, float thr_lo, int max_cands, int32_t* d_counts, float* d_cands, int split,
+                          pt_stream stream);
+
 /* PaddleOCR's SLAHead, the table-structure head of SLANet, as one launch (csrc/sla_head.hip; added under ABI 19: three new entry points, no existing
  * signature changed, so the version stays).  The head is an ONNX Loop in the exported graph: an attention-GRU cell walked T times with the arg-max of
  * step t fed back as the one-hot input of step t + 1 (SLAHead.forward in eval mode + AttentionGRUCell).

@@ -30,6 +30,18 @@ from .ocr_table_model_config import TABLE_MODEL_DICT
 __all__ = ["BaseInferTask"]
 
 
+def onnx_file_under(path):
+    """model.onnx / fp16_model.onnx / inference.onnx under ``path``, or ``path`` itself if it is an .onnx file; None otherwise"""
+    if not path:
+        return None
+    if os.path.isfile(path) and str(path).endswith(".onnx"):
+        return path
+    for cand in ("model.onnx", "fp16_model.onnx", "inference.onnx"):
+        if os.path.isfile(os.path.join(path, cand)):
+            return os.path.join(path, cand)
+    return None
+
+
 class BaseInferTask(metaclass=ABCMeta):
     def __init__(self, model, task, priority_path=None, **kwargs):
         self.model = model
@@ -189,12 +201,7 @@ class BaseInferTask(metaclass=ABCMeta):
         tp = getattr(self, "_task_path", None)
         if not tp or self.synthetic_seed is not None:
             return None
-        if os.path.isfile(tp) and str(tp).endswith(".onnx"):
-            return tp
-        for cand in ("model.onnx", "fp16_model.onnx", "inference.onnx"):
-            if os.path.isfile(os.path.join(tp, cand)):
-                return os.path.join(tp, cand)
-        return None
+        return onnx_file_under(tp)
 
     # ---- run -----------------------------------------------------------------------------------------
     def __call__(self, *args, **kwargs):

@@ -20,7 +20,7 @@ STAMP = LIB + ".stamp"
 
 HIP_SOURCES = ["conv_igemm.hip", "det_kernels.hip", "db_model.hip", "rec_kernels.hip", "crnn_model.hip",
                "lore_kernels.hip", "lore_model.hip", "lore_decode.hip", "centernet_model.hip", "centernet_decode.hip", "lore_processor.hip", "layout_kernels.hip", "layout_model.hip", "dbnas_model.hip", "cls_kernels.hip",
-               "graph_ops.hip", "rect_ops.hip", "large_conv.hip", "det_ops.hip", "ctc_ops.hip", "sla_head.hip", "lstm_op.hip", "cvit_model.hip", "mtl_model.hip", "mtl_decoder.hip", "c_api.hip"]
+               "graph_ops.hip", "rect_ops.hip", "large_conv.hip", "det_ops.hip", "ctc_ops.hip", "layout_ops.hip", "sla_head.hip", "lstm_op.hip", "cvit_model.hip", "mtl_model.hip", "mtl_decoder.hip", "c_api.hip"]
 # compiled ONCE: host-only post-processing and the format-independent corner of the ABI
 CPP_SOURCES = ["db_post.cpp", "api_common.cpp"]
 # HIP compiled ONCE (as namespace pt_bf16): kernels on uint8 pages (page_pre) or fp32 / int32 arrays (table_match) only, no activation format; their entry points take no engine, so the

@@ -1054,6 +1054,44 @@ class HipEngine:
         L.check(self.lib.pt_op_ctc_greedy(self._h, _ptr(x), rows, cp, int(c), _ptr(ids), _ptr(conf), int(split), self._stream()), "pt_op_ctc_greedy")
         return ids, conf
 
+    def op_pico_candidates(self, scores, dists, ncls: int, thr_lo: float, max_cands: int = 2048, split: bool = False, out=None):
+        """The 2 L outputs of a PicoDet export -> candidate records (pt_op_pico_candidates, csrc/layout_ops.hip).  scores / dists: per level the
+        16-bit token rows [B, 1, A_l, Cp] ([hi | lo] when split) of class probabilities (ncls real channels) and distribution logits (32 real
+        channels) -> (counts int32 [B], cands float32 [B, max_cands, 48]) on the device: the anchors whose largest class value is > thr_lo as
+        (int32 level, int32 anchor, ncls probabilities, 32 logits, zeros), values converted (hi + lo in fp32 when split) and copied only.
+        counts reports every candidate, cands holds the first max_cands arrivals; a page's slab past its records is left as it was.
+        out: (counts, cands) to write into instead of new tensors."""
+        scores, dists = list(scores), list(dists)
+        if len(scores) != len(dists) or not scores:
+            raise ValueError(f"op_pico_candidates: {len(scores)} score tensors and {len(dists)} distribution tensors")
+        m = 2 if split else 1
+        B = int(scores[0].shape[0])
+        anchors = []
+        for sc, bd in zip(scores, dists):
+            self._chk(sc, self.act_dtype, "scores")
+            self._chk(bd, self.act_dtype, "dists")
+            a = sc.numel() // (B * sc.shape[-1])
+            if sc.shape[0] != B or bd.shape[0] != B or bd.numel() // (B * bd.shape[-1]) != a or sc.shape[-1] != scores[0].shape[-1] \
+                    or bd.shape[-1] != dists[0].shape[-1]:
+                raise ValueError(f"op_pico_candidates: level shapes {tuple(sc.shape)} / {tuple(bd.shape)} do not pair up, or differ in width from level 0")
+            anchors.append(a)
+        n = len(scores)
+        if out is None:
+            counts = torch.empty((B,), dtype=torch.int32, device=self._tdev)
+            cands = torch.empty((B, int(max_cands), L.PT_LAYOUT_CAND_FLOATS), dtype=torch.float32, device=self._tdev)
+        else:
+            counts, cands = out
+            self._chk(counts, torch.int32, "counts")
+            self._chk(cands, torch.float32, "cands")
+            if counts.numel() < B or cands.numel() < B * int(max_cands) * L.PT_LAYOUT_CAND_FLOATS:
+                raise ValueError("op_pico_candidates: output buffers too small")
+        h_s = (C.c_void_p * n)(*[t.data_ptr() for t in scores])
+        h_d = (C.c_void_p * n)(*[t.data_ptr() for t in dists])
+        h_a = (C.c_int * n)(*anchors)
+        L.check(self.lib.pt_op_pico_candidates(self._h, h_s, h_d, h_a, n, B, scores[0].shape[-1] // m, dists[0].shape[-1] // m, int(ncls), float(thr_lo),
+                                               int(max_cands), _ptr(counts), _ptr(cands), int(split), self._stream()), "pt_op_pico_candidates")
+        return counts, cands
+
     def slanet_preprocess(self, pages: torch.Tensor, tables: np.ndarray, size: int = 488) -> torch.Tensor:
         """SLANetPreprocessor on resident pages (pt_slanet_preprocess): pages uint8 [n_pages, h, w, 3], tables TSR_TABLE_DTYPE records (page, x0, y0,
         crop_w, crop_h) -> float32 NHWC [n, size, size, 3] in B, G, R order, zero-padded at the bottom and the right"""

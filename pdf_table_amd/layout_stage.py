@@ -19,7 +19,7 @@ from .streams import shared_stream
 from . import lib as L
 from .engine import HipEngine
 
-__all__ = ["PicodetConfig", "LayoutStage", "hard_nms", "layout_tables", "LAYOUT_LABELS"]
+__all__ = ["PicodetConfig", "LayoutStage", "OnnxLayoutStage", "hard_nms", "layout_tables", "LAYOUT_LABELS"]
 
 LAYOUT_LABELS = {   # configuration_picodet.py:66-104
     "ch": ["text", "title", "figure", "figure_caption", "table", "table_caption", "header", "footer", "reference", "equation"],
@@ -113,6 +113,10 @@ class LayoutStage:
         with self.eng.precision_scope(self.precision):
             counts, cands = self.eng.layout_forward(pages, cfg.img_height, cfg.img_width, len(cfg.labels),
                                                     thr_lo=cfg.score_threshold - 1e-3, max_cands=self.max_cands)
+        return self._land(counts, cands, landing)
+
+    def _land(self, counts: torch.Tensor, cands: torch.Tensor, landing=None):
+        """counts / records written on the current stream -> their copy into a pinned landing buffer on the copy stream behind an event: (n, ticket)"""
         n = counts.shape[0]
         if self._copy_stream is None:
             self._copy_stream = shared_stream(counts.device, "layout_copy")
@@ -250,4 +254,88 @@ class LayoutStage:
             raise RuntimeError(f"layout: {int(counts.max())} candidate anchors on a page exceed max_cands={self.max_cands}")
         kmax = int(counts.max()) if len(counts) else 0
         rec = host[1][:n, :max(kmax, 1)].numpy()
-        return [self.decode_page(rec[i, :counts[i]], org) for i in range(len(counts))]
+        return [self._decode_record_page(rec[i, :counts[i]], org) for i in range(len(counts))]
+
+    def _decode_record_page(self, rec: np.ndarray, org) -> List[Dict]:
+        """one page's landed records -> its result list (the in-tree head hands back class LOGITS)"""
+        return self.decode_page(rec, org)
+
+
+class OnnxLayoutStage(LayoutStage):
+    """A LayoutStage whose device half is a PicoDet ONNX export walked by ``HipGraphExecutor`` (the reference's layout stage is ONNX-only,
+    ocr_layout_task.py:82-123): same contract -- ``forward(pages, landing=None) -> (n, ticket)``, ``finish(n, ticket, org)``, ``__call__`` -- so
+    ``OcrTablePipeline.predict_stream()`` pipelines it like the in-tree net.  forward(): the engine's pre-processing kernel, the layer walk
+    replayed from the executor's captured HIP graph, ONE pt_op_pico_candidates launch on the graph's 2 L output activations right behind the
+    replay on the same stream (they are the graph's own buffers: stream order is what protects them from the next replay), then the parent's
+    copy of counts and records into the alternating pinned landing buffers.  No host synchronisation of its own.  finish(): the parent's decode
+    with ``probs=True`` (an export's class rows went through the Sigmoid already).  The kernel converts and copies only, so the results equal
+    ``detect_host()`` -- every anchor copied to the host, filtered by numpy -- bit for bit.
+
+    The graph's outputs are checked from their host-known shapes once per input shape (2 L token-row outputs, ncls and 32 real channels; the
+    texts of ``UnsupportedOnnxGraph`` are those the synchronous route raised).  A graph whose outputs are not 16-bit activations, or that has
+    more levels or classes than a candidate record holds, is served by ``detect_host()`` inside forward(): slower, never refused."""
+
+    MAX_LEVELS = 4
+    MAX_CLASSES = L.PT_LAYOUT_CAND_FLOATS - 2 - 32
+
+    def __init__(self, eng: HipEngine, executor, config: PicodetConfig = None, max_cands: int = 2048):
+        super().__init__(eng, config, max_cands=max_cands, precision=None)      # the executor computes in the engine's arithmetic
+        self.exec = executor
+        self._tail_ok: Dict[tuple, bool] = {}       # pre-processed input shape -> True: device tail, False: host route
+
+    def _graph_outputs(self, pages: torch.Tensor):
+        cfg = self.config
+        x = self.eng.layout_preprocess(pages, cfg.img_height, cfg.img_width)
+        return x, self.exec.run_device_graphed(x, 3)      # the layer walk replayed from a captured HIP graph per batch shape
+
+    def _check_outputs(self, acts) -> bool:
+        """the shape check of the synchronous route, from what the host knows of the activations -> True when the device tail can read them"""
+        from .onnx_import import UnsupportedOnnxGraph
+        cfg = self.config
+        ncls = len(cfg.labels)
+        for a in acts:
+            if not getattr(a, "seq", False):
+                raise UnsupportedOnnxGraph(f"layout graph output of shape {a.shape()}: [B, anchors, channels] tensors are expected")
+        half = len(acts) // 2
+        if len(acts) % 2 or not acts:
+            raise UnsupportedOnnxGraph(f"a PicoDet export returns 2 L tensors (L score maps, then L box distributions), this graph returns {len(acts)}")
+        if any(a.c != ncls for a in acts[:half]) or any(a.c != 32 for a in acts[half:2 * half]):
+            raise UnsupportedOnnxGraph(f"layout graph outputs {[tuple(a.shape()) for a in acts]}: {ncls} class scores and 32 distribution bins per anchor "
+                                       f"are expected for task_type '{cfg.task_type}'")
+        if any(s_.shape()[:2] != d_.shape()[:2] for s_, d_ in zip(acts[:half], acts[half:])):
+            return False
+        return half <= self.MAX_LEVELS and ncls <= self.MAX_CLASSES and all(a.t.dtype == self.exec.adt and a.t.is_contiguous() for a in acts)
+
+    def _decode_host(self, acts, org) -> List[List[Dict]]:
+        """every anchor of every level to the host (2 L blocking copies), numpy filters them (decode_outputs)"""
+        self._check_outputs(acts)
+        outs = [self.exec.values(a)[:, 0].cpu().numpy() for a in acts]
+        half = len(outs) // 2
+        return [self.decode_outputs([s_[i] for s_ in outs[:half]], [b_[i] for b_ in outs[half:half * 2]], org) for i in range(outs[0].shape[0])]
+
+    def detect_host(self, pages: torch.Tensor) -> List[List[Dict]]:
+        """the synchronous route: what the device tail is compared against, and the fallback for outputs it cannot read"""
+        _, acts = self._graph_outputs(pages)
+        return self._decode_host(acts, tuple(pages.shape[1:3]))
+
+    def forward(self, pages: torch.Tensor, landing=None):
+        cfg = self.config
+        x, acts = self._graph_outputs(pages)
+        key = tuple(x.shape)
+        ok = self._tail_ok.get(key)
+        if ok is None:
+            ok = self._tail_ok[key] = self._check_outputs(acts)
+        if not ok:
+            return pages.shape[0], ("host", self._decode_host(acts, tuple(pages.shape[1:3])))
+        half = len(acts) // 2
+        counts, cands = self.eng.op_pico_candidates([a.t for a in acts[:half]], [a.t for a in acts[half:]], len(cfg.labels),
+                                                    thr_lo=cfg.score_threshold - 1e-3, max_cands=self.max_cands, split=self.exec.split)
+        return self._land(counts, cands, landing)
+
+    def finish(self, n: int, ticket, org) -> List[List[Dict]]:
+        if ticket[0] == "host":
+            return ticket[1]
+        return super().finish(n, ticket, org)
+
+    def _decode_record_page(self, rec: np.ndarray, org) -> List[Dict]:
+        return self.decode_page(rec, org, probs=True)

@@ -9,7 +9,10 @@ pdf_table_amd.synth_weights.picodet_state_dict) runs on the engine.  ``DocXLayou
 ONNX door (the reference's layout stage is ONNX-only: "pytorch model not support yet!", ocr_layout_task.py:82-123): a ``model.onnx`` /
 ``inference.onnx`` under ``task_path`` (or ``task_path`` = the file) is parsed by ``pdf_table_amd.onnx_import`` and run layer by layer by
 ``HipGraphExecutor`` behind the engine's own pre-processing kernel; its 2 L outputs are split like ``get_onnx_output_dict`` (:159-175: first
-half per-level scores [B, A_l, classes], second half box distributions [B, A_l, 32]) and decoded by the same host post-processor.
+half per-level scores [B, A_l, classes], second half box distributions [B, A_l, 32]) and decoded by the same host post-processor.  The stage
+around the graph is ``OnnxLayoutStage`` (layout_stage.py): the anchors that can pass the score threshold are compacted on the device
+(``pt_op_pico_candidates``) and one pinned copy brings them to the host, with the ``forward`` / ``finish`` halves ``OcrTablePipeline``
+pipelines; ``_detect_pages_host`` keeps the synchronous route (every anchor copied, numpy filters) for comparison.
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import torch
 from . import lib as L
 from .base_infer_task import BaseInferTask
 from .engine import HipEngine
-from .layout_stage import LayoutStage, PicodetConfig
+from .layout_stage import LayoutStage, OnnxLayoutStage, PicodetConfig
 from .ocr_detection_task import _read_image
 from .weights import pack_picodet
 
@@ -85,6 +88,10 @@ class OcrLayoutTask(BaseInferTask):
         self._model = self._predict
 
     def _build_processor(self):
+        if getattr(self, "_exec", None) is not None:
+            # the graph file behind LayoutStage's contract: forward() / finish() halves, candidate compaction on the device (pt_op_pico_candidates)
+            self._stage = OnnxLayoutStage(self._engine, self._exec, self._config)
+            return
         self._stage = LayoutStage(self._engine, self._config, precision=getattr(self, "_stage_precision", None))
 
     def _predict(self, images: List[np.ndarray]) -> List[List[Dict]]:
@@ -108,26 +115,17 @@ class OcrLayoutTask(BaseInferTask):
         return out
 
     def detect_pages(self, pages: torch.Tensor) -> List[List[Dict]]:
-        """batched door: equally sized pages resident on the device"""
+        """batched door: equally sized pages resident on the device.  With an ONNX file: OnnxLayoutStage -- the graph replay, one candidate
+        compaction launch, one pinned copy of the records; the result lists equal _detect_pages_host()'s element for element"""
+        return self._stage(pages)
+
+    def _detect_pages_host(self, pages: torch.Tensor) -> List[List[Dict]]:
+        """the synchronous ONNX route: every anchor of the 2 L graph outputs copied to the host and filtered by numpy (get_onnx_output_dict's
+        split, then LayoutStage.decode_outputs).  What detect_pages() is compared against, and what the stage falls back to for graph outputs
+        its device tail cannot read"""
         if getattr(self, "_exec", None) is None:
             return self._stage(pages)
-        cfg = self._config
-        ncls = len(cfg.labels)
-        x = self._engine.layout_preprocess(pages, cfg.img_height, cfg.img_width)
-        acts = self._exec.run_device_graphed(x, 3)      # the layer walk replayed from a captured HIP graph per batch shape
-        outs = []
-        for a in acts:
-            if not a.seq:
-                from .onnx_import import UnsupportedOnnxGraph
-                raise UnsupportedOnnxGraph(f"layout graph output of shape {a.shape()}: [B, anchors, channels] tensors are expected")
-            outs.append(self._exec.values(a)[:, 0].cpu().numpy())
-        d = self.get_onnx_output_dict(outs)
-        if any(s_.shape[-1] != ncls for s_ in d["boxes"]) or any(b_.shape[-1] != 32 for b_ in d["boxes_num"]):
-            from .onnx_import import UnsupportedOnnxGraph
-            raise UnsupportedOnnxGraph(f"layout graph outputs {[o.shape for o in outs]}: {ncls} class scores and 32 distribution bins per anchor "
-                                       f"are expected for task_type '{cfg.task_type}'")
-        return [self._stage.decode_outputs([s_[i] for s_ in d["boxes"]], [b_[i] for b_ in d["boxes_num"]], tuple(pages.shape[1:3]))
-                for i in range(pages.shape[0])]
+        return self._stage.detect_host(pages)
 
     def _preprocess(self, inputs, **kwargs):
         if not isinstance(inputs, list):

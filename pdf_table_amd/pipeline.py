@@ -32,6 +32,7 @@ from . import lib as L
 from .engine import HipEngine
 from .ocr_detection_task import OcrDetectionTask, _read_image
 from .layout_stage import layout_tables
+from .base_infer_task import onnx_file_under
 from .ocr_layout_task import OcrLayoutTask
 from .ocr_recognition_task import OcrRecognitionTask
 from .rec_stage import build_lines, order_points
@@ -61,6 +62,11 @@ class PageResult:
 
 
 class OcrTablePipeline:
+    """``layout=True, layout_task_path=<dir with model.onnx>`` serves that PicoDet export in ``predict()`` and in ``predict_stream()`` (main
+    stream, ``aux_layout=True``, the second layout pass of ``orientation_vote=True``) through ``OnnxLayoutStage``; ``synthetic_seed`` is then
+    not handed to the layout task (the file is served beside seeded stages), and ``layout_precision`` has no effect: the ONNX executor
+    computes in the engine's arithmetic (``precision``).  Without a graph file the in-tree LCNet graph runs as ``LayoutStage``."""
+
     def __init__(self, device: int = 0, detect_model: str = "db", recognizer: str = "CRNN", thresh: float = 0.2,
                  synthetic_seed: Optional[int] = None, det_task_path: Optional[str] = None,
                  rec_task_path: Optional[str] = None, layout: bool = False, table_structure: bool = False,
@@ -138,7 +144,10 @@ class OcrTablePipeline:
                 lk["synthetic_seed"] = synthetic_seed + 4
             if layout_task_path:
                 lk["task_path"] = layout_task_path
+                if onnx_file_under(layout_task_path):      # a graph file is served as it is (OnnxLayoutStage), beside seeded stages of the same pipeline
+                    lk.pop("synthetic_seed", None)
             if layout_precision:      # the layout net alone in the pair mode ("fp32"): exact table crops under a 16-bit engine (LayoutStage.precision)
+                # with an ONNX file under layout_task_path it has NO effect: the executor computes in the engine's arithmetic (``precision``)
                 lk["stage_precision"] = layout_precision
             self.layout_task = OcrLayoutTask(model=layout_model, engine=self.engine, task_type=layout_task_type, **lk)
         self.table_html = table_html      # structure + recognised text -> HTML per table (OcrTableToHtmlTask, section 8f-2)
