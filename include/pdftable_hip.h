@@ -786,6 +786,38 @@ int pt_tsr_mtl_structure(pt_engine* e, const float* d_f3, int n, int hw, float* 
 int pt_tsr_mtl_cells(pt_engine* e, int total, int32_t* d_cell_ids, float* d_cell_prob, float* d_cell_logits, int32_t* h_steps,
                      int force_redecode, pt_stream stream);
 
+/* The decoders' attention kernels one at a time (csrc/mtl_decoder.hip; since ABI 20): the launch functions of the decoding loops on caller-owned
+ * buffers, for op-level tests.  The engine handle and the stream only: no model is loaded.  No allocation on the device, no host synchronisation.  16-bit
+ * tensors are in the engine's storage format; split: rows [hi C | lo C] (PT_PRECISION_BF16X3).  d = 512 = 8 heads of 64; a key is stored already
+ * divided by 8.  Arguments a kernel cannot take return PT_ERR_INVALID with a message naming the value, and nothing is launched.
+ * pt_op_mtl_pick_split: how the loops cut hw keys into slices for `ntiles` query tiles: 1 <= *nsplit <= 16 slices of *keys_per_split keys (a multiple
+ *   of 32), (*nsplit - 1) * *keys_per_split < hw <= *nsplit * *keys_per_split.  Host arithmetic.
+ * pt_op_mtl_cross_attention: source attention.  kernel: PT_MTL_ATTN_STREAM (mtl_cross_decode_kernel, one query per tile), PT_MTL_ATTN_STREAM8 (the
+ *   same over the e4m3 copy; single-pass modes only), PT_MTL_ATTN_MFMA (mtl_cross_attn_kernel, up to 32 queries per tile).  d_q / d_att: npos * Mp
+ *   rows of 512 (row = position * Mp + sequence, sequences 0 .. M - 1 in use).  d_kv: 16-bit [n_tables * hw, 5120] = [k | v] of five layer slots, or
+ *   its e4m3 copy (uint8, pt_op_mtl_kv_fp8) for STREAM8; the layer reads slot `slot`.  h_tiles: HOST int32 [ntiles, 4] = (table, first query row,
+ *   queries, row stride), copied to d_tiles (device, 16 bytes per tile) on the stream; it must stay valid until that copy has run.  Every query row
+ *   belongs to at most one tile.  The hw keys of a table are read in nsplit slices of keys_per_split (a multiple of 32; the slices must cover hw and
+ *   the last one must hold a key).  nsplit == 1: normalised rows -> d_att, rows in no tile are not written.  nsplit > 1: per-slice (max, sum) ->
+ *   d_mlpart fp32 [nsplit, npos * Mp, 8, 2] and accumulators -> d_opart fp32 [nsplit, npos * Mp, 512], then mtl_cross_combine_kernel merges them
+ *   into EVERY row (position < npos, sequence < M) of d_att: the tiles must cover exactly those rows.  nb == 2 (stream kernels): a second layer in
+ *   the same launches, reading slot + 1, its q / att rows row_bs elements behind the first layer's, its partials opart_bs / ml_bs floats behind.
+ * pt_op_mtl_self_attention: self-attention of positions p0 .. p1 of M sequences over the cache d_cache [p1 + 1 positions][Mp][q 512 | k 512 | v 512]
+ *   (split: [hi 1536 | lo 1536]); the query at position p reads keys 0 .. p, or -- where d_tok[p * Mp + sequence] == pad -- all p1 + 1 positions
+ *   with equal weights (the reference's padding mask).  d_att [(p1 - p0 + 1) * Mp, 512], sequences >= M are not written.  nb == 2: a second layer
+ *   cache_bs / att_bs elements behind.  p0 == p1: a KV-cached step; p0 == 0: the re-decode mode.
+ * pt_op_mtl_kv_fp8: d_out[i] = e4m3(8 d_kv[i]) (saturating at +-448, round to nearest even), n_elems a multiple of 8. */
+#define PT_MTL_ATTN_STREAM 0
+#define PT_MTL_ATTN_STREAM8 1
+#define PT_MTL_ATTN_MFMA 2
+int pt_op_mtl_pick_split(int ntiles, int hw, int32_t* nsplit, int32_t* keys_per_split);
+int pt_op_mtl_cross_attention(pt_engine* e, int kernel, const uint16_t* d_q, const void* d_kv, int n_tables, int hw, int slot, const int32_t* h_tiles,
+                              int ntiles, int32_t* d_tiles, int keys_per_split, int nsplit, int npos, int M, int Mp, float* d_opart, float* d_mlpart,
+                              uint16_t* d_att, int split, int nb, long long row_bs, long long opart_bs, long long ml_bs, pt_stream stream);
+int pt_op_mtl_self_attention(pt_engine* e, const uint16_t* d_cache, const int32_t* d_tok, int pad, int p0, int p1, int Mp, int M, uint16_t* d_att, int split,
+                             int nb, long long cache_bs, long long att_bs, pt_stream stream);
+int pt_op_mtl_kv_fp8(pt_engine* e, const uint16_t* d_kv, long long n_elems, uint8_t* d_out, pt_stream stream);
+
 
 /* ---- image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-491) ----------------
  * Engine-free: these read and write uint8 RGB pages [n, h, w, 3] only (csrc/page_pre.hip, compiled once).

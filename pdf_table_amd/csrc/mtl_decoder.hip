@@ -1245,6 +1245,52 @@ struct Seqs {          // the sequences of one loop
 // (x == x_in: in place).  cache: the first layer's [position][Mp][1536] q/k/v cache, the second's cache_bs elements behind it.
 struct LayerB { std::string q; const float* x_in; float* x; };
 
+// ---- the attention launches.  run_layer / pt_mtl_structure and the op-level entry points (pt_op_mtl_*, tests/test_gpu_mtl_attn.py) go through these
+// three functions, so a test of an entry point runs the launch code of the decoding loops.
+// Self-attention of positions [p0, p1] of M sequences (rows (p - p0) * Mp + s of att); nb == 2: a second layer cache_bs / att_bs elements behind.
+void launch_self_attn(int x3, const bf16_t* cache, const int* tok, int pad, int p0, int p1, int Mp, int M, bf16_t* att, int nb, long long cache_bs,
+                      long long att_bs, hipStream_t s) {
+  const dim3 sgrid((p1 - p0 + 1) * M, 1, nb);
+  if (x3) hipLaunchKernelGGL(mtl_self_decode_kernel<1>, sgrid, dim3(512), 0, s, cache, tok, pad, p0, Mp, M, p1 + 1, att, cache_bs, att_bs);
+  else hipLaunchKernelGGL(mtl_self_decode_kernel<0>, sgrid, dim3(512), 0, s, cache, tok, pad, p0, Mp, M, p1 + 1, att, cache_bs, att_bs);
+}
+
+// Source attention of the query rows in `tiles` + (nsplit > 1) the merge of the key slices over rows pi * Mp + s, pi < npos, s < M.  alg: PT_MTL_ATTN_*;
+// Rs: rows in use = the stride between the slices of opart / mlpart; nb == 2 (stream kernels): a second layer bs_* elements behind, keys / values of
+// the next slot.
+struct CrossArgs {
+  const bf16_t* q; const bf16_t* kv; const unsigned char* kv8;
+  int slot; const int4* tiles; int ntiles, hw, kps, nsplit; long long Rs;
+  float *opart, *mlpart; bf16_t* att;
+  int npos, M, Mp, nb; long long bs_row, bs_opart, bs_ml;
+};
+
+void launch_cross_attn(int alg, int x3, const CrossArgs& a, hipStream_t s) {
+  const dim3 grid(a.ntiles, HEADS, a.nsplit), dgrid(a.ntiles, a.nsplit, a.nb);
+  const int koff = a.slot * 2 * D;
+  if (alg == PT_MTL_ATTN_STREAM8) {
+    hipLaunchKernelGGL(mtl_cross_decode8_kernel, dgrid, dim3(512), 0, s, a.q, a.kv8, koff, a.tiles, a.hw, a.kps, a.nsplit, a.Rs, a.opart, a.mlpart, a.att, a.bs_row,
+                       a.bs_opart, a.bs_ml);
+  } else if (alg == PT_MTL_ATTN_STREAM) {
+    if (x3) hipLaunchKernelGGL(mtl_cross_decode_kernel<1>, dgrid, dim3(512), 0, s, a.q, a.kv, koff, a.tiles, a.hw, a.kps, a.nsplit, a.Rs, a.opart, a.mlpart, a.att,
+                               a.bs_row, a.bs_opart, a.bs_ml);
+    else hipLaunchKernelGGL(mtl_cross_decode_kernel<0>, dgrid, dim3(512), 0, s, a.q, a.kv, koff, a.tiles, a.hw, a.kps, a.nsplit, a.Rs, a.opart, a.mlpart, a.att,
+                            a.bs_row, a.bs_opart, a.bs_ml);
+  } else if (x3) {
+    hipLaunchKernelGGL(mtl_cross_attn_kernel<1>, grid, dim3(64), 0, s, a.q, a.kv, koff, a.tiles, a.hw, a.kps, a.nsplit, a.Rs, a.opart, a.mlpart, a.att);
+  } else {
+    hipLaunchKernelGGL(mtl_cross_attn_kernel<0>, grid, dim3(64), 0, s, a.q, a.kv, koff, a.tiles, a.hw, a.kps, a.nsplit, a.Rs, a.opart, a.mlpart, a.att);
+  }
+  if (a.nsplit > 1)
+    hipLaunchKernelGGL(mtl_cross_combine_kernel, dim3(a.npos * a.M, 1, a.nb), dim3(512), 0, s, a.opart, a.mlpart, a.nsplit, a.Rs, a.Mp, a.M, a.att, x3, a.bs_row,
+                       a.bs_opart, a.bs_ml);
+}
+
+// e4m3 copy of n8 * 8 values of the keys / values
+void launch_kv_fp8(const bf16_t* kv, long long n8, unsigned char* out, hipStream_t s) {
+  hipLaunchKernelGGL(mtl_kv_fp8_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, kv, n8, out);
+}
+
 void run_layer(Ctx& c, int nb, const LayerB* lb, int slot, bf16_t* cache, long long cache_bs, const bf16_t* kv, const Seqs& S, const Work& W, int p0, int p1) {
   const int npos = p1 - p0 + 1;
   const long long rows = (long long)npos * S.Mp;
@@ -1256,9 +1302,7 @@ void run_layer(Ctx& c, int nb, const LayerB* lb, int slot, bf16_t* cache, long l
   if (c.rc != PT_OK) return;
   {
     PtProfScope ps(c.e, c.s, PT_PROF_OTHER, 0, "mtl self attention");
-    const dim3 sgrid(npos * S.M, 1, nb);
-    if (c.x3) hipLaunchKernelGGL(mtl_self_decode_kernel<1>, sgrid, dim3(512), 0, c.s, cache, S.tok, S.pad, p0, S.Mp, S.M, p1 + 1, W.att, cache_bs, W.bs_row);
-    else hipLaunchKernelGGL(mtl_self_decode_kernel<0>, sgrid, dim3(512), 0, c.s, cache, S.tok, S.pad, p0, S.Mp, S.M, p1 + 1, W.att, cache_bs, W.bs_row);
+    launch_self_attn(c.x3, cache, S.tok, S.pad, p0, p1, S.Mp, S.M, W.att, nb, cache_bs, W.bs_row, c.s);
   }
   for (int b = 0; b < nb; ++b) l[b] = Ctx::Lin{W.att + b * W.bs_row, nullptr, "", lb[b].q + ".so", nullptr, lb[b].x, lb[b].x_in, D, 0};
   c.lin(nb, l, rows, D, D, 0, 0, nullptr);
@@ -1267,21 +1311,10 @@ void run_layer(Ctx& c, int nb, const LayerB* lb, int slot, bf16_t* cache, long l
   if (c.rc != PT_OK) return;
   {
     PtProfScope ps(c.e, c.s, PT_PROF_OTHER, 0, "mtl source attention");
-    const dim3 grid(W.ntiles, HEADS, W.nsplit), dgrid(W.ntiles, W.nsplit, nb);
     static const bool decode_kernel = !getenv("PT_MTL_CROSS_MFMA");
-    if (W.single && S.kv8 && !c.x3) {
-      hipLaunchKernelGGL(mtl_cross_decode8_kernel, dgrid, dim3(512), 0, c.s, W.qc, S.kv8, slot * 2 * D, W.tiles, S.hw, W.kps, W.nsplit, W.Rs, W.opart, W.mlpart, W.att,
-                         W.bs_row, W.bs_opart, W.bs_ml);
-    } else if (W.single && (decode_kernel || nb > 1)) {
-      if (c.x3) hipLaunchKernelGGL(mtl_cross_decode_kernel<1>, dgrid, dim3(512), 0, c.s, W.qc, kv, slot * 2 * D, W.tiles, S.hw, W.kps, W.nsplit, W.Rs, W.opart, W.mlpart, W.att,
-                                   W.bs_row, W.bs_opart, W.bs_ml);
-      else hipLaunchKernelGGL(mtl_cross_decode_kernel<0>, dgrid, dim3(512), 0, c.s, W.qc, kv, slot * 2 * D, W.tiles, S.hw, W.kps, W.nsplit, W.Rs, W.opart, W.mlpart, W.att,
-                              W.bs_row, W.bs_opart, W.bs_ml);
-    } else if (c.x3) hipLaunchKernelGGL(mtl_cross_attn_kernel<1>, grid, dim3(64), 0, c.s, W.qc, kv, slot * 2 * D, W.tiles, S.hw, W.kps, W.nsplit, W.Rs, W.opart, W.mlpart, W.att);
-    else hipLaunchKernelGGL(mtl_cross_attn_kernel<0>, grid, dim3(64), 0, c.s, W.qc, kv, slot * 2 * D, W.tiles, S.hw, W.kps, W.nsplit, W.Rs, W.opart, W.mlpart, W.att);
-    if (W.nsplit > 1)
-      hipLaunchKernelGGL(mtl_cross_combine_kernel, dim3(npos * S.M, 1, nb), dim3(512), 0, c.s, W.opart, W.mlpart, W.nsplit, W.Rs, S.Mp, S.M, W.att, c.x3, W.bs_row,
-                         W.bs_opart, W.bs_ml);
+    const int alg = W.single && S.kv8 && !c.x3 ? PT_MTL_ATTN_STREAM8 : W.single && (decode_kernel || nb > 1) ? PT_MTL_ATTN_STREAM : PT_MTL_ATTN_MFMA;
+    const CrossArgs a{W.qc, kv, S.kv8, slot, W.tiles, W.ntiles, S.hw, W.kps, W.nsplit, W.Rs, W.opart, W.mlpart, W.att, npos, S.M, S.Mp, nb, W.bs_row, W.bs_opart, W.bs_ml};
+    launch_cross_attn(alg, c.x3, a, c.s);
   }
   for (int b = 0; b < nb; ++b) l[b] = Ctx::Lin{W.att + b * W.bs_row, nullptr, "", lb[b].q + ".co", nullptr, lb[b].x, lb[b].x, D, 0};
   c.lin(nb, l, rows, D, D, 0, 0, nullptr);
@@ -1474,8 +1507,7 @@ int pt_mtl_structure(pt_engine* e, const float* f3, int n, int hw, float* d_tag_
     if (c.rc != PT_OK) return c.rc;
     if (kv_fp8) {
       PtProfScope ps(e, s, PT_PROF_OTHER, 0, "mtl keys / values -> fp8");
-      const long long n8 = Fr * KVC / 8;
-      hipLaunchKernelGGL(mtl_kv_fp8_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, kv, n8, reinterpret_cast<unsigned char*>(pb + st->o_kv8));
+      launch_kv_fp8(kv, Fr * KVC / 8, reinterpret_cast<unsigned char*>(pb + st->o_kv8), s);
     }
   }
   hipLaunchKernelGGL(mtl_fill_kernel, dim3((Mp + 255) / 256), dim3(256), 0, s, tok, Mp, mt.sos);
@@ -1791,5 +1823,102 @@ int pt_mtl_cells(pt_engine* e, int total, int32_t* d_cell_ids, float* d_cell_pro
   }
   return PT_OK;
 }
+
+// ---- the attention kernels above one at a time (tests/test_gpu_mtl_attn.py): engine handle and stream only, no model loaded, the launch functions
+// of run_layer.  No allocation and no host synchronisation.  Everything a kernel would index with is checked here: a refused call launches nothing.
+namespace api {
+
+int pt_op_mtl_pick_split(int ntiles, int hw, int32_t* nsplit, int32_t* keys_per_split) {
+  PT_REQUIRE(nsplit && keys_per_split && ntiles >= 1 && hw >= 1 && hw <= PE_ROWS, "pt_op_mtl_pick_split: ntiles = %d, hw = %d (ntiles >= 1, hw 1 .. %d)", ntiles, hw,
+             PE_ROWS);
+  int kps = 0;
+  *nsplit = pick_split(ntiles, hw, &kps);
+  *keys_per_split = kps;
+  return PT_OK;
+}
+
+int pt_op_mtl_cross_attention(pt_engine* e, int kernel, const uint16_t* d_q, const void* d_kv, int n_tables, int hw, int slot, const int32_t* h_tiles,
+                              int ntiles, int32_t* d_tiles, int keys_per_split, int nsplit, int npos, int M, int Mp, float* d_opart, float* d_mlpart,
+                              uint16_t* d_att, int split, int nb, long long row_bs, long long opart_bs, long long ml_bs, pt_stream stream) {
+  PT_REQUIRE(e && d_q && d_kv && h_tiles && d_tiles && d_att, "pt_op_mtl_cross_attention: null argument");
+  PT_REQUIRE(kernel == PT_MTL_ATTN_STREAM || kernel == PT_MTL_ATTN_STREAM8 || kernel == PT_MTL_ATTN_MFMA,
+             "pt_op_mtl_cross_attention: kernel = %d (PT_MTL_ATTN_STREAM, _STREAM8 or _MFMA)", kernel);
+  split = split ? 1 : 0;
+  PT_REQUIRE(!(kernel == PT_MTL_ATTN_STREAM8 && split), "pt_op_mtl_cross_attention: the e4m3 stream kernel (stream8) runs in the single-pass modes only, split = 1");
+  PT_REQUIRE(hw >= 1 && hw <= PE_ROWS, "pt_op_mtl_cross_attention: hw = %d (1 .. %d)", hw, PE_ROWS);
+  PT_REQUIRE(keys_per_split >= 32 && keys_per_split % 32 == 0, "pt_op_mtl_cross_attention: keys_per_split = %d must be a positive multiple of 32", keys_per_split);
+  PT_REQUIRE(nsplit >= 1 && nsplit <= 16, "pt_op_mtl_cross_attention: nsplit = %d (1 .. 16)", nsplit);
+  PT_REQUIRE((long long)nsplit * keys_per_split >= hw, "pt_op_mtl_cross_attention: nsplit = %d slices of keys_per_split = %d keys do not cover hw = %d", nsplit,
+             keys_per_split, hw);
+  PT_REQUIRE((long long)(nsplit - 1) * keys_per_split < hw, "pt_op_mtl_cross_attention: the last of nsplit = %d slices of keys_per_split = %d keys is empty at hw = %d",
+             nsplit, keys_per_split, hw);
+  PT_REQUIRE(nb == 1 || (nb == 2 && kernel != PT_MTL_ATTN_MFMA), "pt_op_mtl_cross_attention: nb = %d (1; 2 with the stream kernels)", nb);
+  PT_REQUIRE(slot >= 0 && slot + nb <= NL, "pt_op_mtl_cross_attention: slot = %d with nb = %d (slots 0 .. %d)", slot, nb, NL - 1);
+  PT_REQUIRE(n_tables >= 1 && (long long)n_tables * hw < (1ll << 31), "pt_op_mtl_cross_attention: n_tables = %d", n_tables);
+  PT_REQUIRE(M >= 1 && Mp >= M && npos >= 1 && (long long)npos * Mp < (1ll << 21) && ntiles >= 1 && (long long)ntiles <= (long long)npos * M,
+             "pt_op_mtl_cross_attention: npos = %d, M = %d, Mp = %d, ntiles = %d (1 <= M <= Mp, at most npos * M tiles)", npos, M, Mp, ntiles);
+  const long long R = (long long)npos * Mp;
+  PT_REQUIRE(nsplit == 1 || (d_opart && d_mlpart), "pt_op_mtl_cross_attention: nsplit = %d needs the partial buffers", nsplit);
+  const int mul = split ? 2 : 1;
+  PT_REQUIRE(nb == 1 || (row_bs >= R * D * mul && row_bs % 8 == 0 && (nsplit == 1 || (opart_bs >= (long long)nsplit * R * D && ml_bs >= (long long)nsplit * R * HEADS * 2))),
+             "pt_op_mtl_cross_attention: second-layer strides row_bs = %lld, opart_bs = %lld, ml_bs = %lld overlap the first layer's buffers", row_bs, opart_bs, ml_bs);
+  PT_REQUIRE((((uintptr_t)d_q | (uintptr_t)d_kv | (uintptr_t)d_att | (uintptr_t)d_tiles) & 15) == 0, "pt_op_mtl_cross_attention: unaligned pointer");
+  // every query row once, inside the rows the merge walks (pi < npos, s < M); with key slices the merge reads the partials of ALL those rows
+  std::vector<char> seen((size_t)npos * M, 0);
+  for (int i = 0; i < ntiles; ++i) {
+    const int tab = h_tiles[4 * i], row0 = h_tiles[4 * i + 1], cnt = h_tiles[4 * i + 2], rs = h_tiles[4 * i + 3];
+    PT_REQUIRE(tab >= 0 && tab < n_tables, "pt_op_mtl_cross_attention: tile %d: table %d of %d", i, tab, n_tables);
+    PT_REQUIRE(cnt >= 1 && cnt <= (kernel == PT_MTL_ATTN_MFMA ? 32 : 1) && rs >= 1 && row0 >= 0,
+               "pt_op_mtl_cross_attention: tile %d: %d queries from row %d, stride %d (1 .. 32 queries for mfma, exactly 1 for the stream kernels)", i, cnt, row0, rs);
+    for (int j = 0; j < cnt; ++j) {
+      const long long row = row0 + (long long)j * rs;
+      PT_REQUIRE(row < R && row % Mp < M, "pt_op_mtl_cross_attention: tile %d: query row %lld is outside npos = %d positions of M = %d sequences (Mp = %d)", i, row,
+                 npos, M, Mp);
+      char& f = seen[(size_t)(row / Mp) * M + row % Mp];
+      PT_REQUIRE(!f, "pt_op_mtl_cross_attention: tile %d: query row %lld is in two tiles", i, row);
+      f = 1;
+    }
+  }
+  if (nsplit > 1)
+    for (size_t i = 0; i < seen.size(); ++i)
+      PT_REQUIRE(seen[i], "pt_op_mtl_cross_attention: nsplit = %d merges every row of npos = %d x M = %d, but row %lld is in no tile", nsplit, npos, M,
+                 (long long)(i / M) * Mp + (long long)(i % M));
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  PT_HIP_CHECK(hipMemcpyAsync(d_tiles, h_tiles, (size_t)ntiles * sizeof(int4), hipMemcpyHostToDevice, s));
+  const bool k8 = kernel == PT_MTL_ATTN_STREAM8;
+  const CrossArgs a{reinterpret_cast<const bf16_t*>(d_q), k8 ? nullptr : reinterpret_cast<const bf16_t*>(d_kv), k8 ? reinterpret_cast<const unsigned char*>(d_kv) : nullptr,
+                    slot, reinterpret_cast<const int4*>(d_tiles), ntiles, hw, keys_per_split, nsplit, R, d_opart, d_mlpart, reinterpret_cast<bf16_t*>(d_att),
+                    npos, M, Mp, nb, nb == 2 ? row_bs : 0, nb == 2 ? opart_bs : 0, nb == 2 ? ml_bs : 0};
+  launch_cross_attn(kernel, split, a, s);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_mtl_self_attention(pt_engine* e, const uint16_t* d_cache, const int32_t* d_tok, int pad, int p0, int p1, int Mp, int M, uint16_t* d_att, int split,
+                             int nb, long long cache_bs, long long att_bs, pt_stream stream) {
+  PT_REQUIRE(e && d_cache && d_tok && d_att, "pt_op_mtl_self_attention: null argument");
+  PT_REQUIRE(p0 >= 0 && p0 <= p1 && p1 < PE_ROWS, "pt_op_mtl_self_attention: positions p0 = %d .. p1 = %d (0 <= p0 <= p1 < %d)", p0, p1, PE_ROWS);
+  PT_REQUIRE(M >= 1 && Mp >= M && (long long)(p1 + 1) * Mp < (1ll << 21), "pt_op_mtl_self_attention: M = %d, Mp = %d (1 <= M <= Mp)", M, Mp);
+  PT_REQUIRE(nb == 1 || nb == 2, "pt_op_mtl_self_attention: nb = %d (1 or 2)", nb);
+  const int mul = split ? 2 : 1;
+  PT_REQUIRE(nb == 1 || (cache_bs >= (long long)(p1 + 1) * Mp * 3 * D * mul && cache_bs % 8 == 0 && att_bs >= (long long)(p1 - p0 + 1) * Mp * D * mul && att_bs % 8 == 0),
+             "pt_op_mtl_self_attention: second-layer strides cache_bs = %lld, att_bs = %lld overlap the first layer's buffers", cache_bs, att_bs);
+  PT_REQUIRE((((uintptr_t)d_cache | (uintptr_t)d_att) & 15) == 0, "pt_op_mtl_self_attention: unaligned pointer");
+  launch_self_attn(mul - 1, reinterpret_cast<const bf16_t*>(d_cache), d_tok, pad, p0, p1, Mp, M, reinterpret_cast<bf16_t*>(d_att), nb, nb == 2 ? cache_bs : 0,
+                   nb == 2 ? att_bs : 0, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_mtl_kv_fp8(pt_engine* e, const uint16_t* d_kv, long long n_elems, uint8_t* d_out, pt_stream stream) {
+  PT_REQUIRE(e && d_kv && d_out, "pt_op_mtl_kv_fp8: null argument");
+  PT_REQUIRE(n_elems >= 8 && n_elems % 8 == 0 && n_elems / 8 < (1ll << 39), "pt_op_mtl_kv_fp8: n_elems = %lld must be a positive multiple of 8", n_elems);
+  PT_REQUIRE(((uintptr_t)d_kv & 15) == 0 && ((uintptr_t)d_out & 7) == 0, "pt_op_mtl_kv_fp8: unaligned pointer");
+  launch_kv_fp8(reinterpret_cast<const bf16_t*>(d_kv), n_elems / 8, d_out, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+}  // namespace api
 
 }  // namespace PT_FMT_NS

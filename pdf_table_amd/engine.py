@@ -40,6 +40,14 @@ def _ptr(t: Optional[torch.Tensor]):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def mtl_pick_split(ntiles: int, hw: int) -> Tuple[int, int]:
+    """pt_op_mtl_pick_split: (nsplit, keys_per_split) of the MtlTabNet decoders' source attention for `ntiles` query tiles over hw keys.  Host
+    arithmetic of the library: needs no device and no engine."""
+    ns, kps = C.c_int(), C.c_int()
+    L.check(L.load().pt_op_mtl_pick_split(int(ntiles), int(hw), C.byref(ns), C.byref(kps)), "pt_op_mtl_pick_split")
+    return ns.value, kps.value
+
+
 class HipEngine:
     def __init__(self, device: int = 0):
         self.lib = L.load()
@@ -1236,6 +1244,63 @@ class HipEngine:
             self._chk(cmap, torch.int32, "cmap")
         L.check(self.lib.pt_op_cvit_ln(self._h, _ptr(x), int(rows), x.shape[-1], _ptr(g), _ptr(beta), float(eps), _ptr(out), int(split), int(mode), int(H),
                                        int(W), _ptr(cmap), self._stream()), "pt_op_cvit_ln")
+        return out
+
+    # ---- the MtlTabNet decoders' attention kernels one at a time (csrc/mtl_decoder.hip; no model loaded) ------------------
+    def mtl_pick_split(self, ntiles: int, hw: int):
+        """(nsplit, keys_per_split) the decoding loops use for `ntiles` query tiles over hw keys (host arithmetic)"""
+        return mtl_pick_split(ntiles, hw)
+
+    def op_mtl_cross_attention(self, kernel: int, q: torch.Tensor, kv: torch.Tensor, n_tables: int, hw: int, slot: int, tiles, keys_per_split: int, nsplit: int,
+                               npos: int, M: int, Mp: int, att: torch.Tensor, opart: Optional[torch.Tensor] = None, mlpart: Optional[torch.Tensor] = None,
+                               split: bool = False, nb: int = 1, row_bs: int = 0, opart_bs: int = 0, ml_bs: int = 0) -> torch.Tensor:
+        """pt_op_mtl_cross_attention (include/pdftable_hip.h) into the caller's `att`.  kernel: L.PT_MTL_ATTN_*; tiles: host rows of (table, first query
+        row, queries, row stride); kv: the 16-bit [n_tables * hw, 5120] keys / values (x 2: [hi | lo] when split) or their uint8 e4m3 copy (STREAM8)."""
+        m = 2 if split else 1
+        self._chk(q, self.act_dtype, "q")
+        self._chk(att, self.act_dtype, "att")
+        self._chk(kv, torch.uint8 if kernel == L.PT_MTL_ATTN_STREAM8 else self.act_dtype, "kv")
+        tl = np.ascontiguousarray(np.asarray(tiles, dtype=np.int32).reshape(-1, 4))
+        R = int(npos) * int(Mp)
+        rows_need = (int(nb) - 1) * int(row_bs) + R * 512 * m
+        if q.numel() < rows_need or att.numel() < rows_need or kv.numel() < int(n_tables) * int(hw) * 5120 * (1 if kernel == L.PT_MTL_ATTN_STREAM8 else m):
+            raise ValueError("op_mtl_cross_attention: q / att / kv are smaller than the shapes announce")
+        if nsplit > 1:
+            self._chk(opart, torch.float32, "opart")
+            self._chk(mlpart, torch.float32, "mlpart")
+            if opart.numel() < (int(nb) - 1) * int(opart_bs) + nsplit * R * 512 or mlpart.numel() < (int(nb) - 1) * int(ml_bs) + nsplit * R * 16:
+                raise ValueError("op_mtl_cross_attention: partial buffers are smaller than nsplit slices announce")
+        d_tiles = torch.empty((max(len(tl), 1), 4), dtype=torch.int32, device=self._tdev)
+        self._mtl_tiles = (tl, d_tiles)          # the host list is read by a copy on the stream: keep it until the next call
+        L.check(self.lib.pt_op_mtl_cross_attention(self._h, int(kernel), _ptr(q), _ptr(kv), int(n_tables), int(hw), int(slot), C.c_void_p(tl.ctypes.data), len(tl),
+                                                   _ptr(d_tiles), int(keys_per_split), int(nsplit), int(npos), int(M), int(Mp), _ptr(opart), _ptr(mlpart), _ptr(att),
+                                                   int(split), int(nb), int(row_bs), int(opart_bs), int(ml_bs), self._stream()), "pt_op_mtl_cross_attention")
+        return att
+
+    def op_mtl_self_attention(self, cache: torch.Tensor, tok: torch.Tensor, pad: int, p0: int, p1: int, Mp: int, M: int, att: torch.Tensor, split: bool = False,
+                              nb: int = 1, cache_bs: int = 0, att_bs: int = 0) -> torch.Tensor:
+        """pt_op_mtl_self_attention into the caller's `att`: cache [p1 + 1, Mp, 1536] rows of [q | k | v] (x 2 when split), tok int32 [>= p1 + 1, Mp]"""
+        m = 2 if split else 1
+        self._chk(cache, self.act_dtype, "cache")
+        self._chk(att, self.act_dtype, "att")
+        self._chk(tok, torch.int32, "tok")
+        if (cache.numel() < (int(nb) - 1) * int(cache_bs) + (int(p1) + 1) * int(Mp) * 1536 * m or tok.numel() < (int(p1) + 1) * int(Mp)
+                or att.numel() < (int(nb) - 1) * int(att_bs) + (int(p1) - int(p0) + 1) * int(Mp) * 512 * m):
+            raise ValueError("op_mtl_self_attention: cache / tok / att are smaller than the shapes announce")
+        L.check(self.lib.pt_op_mtl_self_attention(self._h, _ptr(cache), _ptr(tok), int(pad), int(p0), int(p1), int(Mp), int(M), _ptr(att), int(split), int(nb),
+                                                  int(cache_bs), int(att_bs), self._stream()), "pt_op_mtl_self_attention")
+        return att
+
+    def op_mtl_kv_fp8(self, kv: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """the e4m3 copy (x 8, saturating) of a 16-bit tensor whose element count is a multiple of 8 -> uint8 of the same shape (or the first
+        kv.numel() bytes of the caller's `out`)"""
+        self._chk(kv, self.act_dtype, "kv")
+        if out is None:
+            out = torch.zeros(kv.shape, dtype=torch.uint8, device=self._tdev)
+        self._chk(out, torch.uint8, "out")
+        if out.numel() < kv.numel():
+            raise ValueError("op_mtl_kv_fp8: out is smaller than kv")
+        L.check(self.lib.pt_op_mtl_kv_fp8(self._h, _ptr(kv), kv.numel(), _ptr(out), self._stream()), "pt_op_mtl_kv_fp8")
         return out
 
     def op_lstm(self, pregates: torch.Tensor, r_packed: torch.Tensor, hidden: int, dirs: int, reverse: bool, out_c: int, split: bool = False) -> torch.Tensor:

@@ -118,10 +118,14 @@ def dec_eng():
 
 def _run_case(dec_eng, golden_dir, case, mode, force_redecode=False):
     from pdf_table_amd.synth_weights import mtl_tabnet_decoder_state_dict
-    from pdf_table_amd.weights import pack_mtl_decoder
     cfg = dict(BASE_CFG, **DEC_CASES[case])
     g, fmap = _decoder_inputs(golden_dir)
     sd = mtl_tabnet_decoder_state_dict(seed=int(g["seed"]), num_classes=43, num_classes_cell=60)
+    return _run(dec_eng, cfg, sd, fmap, mode, force_redecode)
+
+
+def _run(dec_eng, cfg, sd, fmap, mode, force_redecode=False):
+    from pdf_table_amd.weights import pack_mtl_decoder
     dec_eng.load_weights(L.PT_MODEL_MTL_DECODER, pack_mtl_decoder(sd, cfg))
     dec_eng.set_precision(L.PT_PRECISION_BF16X3 if mode == "bf16x3" else L.PT_PRECISION_BF16)
     try:
@@ -136,7 +140,11 @@ def _run_case(dec_eng, golden_dir, case, mode, force_redecode=False):
 @pytest.mark.parametrize("case", list(DEC_CASES))
 def test_decoders_match_oracle_bf16x3(dec_eng, golden_dir, case):
     cfg, sd, fmap, out = _run_case(dec_eng, golden_dir, case, "bf16x3")
-    want = _oracle_decode(sd, fmap, cfg)
+    _assert_matches_oracle(case, out, _oracle_decode(sd, fmap, cfg))
+
+
+def _assert_matches_oracle(case, out, want):
+    """lengths, tokens, cell counts and steps identical; structure logits, boxes, cell logits and probabilities within 1e-3 (of scale) at every position"""
     tag, box = out["tag_logits"].cpu().numpy(), out["boxes"].cpu().numpy()
     ids, prob, logits = out["cell_ids"].cpu().numpy(), out["cell_prob"].cpu().numpy(), out["cell_logits"].cpu().numpy()
     c0 = 0
@@ -356,14 +364,19 @@ def test_fp8_keys_values_drift_is_recorded(dec_eng, golden_dir, case):
     """pt_engine_set_mtl_kv_fp8: the structure loop's source attention over an e4m3 copy of its keys / values (half the bytes of the loop's
     dominant stream) -- a throughput option of the bf16 mode.  Recorded against the SAME run on bf16 keys / values (what the option changes) and
     against the oracle: tag-logit drift up to the first differing token, sequences that diverge.  Ignored in BF16X3 (identical outputs)."""
-    cfg, sd, fmap, ref = _run_case(dec_eng, golden_dir, case, "bf16")
+    _assert_fp8_drift(dec_eng, lambda mode: _run_case(dec_eng, golden_dir, case, mode), case)
+
+
+def _assert_fp8_drift(dec_eng, run, case):
+    """run(mode) -> (cfg, sd, fmap, out) with the fp8 option off, on and off again; the drift bounds of the fp8 option"""
+    cfg, sd, fmap, ref = run("bf16")
     dec_eng.set_mtl_kv_fp8(True)
     try:
-        _, _, _, out = _run_case(dec_eng, golden_dir, case, "bf16")
-        _, _, _, x3 = _run_case(dec_eng, golden_dir, case, "bf16x3")
+        _, _, _, out = run("bf16")
+        _, _, _, x3 = run("bf16x3")
     finally:
         dec_eng.set_mtl_kv_fp8(False)
-    _, _, _, x3_ref = _run_case(dec_eng, golden_dir, case, "bf16x3")
+    _, _, _, x3_ref = run("bf16x3")
     assert torch.equal(x3["tag_logits"], x3_ref["tag_logits"]) and torch.equal(x3["cell_ids"], x3_ref["cell_ids"])
     want = _oracle_decode(sd, fmap, cfg)
     a, b = out["tag_logits"].cpu().numpy(), ref["tag_logits"].cpu().numpy()
@@ -382,6 +395,57 @@ def test_fp8_keys_values_drift_is_recorded(dec_eng, golden_dir, case):
     print(f"mtl fp8 keys / values [{case}]: tag-logit drift {d_bf16:.2e} of scale against the bf16 keys / values ({flips_bf16} of {len(want)} sequences "
           f"diverge), {d_orc:.2e} against the oracle ({flips_orc} diverge)")
     assert d_bf16 <= 0.1 and d_orc <= 0.15
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The same comparisons at key counts the 3x8 / 6x8 fixtures never reach: seeded random feature maps of 40, 600 and 3600 keys (production: 3600).
+# One table per call, so pick_split() cuts the keys into 2, 10 and 15 slices (last slices of 8, 24 and 16 keys; four 64-key chunks per slice at
+# 3600), in the KV-cached loop (stream kernels) and in the re-decode mode (MFMA kernel); the cell tags sit on tokens these maps emit, so the cell
+# decoder's one-slice MFMA launch reads all hw keys too.  max_len 12 keeps the oracle's O(L^2) schedule under a second per map.
+# Seeds: chosen so that no token of the oracle's sits on a tie (top-2 margin <= 2e-3 of scale), so every token is compared and must be identical.
+# The oracle's smallest margins, structure / cell tokens, of scale: 5x8 seed 523: 2.0e-2 / 6.0e-3 (of seeds 501 .. 579 the only one whose 8 .. 13
+# cells x 7 positions all clear 5e-3; 501 has a cell token at 1.5e-3, 502 at 3e-5); 20x30 seed 501: 1.6e-2 / 5.3e-3 (503 and 508 put a structure
+# token at 8e-4 / 4e-4); 60x60 seed 506: 1.7e-2 / 4.0e-2 (507 puts a cell token at 7e-4).
+# ---------------------------------------------------------------------------------------------------------------------
+RANDOM_MAPS = {"5x8": (5, 8, 523), "20x30": (20, 30, 501), "60x60": (60, 60, 506)}          # h, w, seed
+RANDOM_MAP_CFG = dict(BASE_CFG, idx_tag_cell=[12, 1])
+_random_map_oracle = {}
+
+
+def _random_map(size, golden_dir):
+    """(state dict, feature map [1, 512, h, w], the oracle's outputs) of one random map; the oracle runs once per size"""
+    from pdf_table_amd.synth_weights import mtl_tabnet_decoder_state_dict
+    if size not in _random_map_oracle:
+        h, w, map_seed = RANDOM_MAPS[size]
+        fmap = np.random.default_rng(map_seed).standard_normal((1, 512, h, w)).astype(np.float32)
+        seed = int(np.load(os.path.join(golden_dir, "mtl_tabnet_decoder.npz"))["seed"])            # the decoder weights of the tests above
+        sd = mtl_tabnet_decoder_state_dict(seed=seed, num_classes=43, num_classes_cell=60)
+        want = _oracle_decode(sd, fmap, RANDOM_MAP_CFG)
+        for wt, _, wc in want:                     # the rule of the length test: no compared token sits on a tie of the oracle's own
+            top2 = np.sort(wt, -1)[:, -2:]
+            assert (top2[:, 1] - top2[:, 0]).min() > 2e-3 * np.abs(wt).max(), "a structure token on a tie: pick another seed"
+            assert wc.ndim == 3, "no cell tags emitted: the cell decoder would not run"
+            c2 = np.sort(wc, -1)[..., -2:]
+            assert (c2[..., 1] - c2[..., 0]).min() > 2e-3 * np.abs(wc).max(), "a cell token on a tie: pick another seed"
+        _random_map_oracle[size] = (sd, fmap, want)
+    return _random_map_oracle[size]
+
+
+@pytest.mark.parametrize("redecode", [False, True], ids=["cached", "redecode"])
+@pytest.mark.parametrize("size", list(RANDOM_MAPS))
+def test_decoders_match_oracle_on_random_maps_bf16x3(dec_eng, golden_dir, size, redecode):
+    sd, fmap, want = _random_map(size, golden_dir)
+    from pdf_table_amd.engine import mtl_pick_split
+    hw = fmap.shape[2] * fmap.shape[3]
+    assert mtl_pick_split(1, hw) == {40: (2, 32), 600: (10, 64), 3600: (15, 256)}[hw]          # the slices this test is about
+    _, _, _, out = _run(dec_eng, RANDOM_MAP_CFG, sd, fmap, "bf16x3", force_redecode=redecode)
+    _assert_matches_oracle(f"random {size} {'re-decode' if redecode else 'cached'}", out, want)
+
+
+def test_fp8_keys_values_drift_on_a_600_key_map(dec_eng, golden_dir):
+    """the e4m3 stream kernel over 10 slices of 64 keys (last: 24) under the drift bounds of the 24-key fixtures"""
+    sd, fmap, _ = _random_map("20x30", golden_dir)
+    _assert_fp8_drift(dec_eng, lambda mode: (RANDOM_MAP_CFG, sd, fmap, _run(dec_eng, RANDOM_MAP_CFG, sd, fmap, mode)[3]), "random 20x30")
 
 
 @pytest.mark.parametrize("case", ["golden_ids", "eos_on_an_emitted_token"])
