@@ -386,6 +386,41 @@ int pt_tsr_decode(pt_engine* e, const float* d_hm, const float* d_st, const floa
 int pt_tsr_forward_decode(pt_engine* e, const uint16_t* d_input_bf16, int n, int in_h, int in_w, int wiz_rev,
                           float vis_thresh, int32_t* d_counts, float* d_dets, float* d_logi, pt_stream stream);
 
+/* ---- letterbox rows of the DLA-34 detector's front segment ------------------------------------------------------------------------
+ * A crop wider than high fills only the middle rows of the detector's input; the rest holds the warp's border value.  The front of the
+ * net (base_layer, level0, level1, level2: everything up to the 64-channel map at H/4) has a static receptive field of
+ * pt_tsr_band_radius() input rows, so its output farther than that from the content is what an all-padding table gives at the same
+ * map position.  pt_tsr_plan_bands says, per table, which input rows the front segment has to see:
+ *   full = 1          : all of them -- crop_h >= crop_w, a map with a rotation / shear term (minv[1], minv[3]: one that moves the warp's 10-bit
+ *                       fixed-point coordinates somewhere on the map), or a window that would come
+ *                       within 64 rows of the map's top or bottom (upper_left maps always do), where the convolutions' own zero padding counts
+ *   [row0, row1)      : else, multiples of 64: every row whose bilinear footprint can touch the crop, +- 2, widened by twice the radius
+ *   [keep0, keep1)    : the rows of the H/4 map taken from the band (content +- 2 +- radius; each at least the radius inside the band)
+ *   stack, stack_row  : banded tables are stacked one under the other into tall one-image inputs of at most max_stack_rows rows
+ *                       (<= 0 or more than 32768: 32768); the band starts at input row stack_row of stack `stack`
+ * h_tables: host records.  *n_stacks and *row_fraction (rows planned / (n * inp_h)) may be null. */
+typedef struct pt_tsr_band {
+  int32_t full, row0, row1, keep0, keep1, stack, stack_row, reserved;
+} pt_tsr_band;
+int pt_tsr_band_radius(void);
+int pt_tsr_plan_bands(const pt_tsr_table* h_tables, int n, int inp_h, int inp_w, int max_stack_rows, pt_tsr_band* h_out, int32_t* n_stacks,
+                      double* row_fraction);
+
+/* pt_tsr_preprocess + pt_tsr_forward_decode in one call with the tables known on the host as well (h_tables and d_tables hold the same n records):
+ * the front segment of the detector runs on the planned row bands only, the rest of its level-2 map is filled from the cached map of an
+ * all-padding table, and everything behind runs unchanged.  Same outputs, bit for bit, as the two calls.  The environment variable
+ * PT_TSR_BAND_STACK_ROWS (read per call) lowers the stack cap. */
+int pt_tsr_warp_forward_decode(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* h_tables,
+                               const pt_tsr_table* d_tables, int n, int inp_h, int inp_w, int bgr, int wiz_rev, float vis_thresh,
+                               int32_t* d_counts, float* d_dets, float* d_logi, pt_stream stream);
+
+/* Test hook: the detector's level-2 map (`layers[2]` of DLA.forward: [n, inp_h / 4, inp_w / 4, 64], (hi | lo) = 128 values per pixel in the pair
+ * modes) of n table crops.  bands = 0: the warp and the front segment on whole maps; 1: on the planned row bands, planned with `margin` in place of
+ * pt_tsr_band_radius() (< 0: the radius itself; below it the result is WRONG near the content's edge -- that is what the hook is for). */
+int pt_op_tsr_level2(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* h_tables,
+                     const pt_tsr_table* d_tables, int n, int inp_h, int inp_w, int bgr, int bands, int margin, uint16_t* d_out,
+                     pt_stream stream);
+
 /* ---- CenterNet table cells (TableStructureRec = DLASeg('dla34', down_ratio 4, head_conv 256), center_net/modeling_table_structure.py:22-47;
  * weights PT_MODEL_CENTERNET_DLA34) ------------------------------------------------------------------------------------------- */
 /* Detector network: d_input_bf16 as for pt_tsr_forward_net (pt_tsr_preprocess output; H, W multiples of 32).  Outputs: fp32 NHWC

@@ -95,6 +95,10 @@ void pt_engine_destroy(pt_engine* e) {
   if (e->zero_page) (void)hipFree(e->zero_page);
   if (e->tsr_scratch) (void)hipFree(e->tsr_scratch);
   if (e->tsr_lut) (void)hipFree(e->tsr_lut);
+  for (int i = 0; i < 4; ++i) {
+    if (e->tsr_pad_l2[i]) (void)hipFree(e->tsr_pad_l2[i]);
+    if (e->tsr_pad_l2_ready[i]) (void)hipEventDestroy(e->tsr_pad_l2_ready[i]);
+  }
   if (e->cls_lut) (void)hipFree(e->cls_lut);
   if (e->rec_pp_lut) (void)hipFree(e->rec_pp_lut);
   if (e->rec_zero[0]) (void)hipFree(e->rec_zero[0]);
@@ -108,6 +112,7 @@ void pt_engine_destroy(pt_engine* e) {
   if (e->det_in) (void)hipFree(e->det_in);
   pt_mtl_release(e);
   e->stage_ring.destroy();
+  e->band_ring.destroy();
   if (e->lstm_scratch) (void)hipFree(e->lstm_scratch);
   if (e->lstm_scratch8) (void)hipFree(e->lstm_scratch8);
   if (e->lstm_err) (void)hipHostFree(e->lstm_err);
@@ -168,6 +173,8 @@ static int register_blob(pt_engine* e, int kind, const uint8_t* h_head, size_t h
   e->models[kind] = m;
   if (kind == PT_MODEL_DB_RESNET18 || kind == PT_MODEL_DB_NAS) e->det_kind = kind;   // the active detector
   if (kind == PT_MODEL_CRNN) e->rec_zero_valid[0] = e->rec_zero_valid[1] = false;     // cached all-padding-line activations
+  if (kind == PT_MODEL_LORE_DLA34)
+    for (int i = 0; i < 4; ++i) e->tsr_pad_l2_valid[i] = false;                         // cached all-padding-table level-2 maps
   return PT_OK;
 }
 
@@ -353,17 +360,37 @@ int pt_tsr_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int
                       int n, int inp_h, int inp_w, int bgr, uint16_t* d_out_bf16, pt_stream stream) {
   PT_REQUIRE(e && d_pages_rgb && d_tables && d_out_bf16 && n > 0 && n_pages > 0, "pt_tsr_preprocess: bad arguments");
   PT_HIP_CHECK(hipSetDevice(e->device));
-  if (!e->tsr_lut) {
-    // ((x / 255.) - mean) / std in float64 then cast, as numpy evaluates processer_lore.py:67-70,90
-    const float mean[3] = {0.408f, 0.447f, 0.470f}, stdv[3] = {0.289f, 0.274f, 0.278f};
-    float lut[768];
-    for (int c = 0; c < 3; ++c)
-      for (int v = 0; v < 256; ++v) lut[c * 256 + v] = (float)(((double)v / 255.0 - (double)mean[c]) / (double)stdv[c]);
-    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->tsr_lut), sizeof(lut)));
-    PT_HIP_CHECK(hipMemcpy(e->tsr_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
-  }
-  return pt_launch_tsr_preprocess(d_pages_rgb, ph, pw, d_tables, n, inp_h, inp_w, bgr, e->tsr_lut, d_out_bf16,
+  const float* lut = nullptr;
+  const int rc = pt_lore_norm_lut(e, &lut);
+  if (rc != PT_OK) return rc;
+  return pt_launch_tsr_preprocess(d_pages_rgb, ph, pw, d_tables, n, inp_h, inp_w, bgr, lut, d_out_bf16,
                                   pt_split(e), reinterpret_cast<hipStream_t>(stream));
+}
+
+int pt_tsr_band_radius(void) { return pt_lore_band_radius(); }
+
+int pt_tsr_plan_bands(const pt_tsr_table* h_tables, int n, int inp_h, int inp_w, int max_stack_rows, pt_tsr_band* h_out, int32_t* n_stacks,
+                      double* row_fraction) {
+  return pt_lore_plan_bands(h_tables, n, inp_h, inp_w, max_stack_rows, -1, h_out, n_stacks, row_fraction);
+}
+
+int pt_tsr_warp_forward_decode(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* h_tables,
+                               const pt_tsr_table* d_tables, int n, int inp_h, int inp_w, int bgr, int wiz_rev, float vis_thresh,
+                               int32_t* d_counts, float* d_dets, float* d_logi, pt_stream stream) {
+  PT_REQUIRE(e && d_pages_rgb && h_tables && d_tables && n > 0 && n_pages > 0, "pt_tsr_warp_forward_decode: bad arguments");
+  for (int t = 0; t < n; ++t) PT_REQUIRE(h_tables[t].page >= 0 && h_tables[t].page < n_pages, "pt_tsr_warp_forward_decode: table %d on page %d of %d", t, h_tables[t].page, n_pages);
+  PT_HIP_CHECK(hipSetDevice(e->device));
+  return pt_lore_warp_forward_decode(e, d_pages_rgb, ph, pw, h_tables, d_tables, n, inp_h, inp_w, bgr, 1, -1, wiz_rev, vis_thresh, d_counts, d_dets,
+                                     d_logi, nullptr, reinterpret_cast<hipStream_t>(stream));
+}
+
+int pt_op_tsr_level2(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* h_tables,
+                     const pt_tsr_table* d_tables, int n, int inp_h, int inp_w, int bgr, int bands, int margin, uint16_t* d_out,
+                     pt_stream stream) {
+  PT_REQUIRE(e && d_pages_rgb && h_tables && d_tables && d_out && n > 0 && n_pages > 0, "pt_op_tsr_level2: bad arguments");
+  PT_HIP_CHECK(hipSetDevice(e->device));
+  return pt_lore_warp_forward_decode(e, d_pages_rgb, ph, pw, h_tables, d_tables, n, inp_h, inp_w, bgr, bands ? 1 : 0, margin, 0, 0.f, nullptr, nullptr,
+                                     nullptr, reinterpret_cast<bf16_t*>(d_out), reinterpret_cast<hipStream_t>(stream));
 }
 
 int pt_tsr_forward_net(pt_engine* e, const uint16_t* d_input_bf16, int n, int H, int W, float* d_hm, float* d_st,

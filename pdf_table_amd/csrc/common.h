@@ -192,12 +192,23 @@ struct pt_engine {
   hipEvent_t rec_zero_ready[2] = {nullptr, nullptr};         // recorded behind the build of rec_zero[i]: calls on other streams wait for it
   void* rec_limits = nullptr; size_t rec_limits_cap = 0;     // per-line column limits of the call in flight
   int rec_ragged = 1;                                        // PT_REC_RAGGED=0: compute the padding too (A/B switch)
+  // lore_model.hip: level 2 of the DLA-34 base for an all-padding table ([H/4, W/4, 64] in the storage of precision i), what the banded front
+  // segment fills the letterbox rows of `layers[2]` with; valid for one (weights, precision, input size, conv variant) until the Lore weights are
+  // loaded again
+  void* tsr_pad_l2[4] = {nullptr, nullptr, nullptr, nullptr};
+  size_t tsr_pad_l2_cap[4] = {0, 0, 0, 0};
+  bool tsr_pad_l2_valid[4] = {false, false, false, false};
+  int tsr_pad_l2_key[4][3] = {};                             // {H, W, the 64 -> 64 layers run weight-stationary}
+  hipEvent_t tsr_pad_l2_ready[4] = {nullptr, nullptr, nullptr, nullptr};   // recorded behind the build: calls on other streams wait for it
   // cvit_model.hip: host images of the chunk maps of the last 16 micro-batches.  They are the sources of asynchronous
   // host-to-device copies: a stack vector could die before a deferred copy reads it; a slot is reused only 16 micro-batches
   // (thousands of launches on the same stream) later
   std::vector<int> cvit_maps[16][2];
   int cvit_slot = 0;
   PtPinnedRing stage_ring;                                   // pinned sources of small asynchronous uploads (Lore processor token maps, ConvNextViT chunk maps)
+  // ... of the Lore detector's band tables (two per call), a ring of their own: a slot comes round again four calls later, when its copy is long done --
+  // in stage_ring, which the recogniser turns over several times per batch, taking a slot can mean waiting for the device
+  PtPinnedRing band_ring;
   void* mtl_state = nullptr;                                 // mtl_decoder.hip: buffers + cell lists between pt_tsr_mtl_structure and pt_tsr_mtl_cells
 };
 
@@ -302,6 +313,10 @@ struct ConvDesc {
   int xp_store = 0;
   int alg_n = 0;
   double alg_scale = 1.0;
+  // kernel choice only: where it depends on how many tiles the launch has, count them as if the map were pick_B images of pick_Ho output rows
+  // (0 = the launch's own).  A part of a batch run on its own (row bands of Lore's front segment) then takes the kernel the whole batch takes,
+  // and with it the same summation order
+  int pick_B = 0, pick_Ho = 0;
   // fused heat-map head (allowed when pt_conv_fuses_hm): this 3x3 64 -> 256 + ReLU layer is the hidden layer of a 1x1 256 -> 2 layer that runs in its
   // epilogue; the hidden map is not stored (`out` unused).  hm_w2: that layer's 16-bit tiles [1][8][1][64][32], rows 2 .. 63 zero padding; hm_b2: its
   // fp32 bias [64]; hm_logits: fp32 [pixel][8] as the 1x1 launch with n_valid = 8 writes it; hm_sig: fp32 [pixel][2] = pt_heat_sigmoid(logit), the
@@ -442,6 +457,30 @@ int pt_db_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float*
                       float thresh = 0.f, int* bitmap_done = nullptr);
 int pt_launch_tsr_preprocess(const uint8_t* pages, int ph, int pw, const pt_tsr_table* tabs, int n, int H, int W, int bgr,
                              const float* lut, bf16_t* out, int split, hipStream_t s);
+// the same warp for runs of PT_TSR_BAND_ALIGN destination rows: run i = rows [runs[i].y, + PT_TSR_BAND_ALIGN) of table runs[i].x, written at row
+// runs[i].z of `out` taken as ONE image [rows, W, 4 | 8]
+constexpr int PT_TSR_BAND_ALIGN = 64;
+int pt_launch_tsr_preprocess_rows(pt_engine* e, const uint8_t* pages, int ph, int pw, const pt_tsr_table* tabs, const int4* runs, int n_runs, int H, int W,
+                                  int bgr, const float* lut, bf16_t* out, int split, hipStream_t s);
+// one image [H, W, 4 | 8] of the border value (what the warp writes outside the crop)
+int pt_launch_tsr_pad_image(const float* lut, int H, int W, bf16_t* out, int split, hipStream_t s);
+// out [n][rows][row_elems]: row r of map t = out + src[t].off + (r - src[t].row0) * row_elems where src[t].k0 <= r < src[t].k1, else pad + r * row_elems
+// (the bands' maps lie in the arena `out` lies in: an element offset from it, so that the kernel's loads keep the global address space)
+struct PtBandSrc {
+  long long off;
+  int row0, k0, k1, pad_;
+};
+int pt_launch_tsr_band_assemble(pt_engine* e, const PtBandSrc* src, const bf16_t* pad, bf16_t* out, int n, int rows, int row_elems, hipStream_t s);
+int pt_lore_plan_bands(const pt_tsr_table* tabs, int n, int inp_h, int inp_w, int max_stack_rows, int margin, pt_tsr_band* out, int* n_stacks,
+                       double* row_fraction);
+int pt_lore_band_radius();
+int pt_lore_norm_lut(pt_engine* e, const float** lut_out);      // [3][256] normalisation table of the Lore pre-process (engine-owned, built once)
+// warp + DLA-34 forward + decode with the tables known on the host (band path); l2_out != null: stop behind level 2 and copy `layers[2]` there
+int pt_lore_warp_forward_decode(pt_engine* e, const uint8_t* pages, int ph, int pw, const pt_tsr_table* h_tabs, const pt_tsr_table* d_tabs, int n, int H,
+                                int W, int bgr, int bands, int margin, int wiz_rev, float vis_thresh, int* d_counts, float* d_dets, float* d_logi,
+                                bf16_t* l2_out, hipStream_t s);
+// the plain 64 -> 64 3x3 layer over B maps of Ho x Wo takes the weight-stationary kernel (conv_igemm.hip)
+bool pt_conv_takes_ws64(const pt_engine* e, int B, int Ho, int Wo);
 int pt_picodet_forward_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* h0, float* h1, float* h2, float* h3,
                           hipStream_t s);
 int pt_launch_pico_candidates(const float* head, int B, int A, int ncls, int level, float thr_lo, int max_cands, float* cands,

@@ -3612,6 +3612,13 @@ bool pt_conv_fuses_hm(const pt_engine* e) {
   return !pt_split(e) && use_dma_kernel() && conv_variant() == 3 && !(pv && atoi(pv) < 4) && !(ev && atoi(ev) == 0);
 }
 
+// the tile-count rule of the weight-stationary 64 -> 64 kernel, apart from the layer's own properties (PT_CONV_WS64=0: never, 2: any tile count)
+bool pt_conv_takes_ws64(const pt_engine* e, int B, int Ho, int Wo) {
+  const char* ws_ev = getenv("PT_CONV_WS64");      // read per call (tests)
+  const int ws64 = ws_ev ? atoi(ws_ev) : 1;
+  return ws64 && (ws64 == 2 || (long long)B * ((Ho + 15) / 16) * ((Wo + 31) / 32) >= 4ll * e->num_cu);
+}
+
 int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
   PT_REQUIRE(d.in && d.w && d.bias && (d.out || d.out_f32 || d.head_w || d.argmax_part || d.hm_w2), "conv: null pointer");
   PT_REQUIRE(d.Cin % 32 == 0 && d.Cin > 0, "conv: Cin=%d must be a positive multiple of 32", d.Cin);
@@ -3657,6 +3664,8 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
              "conv: fused pooling needs a plain 3x3 stride-1 layer with even output size");
   PT_REQUIRE(d.relu != 3 || d.slope, "conv: PReLU needs the slope tensor");
   k.split = d.split; k.out_lo_off = d.out_lo_off;
+  // the extent the kernel choice below counts tiles over (ConvDesc.pick_B / pick_Ho)
+  const int pB = d.pick_B > 0 ? d.pick_B : k.B, pHo = d.pick_Ho > 0 ? d.pick_Ho : k.Ho;
   for (int i = 0; i < 8; ++i) k.tap_mask[i] = d.tap_mask[i];
   {
     // the layer asks for it (ConvDesc.xp_store: the detector's graph, +0.9 % det-only; the layout net's many small hardswish GEMMs lose
@@ -3699,7 +3708,7 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
   }
   // stride-2 3x3 layers with 128-wide output blocks (ResNet-18 / DLA-34 down-sampling convs): the 16-channel-slice DMA kernel on an 8 x 32 x 128 tile
   // (PT_CONV_S2_DMA=0: the register-staged 4 x 32 x 64 tile, A/B switch)
-  if (d.ks == 3 && d.stride == 2 && !d.split && d.N % 128 == 0 && d.Cin % 32 == 0 && d.Cin >= 64 && k.Ho >= 8 && !d.head_w && !d.argmax_part && !d.n_valid &&
+  if (d.ks == 3 && d.stride == 2 && !d.split && d.N % 128 == 0 && d.Cin % 32 == 0 && d.Cin >= 64 && pHo >= 8 && !d.head_w && !d.argmax_part && !d.n_valid &&
       !d.out_f32 && !d.res_f32 && !d.res && d.relu < 2 && !d.ylimit && !d.xlimit && !d.xlimit_rows && !d.pool && d.rep == 1 && !d.shuffle_cout && use_dma_kernel()) {
     static int s2 = -1;
     if (s2 < 0) { const char* ev = getenv("PT_CONV_S2_DMA"); s2 = ev ? atoi(ev) : 1; }
@@ -3716,14 +3725,12 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
     const int cv = conv_variant();
     // plain 64 -> 64 layers with enough tiles to give every CU a run of them: the weight-stationary persistent kernel
     // (PT_CONV_WS64=0: the v3 tiles, A/B switch)
-    const char* ws_ev = getenv("PT_CONV_WS64");      // read per call: 2 forces the kernel for any tile count (tests)
-    const int ws64 = ws_ev ? atoi(ws_ev) : 1;
     bool masked = false;
     for (int i = 0; i < 8; ++i) masked = masked || d.tap_mask[i] != 0;
-    if (ws64 && cv == 3 && !d.split && d.Cin == 64 && d.N == 64 && d.rep == 1 && !d.shuffle_cout && d.res_mode <= 1 && !masked &&
-        (ws64 == 2 || (long long)k.B * ((k.Ho + 15) / 16) * ((k.Wo + 31) / 32) >= 4ll * e->num_cu))
+    if (cv == 3 && !d.split && d.Cin == 64 && d.N == 64 && d.rep == 1 && !d.shuffle_cout && d.res_mode <= 1 && !masked &&
+        pt_conv_takes_ws64(e, pB, pHo, k.Wo))
       return launch_ws64(e, k, s, flop);
-    const bool v3ok = (d.N % 128 == 0) ? k.Ho >= 12 : k.Ho >= 24;
+    const bool v3ok = (d.N % 128 == 0) ? pHo >= 12 : pHo >= 24;
     const bool wide = d.Cin >= 128;
     int pick = 0;
     if (cv == 3 && v3ok) pick = 3;
@@ -3737,7 +3744,7 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
     bool use_half = half == 1;
     if (half < 0 && pick == 3) {
       const bool nt2 = d.N % 128 == 0;
-      const long long full = (long long)k.B * ((k.Ho + (nt2 ? 15 : 31)) / (nt2 ? 16 : 32)) * ((k.Wo + 31) / 32) * (d.N / (nt2 ? 128 : 64));
+      const long long full = (long long)pB * ((pHo + (nt2 ? 15 : 31)) / (nt2 ? 16 : 32)) * ((k.Wo + 31) / 32) * (d.N / (nt2 ? 128 : 64));
       use_half = d.Cin <= 128 || (full < 2ll * e->num_cu && full % e->num_cu != 0);
     }
     // v4 (software-pipelined tap loop) for the unmasked layers; PT_CONV_PIPE=0: v3 everywhere (A/B switch, read per call)
@@ -3764,7 +3771,7 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
       // TF/s, @60^2 1174 -> 1198, 512 -> 512 @32^2 1379 -> 1404, @30^2 1267 -> 1275; the 4-wave tile LOSES 14 % as a persistent kernel -- 128 -> 128 @128^2
       // 1134 -> 975: two of its workgroups per CU already cover each other's prologues, and the run's bookkeeping costs it registers it does not have)
       const bool nt2 = d.N % 128 == 0;
-      const long long tiles = (long long)k.B * ((k.Ho + (nt2 ? 15 : 31)) / (nt2 ? 16 : 32)) * ((k.Wo + 31) / 32) * (d.N / (nt2 ? 128 : 64));
+      const long long tiles = (long long)pB * ((pHo + (nt2 ? 15 : 31)) / (nt2 ? 16 : 32)) * ((k.Wo + 31) / 32) * (d.N / (nt2 ? 128 : 64));
       // (a four-slice layer without a residual is better off on the persistent 8-wave tile than on the 4-wave one: 64 -> 256 @256^2 900 -> 955 TF/s; with
       // eight slices the two are level -- 128 -> 128 @128^2 1101 / 1120 -- and with a residual the 4-wave tile wins, 922 against 862)
       if (use_half && half < 0 && direct && pipe >= 4 && d.Cin == 64 && nt2 && !d.res && tiles >= 2ll * e->num_cu) use_half = false;

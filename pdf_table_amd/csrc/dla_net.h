@@ -25,6 +25,15 @@ struct DlaCtx : NetCtx {
   float* om = nullptr;      // shared offset/mask scratch, fp32 [pixel][32]
   const int* ylimit = nullptr;   // when set: convs skip output tiles at rows >= *ylimit (sparse-head mosaics)
   double alg_scale = 1.0;        // roofline accounting: fraction of a launch's output pixels the algorithm needs
+  // a part of a batch run on its own (Lore's row bands: one tall image of part_H input rows cut from pick_n maps of whole_H rows): the conv launcher
+  // chooses its kernels as for the whole batch (ConvDesc.pick_B / pick_Ho), so that a value is summed in the same order wherever it is computed
+  int pick_n = 0, part_H = 0, whole_H = 0;
+  void pick(ConvDesc& c) const {
+    if (!pick_n) return;
+    const int in_h = (int)((long long)c.H * whole_H / part_H), pad = c.ks / 2;
+    c.pick_B = pick_n;
+    c.pick_Ho = (in_h + 2 * pad - c.ks) / c.stride + 1;
+  }
 
   // conv with folded bias; q = weight name prefix; N = GEMM width (multiple of 64), nv = channels stored (0 = N)
   void conv(const T& in, const std::string& q, int N, int ks, int stride, const T& out, int relu, const T* res = nullptr,
@@ -33,6 +42,7 @@ struct DlaCtx : NetCtx {
     if (!conv_desc(c, in, q, N, ks, stride, relu)) return;
     if (cin_override) c.Cin = cin_override;
     c.n_valid = nv; c.ylimit = ylimit; c.alg_n = alg_n; c.alg_scale = alg_scale;
+    pick(c);
     if (out_f32) to_f32(c, out_f32, f32_cs);
     else to_map(c, out);
     if (res) { c.res = res->p; c.res_mode = 1; }
@@ -54,6 +64,7 @@ struct DlaCtx : NetCtx {
     }
     c.w = W(w); c.bias = F(b);
     c.N = N; c.ks = 1; c.stride = 1; c.relu = relu; c.split = x3; c.alg_scale = alg_scale;
+    pick(c);
     to_map(c, out);
     launch(c);
   }
@@ -103,8 +114,28 @@ struct DlaCtx : NetCtx {
   }
 };
 
-// DLA.forward up to level5: layers[l] = output of level l (levels 0 and 1 only as far as the chosen path materialises them)
-static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
+// The front segment of DLA.forward: base_layer, level0, level1, level2 on c.n images of H x W.  Its layers have small static receptive fields:
+// kFront lists them (kernel, stride, padding) along the longest path to a level-2 output row -- level2's tree1.conv1 (stride 2), then tree1.conv2,
+// tree2.conv1, tree2.conv2; the 2x2 pool, the 1x1 project and the 1x1 root reach no farther -- and dla_front_radius() folds the list into the
+// distance, in input rows, beyond which an input row cannot reach a given row of `layers[2]` (the stride-4 map; row r sits at input row 4 r)
+struct DlaFrontLayer { int k, stride, pad; };
+constexpr DlaFrontLayer kFront[] = {{7, 1, 3},                              // base_layer
+                                    {3, 1, 1},                              // level0
+                                    {3, 2, 1},                              // level1
+                                    {3, 2, 1}, {3, 1, 1}, {3, 1, 1}, {3, 1, 1}};   // level2: tree1.conv1, tree1.conv2, tree2.conv1, tree2.conv2
+constexpr int kFrontStride = 4;
+constexpr int dla_front_radius() {
+  // output row 0 reads input rows [lo, hi]: walk the list backwards
+  int lo = 0, hi = 0;
+  for (int i = (int)(sizeof(kFront) / sizeof(kFront[0])) - 1; i >= 0; --i) {
+    lo = lo * kFront[i].stride - kFront[i].pad;
+    hi = hi * kFront[i].stride - kFront[i].pad + kFront[i].k - 1;
+  }
+  return hi > -lo ? hi : -lo;
+}
+static_assert(dla_front_radius() == 19, "DLA-34 front segment: receptive-field radius");
+
+static void dla34_front(DlaCtx& c, std::vector<T>& layers, const bf16_t* x, int H, int W) {
   pt_engine* e = c.e;
   hipStream_t s = c.s;
   const int n = c.n;
@@ -114,7 +145,6 @@ static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
   // (lore_kernels.hip: dla_thin_chain_kernel; PT_DLA_CHAIN=0: the three launches, A/B switch read per call)
   const char* chain_env = getenv("PT_DLA_CHAIN");
   const bool chain = !c.x3 && H % 2 == 0 && W % 2 == 0 && !(chain_env && atoi(chain_env) == 0);
-  std::vector<T> layers(6);
   if (chain) {
     layers[1] = c.alloc(H / 2, W / 2, 32);
     const PtTensor *ws = c.get("base_layer.w"), *bs = c.get("base_layer.b"), *w0 = c.get("level0.wt"), *b0 = c.get("level0.bt"),
@@ -144,8 +174,22 @@ static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
       }
     }
   }
-  for (int l = 2; l < 6; ++l)
-    layers[l] = c.tree("level" + std::to_string(l), lv[l], layers[l - 1], ch[l - 1], ch[l], 2, l > 2, {});
+  layers[2] = c.tree("level2", lv[2], layers[1], ch[1], ch[2], 2, false, {});
+}
+
+// levels 3 .. 5 behind a front segment
+static void dla34_rest(DlaCtx& c, std::vector<T>& layers) {
+  const int ch[6] = {16, 32, 64, 128, 256, 512};
+  const int lv[6] = {1, 1, 1, 2, 2, 1};
+  for (int l = 3; l < 6; ++l)
+    layers[l] = c.tree("level" + std::to_string(l), lv[l], layers[l - 1], ch[l - 1], ch[l], 2, true, {});
+}
+
+// DLA.forward up to level5: layers[l] = output of level l (levels 0 and 1 only as far as the chosen path materialises them)
+static std::vector<T> dla34_base(DlaCtx& c, const bf16_t* x, int H, int W) {
+  std::vector<T> layers(6);
+  dla34_front(c, layers, x, H, W);
+  dla34_rest(c, layers);
   return layers;
 }
 

@@ -289,16 +289,9 @@ __global__ __launch_bounds__(256) void dwconvt_up2_add_kernel(const bf16_t* __re
 // (lore/processer_lore.py:85-90), sampling the table crop straight from the resident page.  OpenCV's WarpAffineInvoker
 // arithmetic: inverse map in fp64, 10-bit fixed-point coordinates, 1/32-pixel positions, 15-bit weights.
 // lut[c][v] = float(((v / 255.) - mean[c]) / std[c]) evaluated in fp64 on the host like numpy does.
-__global__ __launch_bounds__(256) void tsr_preprocess_kernel(const uint8_t* __restrict__ pages, int ph, int pw,
-                                                              const pt_tsr_table* __restrict__ tabs, int H, int W, int bgr,
-                                                              const float* __restrict__ lut, bf16_t* __restrict__ out,
-                                                              int split) {
-  a16_kernel_enter();
-  const int t = blockIdx.y;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= H * W) return;
-  const int y = i / W, x = i - y * W;
-  const pt_tsr_table tb = tabs[t];
+// destination pixel (x, y) of table `tb`, stored at o (4 values, 8 = hi | lo when split)
+__device__ __forceinline__ void tsr_warp_pixel(const uint8_t* __restrict__ pages, int ph, int pw, const pt_tsr_table& tb, int x, int y, int bgr,
+                                               const float* __restrict__ lut, bf16_t* __restrict__ o, int split) {
   auto sat = [](double v) { return (long long)fmin(fmax(rint(v), -2147483648.0), 2147483647.0); };
   const long long adelta = sat(tb.minv[0] * x * 1024.0), bdelta = sat(tb.minv[3] * x * 1024.0);
   const long long X0 = sat((tb.minv[1] * y + tb.minv[2]) * 1024.0) + 16, Y0 = sat((tb.minv[4] * y + tb.minv[5]) * 1024.0) + 16;
@@ -327,7 +320,6 @@ __global__ __launch_bounds__(256) void tsr_preprocess_kernel(const uint8_t* __re
     u = u < 0 ? 0 : (u > 255 ? 255 : u);
     v[c] = lut[c * 256 + u];
   }
-  bf16_t* o = out + ((size_t)t * H * W + i) * (split ? 8 : 4);
   uint32_t hb[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) { hb[c] = f2bf(v[c]); o[c] = (bf16_t)hb[c]; }
@@ -337,6 +329,62 @@ __global__ __launch_bounds__(256) void tsr_preprocess_kernel(const uint8_t* __re
     for (int c = 0; c < 3; ++c) o[4 + c] = (bf16_t)f2bf(v[c] - bf2f(hb[c]));
     o[7] = 0;
   }
+}
+
+__global__ __launch_bounds__(256) void tsr_preprocess_kernel(const uint8_t* __restrict__ pages, int ph, int pw,
+                                                              const pt_tsr_table* __restrict__ tabs, int H, int W, int bgr,
+                                                              const float* __restrict__ lut, bf16_t* __restrict__ out,
+                                                              int split) {
+  a16_kernel_enter();
+  const int t = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= H * W) return;
+  const int y = i / W, x = i - y * W;
+  tsr_warp_pixel(pages, ph, pw, tabs[t], x, y, bgr, lut, out + ((size_t)t * H * W + i) * (split ? 8 : 4), split);
+}
+
+// The same warp for runs of PT_TSR_BAND_ALIGN destination rows (blockIdx.y = run): rows [runs[r].y, + ALIGN) of table runs[r].x land at rows
+// runs[r].z ... of `out`, one tall image [rows, W, 4 | 8] -- whole maps and the row bands of the letterboxed tables, stacked (lore_model.hip)
+__global__ __launch_bounds__(256) void tsr_preprocess_rows_kernel(const uint8_t* __restrict__ pages, int ph, int pw,
+                                                                   const pt_tsr_table* __restrict__ tabs, const int4* __restrict__ runs, int H,
+                                                                   int W, int bgr, const float* __restrict__ lut, bf16_t* __restrict__ out,
+                                                                   int split) {
+  a16_kernel_enter();
+  const int4 r = runs[blockIdx.y];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= PT_TSR_BAND_ALIGN * W) return;
+  const int dy = i / W, x = i - dy * W;
+  if (r.y + dy >= H) return;
+  tsr_warp_pixel(pages, ph, pw, tabs[r.x], x, r.y + dy, bgr, lut, out + ((size_t)(r.z + dy) * W + x) * (split ? 8 : 4), split);
+}
+
+// one image of the warp's border value: source value 0 in every channel
+__global__ __launch_bounds__(256) void tsr_pad_image_kernel(const float* __restrict__ lut, int npix, bf16_t* __restrict__ out, int split) {
+  a16_kernel_enter();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= npix) return;
+  bf16_t* o = out + (size_t)i * (split ? 8 : 4);
+  uint32_t hb[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { hb[c] = f2bf(lut[c * 256]); o[c] = (bf16_t)hb[c]; }
+  o[3] = 0;
+  if (split) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[4 + c] = (bf16_t)f2bf(lut[c * 256] - bf2f(hb[c]));
+    o[7] = 0;
+  }
+}
+
+// `layers[2]` of n tables from the row bands the front segment ran on: map row r of table t is copied from its band where src[t] keeps it, from the
+// all-padding table's map `pad` elsewhere.  One workgroup per (table, row), 16 bytes per lane and step.
+__global__ __launch_bounds__(256) void tsr_band_assemble_kernel(const PtBandSrc* __restrict__ src, const bf16_t* __restrict__ pad,
+                                                                 bf16_t* __restrict__ out, int rows, int row_elems) {
+  a16_kernel_enter();
+  const int t = blockIdx.x / rows, r = blockIdx.x - t * rows;
+  const PtBandSrc b = src[t];
+  const bf16_t* from = (r >= b.k0 && r < b.k1) ? out + (b.off + (long long)(r - b.row0) * row_elems) : pad + (size_t)r * row_elems;
+  bf16_t* to = out + ((size_t)t * rows + r) * row_elems;
+  for (int i = threadIdx.x * 8; i < row_elems; i += 256 * 8) *reinterpret_cast<u32x4*>(to + i) = *reinterpret_cast<const u32x4*>(from + i);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -2036,6 +2084,35 @@ int pt_launch_tsr_preprocess(const uint8_t* pages, int ph, int pw, const pt_tsr_
   PT_REQUIRE(pages && tabs && lut && out && n > 0 && H > 0 && W > 0, "tsr preprocess: bad arguments");
   hipLaunchKernelGGL(tsr_preprocess_kernel, dim3((H * W + 255) / 256, n), dim3(256), 0, s, pages, ph, pw, tabs, H, W, bgr, lut,
                      out, split);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_launch_tsr_preprocess_rows(pt_engine* e, const uint8_t* pages, int ph, int pw, const pt_tsr_table* tabs, const int4* runs, int n_runs, int H, int W,
+                                  int bgr, const float* lut, bf16_t* out, int split, hipStream_t s) {
+  PT_REQUIRE(pages && tabs && runs && lut && out && n_runs > 0 && n_runs < 65536 && H > 0 && W > 0, "tsr preprocess rows: bad arguments");
+  const double px = (double)n_runs * PT_TSR_BAND_ALIGN * W;
+  e->prof.next_bytes = px * (split ? 16.0 : 8.0);      // the stored pixels; the crop's bytes depend on its scale
+  PtProfScope prof(e, s, PT_PROF_OTHER, 0, "tsr warp rows");
+  hipLaunchKernelGGL(tsr_preprocess_rows_kernel, dim3((PT_TSR_BAND_ALIGN * W + 255) / 256, n_runs), dim3(256), 0, s, pages, ph, pw, tabs, runs, H, W, bgr,
+                     lut, out, split);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_launch_tsr_pad_image(const float* lut, int H, int W, bf16_t* out, int split, hipStream_t s) {
+  PT_REQUIRE(lut && out && H > 0 && W > 0 && (long long)H * W < (1ll << 30), "tsr pad image: bad arguments");
+  hipLaunchKernelGGL(tsr_pad_image_kernel, dim3((H * W + 255) / 256), dim3(256), 0, s, lut, H * W, out, split);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_launch_tsr_band_assemble(pt_engine* e, const PtBandSrc* src, const bf16_t* pad, bf16_t* out, int n, int rows, int row_elems, hipStream_t s) {
+  PT_REQUIRE(src && pad && out && n > 0 && rows > 0 && row_elems > 0 && row_elems % 8 == 0 && (long long)n * rows < (1ll << 31),
+             "tsr band assemble: bad arguments");
+  e->prof.next_bytes = (double)n * rows * row_elems * 2.0 * 2.0;      // every row read once and written once
+  PtProfScope prof(e, s, PT_PROF_OTHER, 0, "tsr band assemble");
+  hipLaunchKernelGGL(tsr_band_assemble_kernel, dim3((unsigned)(n * rows)), dim3(256), 0, s, src, pad, out, rows, row_elems);
   PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }

@@ -11,9 +11,80 @@
 // out) -> dcn_im2col_kernel -> 1x1 GEMM over 9*C columns; the `up(x) + skip` add is fused into the up-sampler.
 // The 16-channel levels (base_layer, level0, level1) run on dedicated thin kernels and keep their real 16 channels.
 // The base and the launch context it runs on are shared with CenterNet's detector (dla_net.h).
+#include <math.h>
+#include <string.h>
+
 #include "dla_net.h"
 
 namespace PT_FMT_NS {
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Row bands of the front segment (include/pdftable_hip.h: pt_tsr_plan_bands).  The radius comes from dla_net.h's layer list.
+// ---------------------------------------------------------------------------------------------------------------------
+int pt_lore_band_radius() { return dla_front_radius(); }
+
+constexpr int kBandSlack = 2;               // rows added to the content on either side before anything else
+constexpr int kBandStackCap = 32768;        // input rows per stack: the largest map of the segment (32 channels at half size) is then 512 MiB
+
+int pt_lore_plan_bands(const pt_tsr_table* tabs, int n, int inp_h, int inp_w, int max_stack_rows, int margin, pt_tsr_band* out, int* n_stacks,
+                       double* row_fraction) {
+  PT_REQUIRE(tabs && out && n > 0 && inp_h > 0 && inp_w > 0 && inp_h % kFrontStride == 0, "tsr band plan: bad arguments");
+  const int R = margin < 0 ? dla_front_radius() : margin, AL = PT_TSR_BAND_ALIGN;
+  const int cap = (max_stack_rows <= 0 || max_stack_rows > kBandStackCap) ? kBandStackCap : max_stack_rows;
+  auto sat = [](double v) { return (long long)fmin(fmax(rint(v), -2147483648.0), 2147483647.0); };
+  int stack = -1, used = 0;
+  long long planned = 0;
+  for (int t = 0; t < n; ++t) {
+    const pt_tsr_table& tb = tabs[t];
+    pt_tsr_band b;
+    memset(&b, 0, sizeof(b));
+    b.full = 1; b.row1 = inp_h; b.keep1 = inp_h / kFrontStride; b.stack = -1;
+    // the rows tsr_preprocess_kernel can write anything but the border value to: its own arithmetic for the source row (no column term: minv[3] == 0)
+    int c0 = inp_h, c1 = -1;
+    // no rotation / shear term: none the kernel's 10-bit fixed point can see anywhere on the map (the host's 3-point solve leaves terms of 1e-17)
+    const bool axis = fabs(tb.minv[3]) * inp_w * 1024.0 < 0.5 && fabs(tb.minv[1]) * inp_h * 1024.0 < 0.5;
+    const bool letterbox = inp_h % AL == 0 && tb.crop_h < tb.crop_w && axis && tb.minv[4] > 0.0;
+    if (letterbox) {
+      // source row of destination row y; it does not fall as y grows (minv[4] > 0: products, sums and roundings are all monotone)
+      auto src_row = [&](int y) {
+        const long long Y = (sat((tb.minv[4] * y + tb.minv[5]) * 1024.0) + 16) >> 5;
+        const long long sy = Y >> 5;
+        return sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
+      };
+      // a row has one of its two source rows (sy, sy + 1) in the crop when -1 <= sy < crop_h: the first row with sy >= -1, the first with sy >= crop_h
+      auto first_at = [&](long long v) {
+        int lo = 0, hi = inp_h;
+        while (lo < hi) {
+          const int mid = (lo + hi) / 2;
+          if (src_row(mid) >= v) hi = mid;
+          else lo = mid + 1;
+        }
+        return lo;
+      };
+      c0 = first_at(-1);
+      c1 = first_at(tb.crop_h) - 1;
+    }
+    if (letterbox && c0 <= c1) {
+      const int lo = c0 - kBandSlack - 2 * R, hi = c1 + 1 + kBandSlack + 2 * R;
+      const int A = lo >= 0 ? lo / AL * AL : -AL, B = (hi + AL - 1) / AL * AL;
+      // a window that meets the map's first or last AL rows runs the whole map: there the convolutions' zero padding is part of the result
+      if (A >= AL && B <= inp_h - AL && B - A <= cap) {
+        b.full = 0; b.row0 = A; b.row1 = B;
+        // map row r (input row 4 r) sees input rows 4 r - R .. 4 r + R
+        b.keep0 = (c0 - kBandSlack - R + kFrontStride - 1) / kFrontStride;
+        b.keep1 = (c1 + kBandSlack + R) / kFrontStride + 1;
+        if (stack < 0 || used + (B - A) > cap) { ++stack; used = 0; }
+        b.stack = stack; b.stack_row = used;
+        used += B - A;
+      }
+    }
+    planned += b.row1 - b.row0;
+    out[t] = b;
+  }
+  if (n_stacks) *n_stacks = stack + 1;
+  if (row_fraction) *row_fraction = (double)planned / ((double)n * inp_h);
+  return PT_OK;
+}
 
 int pt_launch_dcn_im2col(const bf16_t* x, const float* om, bf16_t* cols, int B, int H, int W, int C, int split,
                          hipStream_t s);
@@ -107,6 +178,146 @@ struct Ctx : DlaCtx {
 
 // x: NHWC4 bf16 [n, H, W, 4] ([hi rgb0 | lo rgb0] in BF16X3 mode); heads: fp32 NHWC at H/4 x W/4 with channel
 // strides 8 (hm: 2 valid), 8 (st), 8 (wh), 256 (ax), 256 (cr), 8 (reg: 2 valid)
+struct BandArgs {        // warp inside the call (pt_lore_warp_forward_decode): the tables on both sides, the pages they are cut from
+  const uint8_t* pages;
+  int ph, pw;
+  const pt_tsr_table *h_tabs, *d_tabs;
+  int bgr, bands, margin;
+  bf16_t* l2_out;        // test hook: stop behind level 2
+};
+
+// [3][256] ((v / 255.) - mean) / std in float64 then cast, as numpy evaluates processer_lore.py:67-70,90
+int pt_lore_norm_lut(pt_engine* e, const float** lut_out) {
+  if (!e->tsr_lut) {
+    const float mean[3] = {0.408f, 0.447f, 0.470f}, stdv[3] = {0.289f, 0.274f, 0.278f};
+    float lut[768];
+    for (int c = 0; c < 3; ++c)
+      for (int v = 0; v < 256; ++v) lut[c * 256 + v] = (float)(((double)v / 255.0 - (double)mean[c]) / (double)stdv[c]);
+    PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->tsr_lut), sizeof(lut)));
+    PT_HIP_CHECK(hipMemcpy(e->tsr_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
+  }
+  *lut_out = e->tsr_lut;
+  return PT_OK;
+}
+
+// host array -> device (arena) behind the launches queued so far, through the engine's pinned ring of band tables
+static int upload_small(pt_engine* e, void* d_dst, const void* h_src, size_t bytes, hipStream_t s) {
+  void* hs = e->band_ring.acquire(bytes);
+  PT_REQUIRE(hs, "Lore net: pinned staging allocation failed");
+  memcpy(hs, h_src, bytes);
+  PT_HIP_CHECK(hipMemcpyAsync(d_dst, hs, bytes, hipMemcpyHostToDevice, s));
+  PT_REQUIRE(e->band_ring.release(s) == 0, "Lore net: event record failed");
+  return PT_OK;
+}
+
+// The front segment with the letterbox rows left out: warp the planned rows (whole maps of the `full` tables, then the bands, stacked into tall
+// one-image inputs), run base_layer .. level2 on the full group and on every stack, and assemble `layers[2]` of all n tables from the bands' kept rows
+// and the cached map of an all-padding table.  `in`: [n * H, W, 4 | 8] from the arena.  Returns the assembled map in layers[2].
+static int lore_band_front(Ctx& c, std::vector<T>& layers, const BandArgs& bd, const std::vector<pt_tsr_band>& plan, int n_stacks, const float* lut,
+                           bf16_t* in, int H, int W) {
+  pt_engine* e = c.e;
+  hipStream_t s = c.s;
+  const int n = c.n, px = 4 * c.mul, AL = PT_TSR_BAND_ALIGN, rows4 = H / kFrontStride, row_elems = W / kFrontStride * 64 * c.mul;
+  // where everything lies in `in`: the full tables' maps first, then the stacks
+  std::vector<int> stack_rows(n_stacks, 0), stack_off(n_stacks, 0), full_idx(n, -1);
+  int nf = 0;
+  for (int t = 0; t < n; ++t) {
+    if (plan[t].full) full_idx[t] = nf++;
+    else stack_rows[plan[t].stack] += plan[t].row1 - plan[t].row0;
+  }
+  for (int k = 0, off = nf * H; k < n_stacks; off += stack_rows[k], ++k) stack_off[k] = off;
+  const int runs_max = n * ((H + AL - 1) / AL);      // the all-full case: device tables and arena use do not depend on the plan
+  int4* d_runs = c.take<int4>((size_t)runs_max * sizeof(int4));
+  PtBandSrc* d_src = c.take<PtBandSrc>((size_t)n * sizeof(PtBandSrc));
+  T l2 = c.alloc(rows4, W / kFrontStride, 64);
+  const size_t o1 = c.mark();
+  {      // what the segment takes when every table runs in full: the arena is sized for that
+    const bool dry = c.dry;
+    c.dry = true;
+    std::vector<T> tmp(6);
+    dla34_front(c, tmp, in, H, W);
+    c.dry = dry;
+  }
+  const size_t worst = c.mark() + (64u << 10);      // (+ the alignment gaps of the few more takes several groups make)
+  c.rewind(o1);
+  if (c.go()) {
+    std::vector<int4> runs;
+    runs.reserve(runs_max);
+    for (int t = 0; t < n; ++t) {
+      const pt_tsr_band& b = plan[t];
+      const int dst = b.full ? full_idx[t] * H : stack_off[b.stack] + b.stack_row;
+      for (int y = b.row0; y < b.row1; y += AL) runs.push_back(int4{t, y, dst + (y - b.row0), 0});
+    }
+    PT_REQUIRE((int)runs.size() <= runs_max, "Lore net: band plan larger than the batch");
+    int r = upload_small(e, d_runs, runs.data(), runs.size() * sizeof(int4), s);
+    if (r == PT_OK) r = pt_launch_tsr_preprocess_rows(e, bd.pages, bd.ph, bd.pw, bd.d_tabs, d_runs, (int)runs.size(), H, W, bd.bgr, lut, in, c.x3, s);
+    if (r != PT_OK) return r;
+  }
+  // every group chooses its kernels as the whole batch does
+  c.pick_n = n; c.whole_H = H;
+  // the all-padding table's level-2 map: once per (weights, precision, input size, kernel family of the 64 -> 64 layers)
+  const int pi = e->precision & 3;
+  const int key[3] = {H, W, (!c.x3 && pt_conv_takes_ws64(e, n, rows4, W / kFrontStride)) ? 1 : 0};
+  const size_t pad_bytes = (size_t)rows4 * row_elems * sizeof(bf16_t);
+  if (!e->tsr_pad_l2_valid[pi] || memcmp(e->tsr_pad_l2_key[pi], key, sizeof(key)) != 0) {
+    c.n = 1; c.part_H = H;
+    bf16_t* pin = c.take<bf16_t>((size_t)H * W * px * sizeof(bf16_t));
+    if (c.go()) {
+      if (e->tsr_pad_l2_cap[pi] < pad_bytes) {
+        if (e->tsr_pad_l2[pi]) PT_HIP_CHECK(hipFree(e->tsr_pad_l2[pi]));      // (waits for the device: nobody reads the old block any more)
+        e->tsr_pad_l2[pi] = nullptr; e->tsr_pad_l2_cap[pi] = 0;
+        PT_HIP_CHECK(hipMalloc(&e->tsr_pad_l2[pi], pad_bytes));
+        e->tsr_pad_l2_cap[pi] = pad_bytes;
+      }
+      const int r = pt_launch_tsr_pad_image(lut, H, W, pin, c.x3, s);
+      if (r != PT_OK) return r;
+    }
+    std::vector<T> pl(6);
+    dla34_front(c, pl, pin, H, W);
+    if (c.go()) {
+      PT_HIP_CHECK(hipMemcpyAsync(e->tsr_pad_l2[pi], pl[2].p, pad_bytes, hipMemcpyDeviceToDevice, s));
+      e->tsr_pad_l2_valid[pi] = true;
+      memcpy(e->tsr_pad_l2_key[pi], key, sizeof(key));
+      // later calls may run on another stream: they wait for this build through the event
+      if (!e->tsr_pad_l2_ready[pi]) PT_HIP_CHECK(hipEventCreateWithFlags(&e->tsr_pad_l2_ready[pi], hipEventDisableTiming));
+      PT_HIP_CHECK(hipEventRecord(e->tsr_pad_l2_ready[pi], s));
+    }
+    c.n = n;
+    c.rewind(o1);
+  } else if (c.go() && e->tsr_pad_l2_ready[pi]) {
+    PT_HIP_CHECK(hipStreamWaitEvent(s, e->tsr_pad_l2_ready[pi], 0));      // a no-op once the build has completed
+  }
+  T full_l2;
+  std::vector<T> stack_l2(n_stacks);
+  if (nf) {
+    c.n = nf; c.part_H = H;
+    std::vector<T> fl(6);
+    dla34_front(c, fl, in, H, W);
+    full_l2 = fl[2];
+  }
+  for (int k = 0; k < n_stacks; ++k) {
+    c.n = 1; c.part_H = stack_rows[k];
+    std::vector<T> sl(6);
+    dla34_front(c, sl, in + (size_t)stack_off[k] * W * px, stack_rows[k], W);
+    stack_l2[k] = sl[2];
+  }
+  c.n = n; c.pick_n = 0;
+  if (c.go()) {
+    std::vector<PtBandSrc> src(n);
+    for (int t = 0; t < n; ++t) {
+      const pt_tsr_band& b = plan[t];
+      if (b.full) src[t] = PtBandSrc{(full_l2.p - l2.p) + (long long)full_idx[t] * rows4 * row_elems, 0, 0, rows4, 0};
+      else src[t] = PtBandSrc{(stack_l2[b.stack].p - l2.p) + (long long)(b.stack_row / kFrontStride) * row_elems, b.row0 / kFrontStride, b.keep0, b.keep1, 0};
+    }
+    int r = upload_small(e, d_src, src.data(), src.size() * sizeof(PtBandSrc), s);
+    if (r == PT_OK) r = pt_launch_tsr_band_assemble(e, d_src, reinterpret_cast<const bf16_t*>(e->tsr_pad_l2[pi]), l2.p, n, rows4, row_elems, s);
+    if (r != PT_OK) return r;
+  }
+  c.reserve_to(worst);
+  layers[2] = l2;
+  return PT_OK;
+}
+
 struct SparseArgs {      // fused forward + decode: the ax / cr heads run on patch mosaics around the decoded positions
   int wiz_rev;
   float vis_thresh;
@@ -115,11 +326,28 @@ struct SparseArgs {      // fused forward + decode: the ax / cr heads run on pat
 };
 
 static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, float* hm, float* st, float* wh, float* ax,
-                        float* cr, float* reg, const SparseArgs* sp, hipStream_t s) {
+                        float* cr, float* reg, const SparseArgs* sp, hipStream_t s, const BandArgs* bd = nullptr) {
   PT_REQUIRE(H % 32 == 0 && W % 32 == 0 && H > 0 && W > 0, "Lore net: input %dx%d must be multiples of 32", H, W);
-  PT_REQUIRE(x && n > 0 && (sp || (hm && st && wh && ax && cr && reg)), "Lore net: null pointer");
+  PT_REQUIRE((x || bd) && n > 0 && (sp || (bd && bd->l2_out) || (hm && st && wh && ax && cr && reg)), "Lore net: null pointer");
   const PtModel* m = pt_find_model(e, PT_MODEL_LORE_DLA34, "Lore DLA-34", "PT_MODEL_LORE_DLA34");
   if (!m) return PT_ERR_STATE;
+  // warp inside the call: the row bands the front segment needs, planned on the host
+  const float* lut = nullptr;
+  std::vector<pt_tsr_band> plan;
+  int n_stacks = 0, n_banded = 0;
+  if (bd) {
+    const int r = pt_lore_norm_lut(e, &lut);
+    if (r != PT_OK) return r;
+  }
+  if (bd && bd->bands) {
+    const char* cap_env = getenv("PT_TSR_BAND_STACK_ROWS");      // tests: a low cap splits a batch into several stacks (read per call)
+    int cap = kBandStackCap / (pt_split(e) ? 2 : 1);             // the pair modes' maps are twice the bytes
+    if (cap_env && atoi(cap_env) > 0 && atoi(cap_env) < cap) cap = atoi(cap_env);
+    plan.resize(n);
+    const int r = pt_lore_plan_bands(bd->h_tabs, n, H, W, cap, bd->margin, plan.data(), &n_stacks, nullptr);
+    if (r != PT_OK) return r;
+    for (int t = 0; t < n; ++t) n_banded += plan[t].full ? 0 : 1;
+  }
   Ctx c;
   c.init(e, m, "Lore DLA-34", s, n, PT_ARENA_TSR);
   float* heads[6] = {hm, st, wh, ax, cr, reg};
@@ -133,7 +361,27 @@ static int lore_dla_run(pt_engine* e, const bf16_t* x, int n, int H, int W, floa
     c.cols = c.take<bf16_t>(px4 * 576 * c.mul * sizeof(bf16_t));
     c.om = c.take<float>(px4 * 32 * sizeof(float));
 
-    std::vector<T> layers = dla34_base(c, x, H, W);
+    std::vector<T> layers(6);
+    if (!bd) {
+      dla34_front(c, layers, x, H, W);
+    } else {
+      bf16_t* in = c.take<bf16_t>((size_t)n * H * W * 4 * c.mul * sizeof(bf16_t));
+      if (n_banded) {
+        const int r = lore_band_front(c, layers, *bd, plan, n_stacks, lut, in, H, W);
+        if (r != PT_OK) return r;
+      } else {      // nothing to skip (or PT_TSR_BANDS off in the hook): the warp and the segment on whole maps
+        if (c.go()) {
+          const int r = pt_launch_tsr_preprocess(bd->pages, bd->ph, bd->pw, bd->d_tabs, n, H, W, bd->bgr, lut, in, c.x3, s);
+          if (r != PT_OK) return r;
+        }
+        dla34_front(c, layers, in, H, W);
+      }
+      if (bd->l2_out) {
+        if (c.go()) PT_HIP_CHECK(hipMemcpyAsync(bd->l2_out, layers[2].p, (size_t)n * (H / 4) * (W / 4) * 64 * c.mul * sizeof(bf16_t), hipMemcpyDeviceToDevice, s));
+        return c.rc;
+      }
+    }
+    dla34_rest(c, layers);
 
     // DLAUp.forward (lore_dla_34.py:128-134): ida_0 on [4,6), ida_1 on [3,6), ida_2 on [2,6)
     std::vector<T> out = {layers[5]};
@@ -254,6 +502,16 @@ int pt_lore_forward_decode(pt_engine* e, const bf16_t* x, int n, int H, int W, i
   PT_REQUIRE(d_counts && d_dets && d_logi, "Lore forward+decode: null pointer");
   SparseArgs sp{wiz_rev, vis_thresh, d_counts, d_dets, d_logi};
   return lore_dla_run(e, x, n, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &sp, s);
+}
+
+// warp + forward + decode with the tables known on the host: the front segment skips the letterbox rows (lore_band_front)
+int pt_lore_warp_forward_decode(pt_engine* e, const uint8_t* pages, int ph, int pw, const pt_tsr_table* h_tabs, const pt_tsr_table* d_tabs, int n, int H,
+                                int W, int bgr, int bands, int margin, int wiz_rev, float vis_thresh, int* d_counts, float* d_dets, float* d_logi,
+                                bf16_t* l2_out, hipStream_t s) {
+  PT_REQUIRE(pages && h_tabs && d_tabs && ph > 0 && pw > 0 && (l2_out || (d_counts && d_dets && d_logi)), "Lore warp+forward+decode: null pointer");
+  SparseArgs sp{wiz_rev, vis_thresh, d_counts, d_dets, d_logi};
+  BandArgs bd{pages, ph, pw, h_tabs, d_tabs, bgr, bands, margin, l2_out};
+  return lore_dla_run(e, nullptr, n, H, W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, l2_out ? nullptr : &sp, s, &bd);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -75,6 +75,17 @@ struct NetCtx {
     if (!p) ok = false;
     return p;
   }
+  // a stretch of the arena used twice: mark(), takes, rewind(mark); reserve_to(off): the arena counts as used up to `off` (a worst case planned for,
+  // whatever this call took), so that its high-water mark does not depend on the call's data
+  size_t mark() const { return e->arenas[arena].off; }
+  void rewind(size_t off) { e->arenas[arena].off = off; }
+  void reserve_to(size_t off) {
+    PtArena& A = e->arenas[arena];
+    if (off <= A.off) return;
+    if (off > A.cap) ok = false;
+    A.off = off;
+    if (off > A.high) A.high = off;
+  }
   T alloc(int H, int W, int C) {
     T t;
     t.H = H; t.W = W; t.C = C;

@@ -300,6 +300,56 @@ class HipEngine:
                                                _ptr(dets), _ptr(logi), self._stream()), "pt_tsr_forward_decode")
         return (counts.cpu().numpy() if sync else counts), dets, logi
 
+    def tsr_band_radius(self) -> int:
+        """receptive-field radius, in input rows, of the DLA-34 front segment (base_layer .. level2)"""
+        return int(self.lib.pt_tsr_band_radius())
+
+    def tsr_plan_bands(self, tables, inp_h: int = 1024, inp_w: int = 1024, max_stack_rows: int = 0):
+        """pt_tsr_plan_bands (host arithmetic of the library): tables numpy TSR_TABLE_DTYPE -> (bands int32 [n, 8] = full, row0, row1,
+        keep0, keep1, stack, stack_row, reserved; number of stacks; fraction of the n * inp_h rows planned)"""
+        tb = np.ascontiguousarray(tables)
+        n = len(tb)
+        out = np.zeros((n, 8), np.int32)
+        ns, frac = C.c_int(0), C.c_double(0.0)
+        L.check(self.lib.pt_tsr_plan_bands(tb.ctypes.data, n, inp_h, inp_w, int(max_stack_rows), out.ctypes.data, C.byref(ns), C.byref(frac)),
+                "pt_tsr_plan_bands")
+        return out, int(ns.value), float(frac.value)
+
+    def tsr_warp_forward_decode(self, pages: torch.Tensor, tables, inp_h: int = 1024, inp_w: int = 1024, bgr: bool = True, wiz_rev: bool = True,
+                                vis_thresh: float = 0.2, sync: bool = True, out=None):
+        """tsr_preprocess + tsr_forward_decode in one call (pt_tsr_warp_forward_decode): the detector's front segment runs on the row bands the
+        letterboxed crops fill.  pages uint8 [np,h,w,3] on the device, tables numpy TSR_TABLE_DTYPE; out as for tsr_forward_decode."""
+        self._chk(pages, torch.uint8, "pages")
+        npg, ph, pw, _ = pages.shape
+        tb_h = np.ascontiguousarray(tables)
+        n = len(tb_h)
+        tb = _upload(tb_h.view(np.uint8).reshape(n, -1), self._tdev)
+        if out is not None:
+            counts, dets, logi = out
+            assert counts.shape == (n,) and dets.shape == (n, L.PT_TSR_MAX_CELLS, 9) and logi.shape == (n, L.PT_TSR_MAX_CELLS, 256)
+            assert counts.is_contiguous() and dets.is_contiguous() and logi.is_contiguous()
+        else:
+            counts = torch.zeros((n,), dtype=torch.int32, device=self._tdev)
+            dets = torch.empty((n, L.PT_TSR_MAX_CELLS, 9), dtype=torch.float32, device=self._tdev)
+            logi = torch.empty((n, L.PT_TSR_MAX_CELLS, 256), dtype=torch.float32, device=self._tdev)
+        L.check(self.lib.pt_tsr_warp_forward_decode(self._h, _ptr(pages), npg, ph, pw, tb_h.ctypes.data, _ptr(tb), n, inp_h, inp_w, int(bgr),
+                                                    int(wiz_rev), float(vis_thresh), _ptr(counts), _ptr(dets), _ptr(logi), self._stream()),
+                "pt_tsr_warp_forward_decode")
+        return (counts.cpu().numpy() if sync else counts), dets, logi
+
+    def op_tsr_level2(self, pages: torch.Tensor, tables, inp_h: int, inp_w: int, bgr: bool = True, bands: bool = True, margin: int = -1):
+        """pt_op_tsr_level2 (test hook): `layers[2]` of the DLA-34 base for the table crops, [n, inp_h/4, inp_w/4, 64 | 128] in the activation format;
+        bands=False: on whole maps; margin >= 0 plans the bands with that radius (wrong below tsr_band_radius())."""
+        self._chk(pages, torch.uint8, "pages")
+        npg, ph, pw, _ = pages.shape
+        tb_h = np.ascontiguousarray(tables)
+        n = len(tb_h)
+        tb = _upload(tb_h.view(np.uint8).reshape(n, -1), self._tdev)
+        out = torch.empty((n, inp_h // 4, inp_w // 4, 128 if self.split else 64), dtype=self.act_dtype, device=self._tdev)
+        L.check(self.lib.pt_op_tsr_level2(self._h, _ptr(pages), npg, ph, pw, tb_h.ctypes.data, _ptr(tb), n, inp_h, inp_w, int(bgr), int(bands),
+                                          int(margin), _ptr(out), self._stream()), "pt_op_tsr_level2")
+        return out
+
     def centernet_forward_net(self, x: torch.Tensor):
         """CenterNet table-cell detector (DLA-34 + DLAUp, PT_MODEL_CENTERNET_DLA34): x bf16 NHWC4 [n,H,W,4] (BF16X3: 8 channels) -> dict of
         fp32 NHWC head maps at H/4 x W/4 ({'hm': [n,h,w,2] pre-sigmoid, 'v2c': [.,8], 'c2v': [.,8], 'reg': [.,2]}; hm / reg are views of

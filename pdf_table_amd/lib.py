@@ -105,6 +105,10 @@ def _proto(lib):
         "pt_tsr_forward_net_wireless": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp]),
         "pt_tsr_decode": (i, [vp, vp, vp, vp, vp, vp, vp, i, i, i, i, f, vp, vp, vp, vp]),
         "pt_tsr_forward_decode": (i, [vp, vp, i, i, i, i, f, vp, vp, vp, vp]),
+        "pt_tsr_band_radius": (i, []),
+        "pt_tsr_plan_bands": (i, [vp, i, i, i, i, vp, ip, vp]),
+        "pt_tsr_warp_forward_decode": (i, [vp, vp, i, i, i, vp, vp, i, i, i, i, i, f, vp, vp, vp, vp]),
+        "pt_op_tsr_level2": (i, [vp, vp, i, i, i, vp, vp, i, i, i, i, i, i, vp, vp]),
         "pt_tsr_process": (i, [vp, vp, vp, vp, i, i, vp, vp, vp]),
         "pt_centernet_forward_net": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp]),
         "pt_centernet_decode": (i, [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]),

@@ -204,9 +204,16 @@ class TsrStage:
             logi_all = torch.empty((nt, L.PT_TSR_MAX_CELLS, 256), dtype=torch.float32, device=dev)
         for i in range(0, len(tables), size):
             tb = tables[i:i + size]
+            out = (counts_all[i:i + len(tb)], dets_all[i:i + len(tb)], logi_all[i:i + len(tb)]) if fused and nmb > 1 else None
+            if fused and os.environ.get("PT_TSR_BANDS", "1") != "0":
+                # warp + net + decode in one call with the tables known to the library: the detector's front segment skips the letterbox rows of
+                # crops wider than high (PT_TSR_BANDS=0, read per call: the two calls below, A/B switch)
+                counts, dets, logi = self.eng.tsr_warp_forward_decode(pages, tb, inp_h, inp_w, bgr=self.bgr, wiz_rev=cfg.wiz_rev,
+                                                                      vis_thresh=cfg.vis_thresh, sync=False, out=out)
+                pending.append((i, len(tb), counts, dets, logi))
+                continue
             x = self.eng.tsr_preprocess(pages, tb, inp_h, inp_w, bgr=self.bgr)
             if fused:      # one call, ax / cr heads only where the decode reads them
-                out = (counts_all[i:i + len(tb)], dets_all[i:i + len(tb)], logi_all[i:i + len(tb)]) if nmb > 1 else None
                 counts, dets, logi = self.eng.tsr_forward_decode(x, wiz_rev=cfg.wiz_rev, vis_thresh=cfg.vis_thresh, sync=False, out=out)
             else:
                 heads = self.eng.tsr_forward_net(x, wireless=cfg.backbone == "ResNet-18")
