@@ -720,6 +720,20 @@ int pt_slanet_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, 
  * is launched).  One launch, no allocation, no host synchronisation (capturable). */
 int pt_op_table_match(const float* d_loc, const int32_t* d_ids, const int32_t* d_steps, int B, int T, int L, const uint8_t* d_cell_flags, int V,
                       const float* d_frames, const float* d_lines, const int32_t* d_offsets, int M, int32_t* d_out, pt_stream stream);
+/* Text lines -> cells of Lore tables (csrc/lore_match.hip, compiled once, engine-free; added under ABI 20: one new entry point, no existing signature
+ * changed, so the version stays): OcrTableToHtmlTask's find_top1_mach_box over the outputs of pt_tsr_decode and pt_tsr_process while they are on the
+ * device.  d_dets fp32 [B, PT_TSR_MAX_CELLS, 9] (the quads BEFORE the map back to source pixels), d_axes fp32 [B, PT_TSR_MAX_CELLS, 4] the final logical
+ * axes [left, right, top, bottom], unrounded, d_counts int32 [B] (clamped to 0 .. PT_TSR_MAX_CELLS; rows at and beyond the count are never read).
+ * d_affine fp64 [B, 6]: per table the inverse 2x3 map (t00 t01 t02 t10 t11 t12); d_offset fp64 [B, 2]: the crop's (x0, y0) on its page.  A vertex is
+ * fl32((t00 px + t01 py) + t02) (y alike) plus the offset in double; the cell box is (bottom-left, top-right) = (vertex 3, vertex 1); an axis rounds up
+ * where its fraction is > 0.5 (float32).  d_lines fp32 [M, 4] (min x, min y, max x, max y; 16-byte aligned) grouped by table, d_offsets int32 [B + 1] as
+ * for pt_op_table_match (no index outside [0, M) is ever touched).  d_out int32 [M]: per line the ROW INDEX of its cell -- the first cell, in the
+ * order sorted by (top, left, bottom, right, row), that contains the line grown by 2 pixels, else the first minimum of (1 - iou, corner distance), all
+ * in double as table_text_match.find_top1_match computes them -- or -1 in a table whose clamped count is 0.  1 <= B <= 65535, M >= 0 (0: nothing is
+ * launched).  One launch of one workgroup per table with 96,000 bytes of LDS: the first call on a device raises the kernel's LDS limit (a host-side
+ * setting) and returns PT_ERR_STATE inside a stream capture, so call once before capturing.  No allocation, no host synchronisation. */
+int pt_op_lore_match(const float* d_dets, const float* d_axes, const int32_t* d_counts, int B, const double* d_affine, const double* d_offset,
+                     const float* d_lines, const int32_t* d_offsets, int M, int32_t* d_out, pt_stream stream);
 
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------

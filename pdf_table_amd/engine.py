@@ -1232,6 +1232,34 @@ class HipEngine:
                                            _ptr(offsets), M, _ptr(out), self._stream()), "pt_op_table_match")
         return out
 
+    def op_lore_match(self, dets: torch.Tensor, axes: torch.Tensor, counts: torch.Tensor, affine: torch.Tensor, offset: torch.Tensor,
+                      lines: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+        """Text lines -> cell rows of Lore tables, in one launch (pt_op_lore_match, csrc/lore_match.hip): table_text_match.find_top1_match over the
+        cells table_cells_from_logits would build, on the device.  dets float32 [B, PT_TSR_MAX_CELLS, 9] (tsr_decode) / axes float32
+        [B, PT_TSR_MAX_CELLS, 4] (tsr_process: ``stacked`` or ``logic``, unrounded) / counts int32 [B]; affine float64 [B, 6]: the inverse map
+        transform_quads builds, per table; offset float64 [B, 2]: the crop's (x0, y0); lines float32 [M, 4] grouped by table and offsets int32
+        [B + 1] (0 .. M, non-decreasing) -> int32 [M]: per line the INPUT row index of its cell, -1 in a table without cells.  Everything stays
+        on the device; nothing synchronises."""
+        self._chk(dets, torch.float32, "dets")
+        self._chk(axes, torch.float32, "axes")
+        self._chk(counts, torch.int32, "counts")
+        self._chk(affine, torch.float64, "affine")
+        self._chk(offset, torch.float64, "offset")
+        self._chk(lines, torch.float32, "lines")
+        self._chk(offsets, torch.int32, "offsets")
+        if dets.dim() != 3 or tuple(dets.shape[1:]) != (L.PT_TSR_MAX_CELLS, 9) or tuple(axes.shape) != (dets.shape[0], L.PT_TSR_MAX_CELLS, 4):
+            raise ValueError(f"op_lore_match: dets must be [B, {L.PT_TSR_MAX_CELLS}, 9] and axes [B, {L.PT_TSR_MAX_CELLS}, 4], got {tuple(dets.shape)} "
+                             f"and {tuple(axes.shape)}")
+        B = dets.shape[0]
+        M = lines.numel() // 4
+        if lines.numel() != 4 * M or counts.numel() != B or affine.numel() != 6 * B or offset.numel() != 2 * B or offsets.numel() != B + 1:
+            raise ValueError(f"op_lore_match: {B} tables need counts [B], affine [B, 6], offset [B, 2], offsets [B + 1] and lines [M, 4]; got "
+                             f"{tuple(counts.shape)}, {tuple(affine.shape)}, {tuple(offset.shape)}, {tuple(offsets.shape)}, {tuple(lines.shape)}")
+        out = torch.empty((M,), dtype=torch.int32, device=self._tdev)
+        L.check(self.lib.pt_op_lore_match(_ptr(dets), _ptr(axes), _ptr(counts), B, _ptr(affine), _ptr(offset), _ptr(lines), _ptr(offsets), M,
+                                          _ptr(out), self._stream()), "pt_op_lore_match")
+        return out
+
     def op_attention(self, qkv: torch.Tensor, heads: int, d: int, scale: float, out_c: int, split: bool = False) -> torch.Tensor:
         """qkv bf16 [B, 1, T, >= 3 heads d] rows of [q | k | v] -> bf16 [B, 1, T, out_c] (channels heads * d .. out_c are zero); split: both tensors
         carry [hi | lo] halves of that width"""

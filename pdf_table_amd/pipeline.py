@@ -78,12 +78,20 @@ class OcrTablePipeline:
                  precision: str = "bf16", layout_precision: Optional[str] = None, deskew: bool = False,
                  sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
                  table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
-                 rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, **kwargs):
+                 rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, device_match: bool = False, **kwargs):
         if table_structure_model == "SLANet" and not tsr_task_path:
             # the ONNX-only model has no in-tree (seeded) weights: without its directory there is nothing to serve.  Refused here, before any
             # engine exists, not on the first page
             raise ValueError("table_structure_model='SLANet' without tsr_task_path=<dir with model.onnx and table_structure_dict[_ch].txt> is out "
                              "of scope for OcrTablePipeline: the model is ONNX-only, there are no seeded weights for it")
+        if device_match and table_structure_model != "Lore":
+            # SLANet's stage matches on the device already, MtlTabNet / TableMaster make their polygons on the host, CenterNet has no HTML
+            raise ValueError(f"device_match=True assigns text lines to the cells of the Lore structure model on the device (pt_op_lore_match); "
+                             f"table_structure_model={table_structure_model!r} has no such route")
+        # device_match=True (with table_html=True and table_structure=True): the Lore stage assigns every table's candidate lines to its cells
+        # on the device, behind the processor (TsrStage.process(match=...)); _attach_html then skips find_top1_match.  Off by default: the
+        # table dicts then carry no 'matched' / 'matched_lines' keys
+        self.device_match = bool(device_match)
         # which route _attach_html takes for results without logical locations (tokens + one box per cell): SLANet's lines are matched on the
         # device by its stage, MtlTabNet / TableMaster on the host with use_master (tsr_match_need_use_master)
         self.table_structure_model = table_structure_model
@@ -191,13 +199,17 @@ class OcrTablePipeline:
     @classmethod
     def from_engine(cls, engine: HipEngine, det_stage: DetStage, rec_stage, layout_stage=None, tsr_stage=None, table_html: bool = False,
                     overlap_rec: bool = False, aux_layout: bool = False, tsr_on_aux: bool = False, lookahead: int = 1,
-                    orientation_stage=None) -> "OcrTablePipeline":
+                    orientation_stage=None, device_match: bool = False) -> "OcrTablePipeline":
         """The façade over an engine whose weights are ALREADY loaded -- e.g. packed once on rank 0, broadcast over RCCL and loaded from
         device memory on every rank (dist_utils.broadcast_blob, ``bench.py --gpus N``) -- and over stage objects the caller built on it.
         ``predict()`` / ``predict_stream()`` are the same code as after the ordinary constructor.  ``orientation_stage``: a ClsStage of the
         "textline_orientation" task on that engine: the text-line orientation vote (what ``text_orientation=True`` attaches)."""
         import types
+        from .tsr_stage import TsrStage
+        if device_match and not isinstance(tsr_stage, TsrStage):
+            raise ValueError(f"device_match=True needs a Lore stage (TsrStage: pt_op_lore_match), not {type(tsr_stage).__name__}")
         self = cls.__new__(cls)
+        self.device_match = bool(device_match)
         self.engine, self.overlap_rec, self.rotate_upside_down, self._rec_stream = engine, overlap_rec, True, None
         self.table_html, self.orientation_task, self.aux_layout, self.tsr_on_aux = table_html, None, aux_layout, tsr_on_aux
         self.lookahead = lookahead
@@ -679,11 +691,16 @@ class OcrTablePipeline:
                     # cannot be re-used by the caching allocator when it is freed: every batch then paid a hipMalloc (a device-wide
                     # synchronisation) for its successor (measured: 443-462 -> pages/s of the private loop)
                 st["tsr"] = (pending, metas, offs, ev)
+                # device_match: the candidate lines of these tables, chosen now that the batch's boxes are known (after the orientation
+                # vote: those of the second pass); process_tables() uploads them and queues the match behind the processor
+                st["tsr_match"] = (tsr_stage.match_input(tables, metas, tb, self._match_on_device(st["boxes"])["text_boxes"])
+                                   if lore_match and pending is not None else None)
 
         # Lore / CenterNet: start / process / collect; MtlTabNet: one synchronous call; SLANet (start / finish only) goes the synchronous way too, in
         # collect(), where the batch's text boxes are known and its lines can be matched on the device
         staged_tsr = tsr_stage is not None and hasattr(tsr_stage, "start") and hasattr(tsr_stage, "process")
         tsr_on_aux = bool(getattr(self, "tsr_on_aux", False))
+        lore_match = staged_tsr and self._lore_match_on_device()
 
         def process_tables(st):
             """device half 2 of the table stage for a batch whose decode was queued one step ago: cell counts from pinned memory (waits
@@ -693,13 +710,14 @@ class OcrTablePipeline:
                 return
             pending, ev = st["tsr"][0], st["tsr"][3]
             w0 = getattr(tsr_stage, "wait_s", 0.0)
+            mkw = {"match": st["tsr_match"]} if st.get("tsr_match") is not None else {}
             if tsr_on_aux:
                 with torch.cuda.stream(aux):      # behind the decode of THESE tables only, beside whatever the main stream runs
                     aux.wait_event(ev)
-                    st["processed"] = tsr_stage.process(pending)
+                    st["processed"] = tsr_stage.process(pending, **mkw)
             else:
                 with stage_range("table_structure.processor"):
-                    st["processed"] = tsr_stage.process(pending)
+                    st["processed"] = tsr_stage.process(pending, **mkw)
             host["tables.wait_decode"] = host.get("tables.wait_decode", 0.0) + getattr(tsr_stage, "wait_s", 0.0) - w0
 
         def collect(st) -> List[PageResult]:
@@ -851,10 +869,17 @@ class OcrTablePipeline:
             self.metric["gpu_ms_inside_phases"] = busy         # device time between the first and the last launch of a phase
             self.metric["gpu_ms_between_phases"] = idle        # device time between two phases' launches: the queue was empty (or copies ran)
 
+    def _lore_match_on_device(self) -> bool:
+        """device_match=True with table_html=True and a Lore stage: the stage's 'matched' map replaces find_top1_match on the host"""
+        from .tsr_stage import TsrStage
+        task = self.table_structure_task
+        return bool(getattr(self, "device_match", False) and self.table_html and task is not None and isinstance(task._stage, TsrStage))
+
     def _match_on_device(self, boxes) -> dict:
         """table_html with SLANet: the stage matches every table's lines to its cells on the device (SlaNetStage, pt_op_table_match) and needs
-        the pages' text boxes for it; every other model: nothing more to pass"""
-        if not (self.table_html and getattr(self, "table_structure_model", None) == "SLANet"):
+        the pages' text boxes for it; so does the Lore stage with device_match=True (TsrStage, pt_op_lore_match); every other model: nothing
+        more to pass"""
+        if not (self.table_html and (getattr(self, "table_structure_model", None) == "SLANet" or self._lore_match_on_device())):
             return {}
         from .table_text_match import text_boxes
         return {"text_boxes": [text_boxes(b) if len(b) else np.zeros((0, 4)) for b in boxes]}
@@ -888,6 +913,13 @@ class OcrTablePipeline:
                 if len(table.get("scores", [])) == 0:
                     table["table_html"], table["db_table_html"] = [], []
                     continue
+                if "matched" in table:      # device_match=True: the stage's map (TsrStage.process(match=...)), no [lines, cells] pass here
+                    table["table_html"], table["db_table_html"] = page_table_html(
+                        table["polygons"], table["logi"], tb[k][ti], boxes[k], texts[k], matched=table["matched"],
+                        matched_lines=table["matched_lines"])
+                    continue
+                if self._lore_match_on_device():
+                    raise RuntimeError("device_match=True: the Lore stage returned no 'matched' map for a table with cells")
                 table["table_html"], table["db_table_html"] = page_table_html(
                     table["polygons"], table["logi"], tb[k][ti], boxes[k], texts[k])
 

@@ -40,12 +40,13 @@ def _dist(a, b) -> float:
     return float(np.sqrt((float(a[0]) - float(b[0])) ** 2 + (float(a[1]) - float(b[1])) ** 2))
 
 
-def table_cells_from_logits(polygons: np.ndarray, logi: np.ndarray) -> List[TableCell]:
+def table_cells_from_logits(polygons: np.ndarray, logi: np.ndarray, return_order: bool = False):
     """polygons [n,8] (x1,y1 .. x4,y4: TL, TR, BR, BL), logi [n,4] = [left, right, top, bottom] -> cells in the
-    reference's order (sorted by top, left, bottom, right; ties keep the input order)."""
+    reference's order (sorted by top, left, bottom, right; ties keep the input order).  return_order=True: (cells, order), order[j] the input
+    row of the j-th cell."""
     n = len(polygons)
     if n == 0:
-        return []
+        return ([], []) if return_order else []
     order = sorted(range(n), key=lambda i: (logi[i][2], logi[i][0], logi[i][3], logi[i][1]))
     p = np.asarray(polygons)
     first, last = p[order[0]], p[order[-1]]
@@ -62,7 +63,7 @@ def table_cells_from_logits(polygons: np.ndarray, logi: np.ndarray) -> List[Tabl
         cells.append(TableCell(x1=b[6], y1=b[7], x2=b[2], y2=b[3], row_index=top + 1, col_index=left + 1,
                                row_span=bottom - top + 1, col_span=right - left + 1, width_ratio=wr, height_ratio=hr,
                                lt=(b[0], b[1]), rb=(b[4], b[5])))
-    return cells
+    return (cells, order) if return_order else cells
 
 
 def cells_to_structure_html(cells: List[TableCell]) -> str:

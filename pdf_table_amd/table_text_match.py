@@ -16,7 +16,7 @@ Reference behaviours kept on purpose:
 from __future__ import annotations
 
 import re
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -118,10 +118,15 @@ def ocr_post_process(text: str) -> str:
 
 
 def match_table_cells_and_text(cells: List[TableCell], tboxes: np.ndarray, texts: Sequence[str],
-                               post_process: bool = False) -> List[TableCell]:
+                               post_process: bool = False, top1: Optional[np.ndarray] = None) -> List[TableCell]:
     """match_table_cell_and_text_cell up to the HTML: returns the cells sorted by (row_index, col_index), matched cells
-    first in the reference's intermediate list (irrelevant after the sort, which is stable)"""
-    if len(tboxes):
+    first in the reference's intermediate list (irrelevant after the sort, which is stable).  ``top1``: per text box the
+    position of its cell in ``cells``, computed elsewhere (the Lore stage's device match); find_top1_match is then skipped."""
+    if top1 is not None:
+        top1 = np.asarray(top1, np.int64)
+        if len(top1) != len(tboxes) or (len(top1) and (top1.min() < 0 or top1.max() >= len(cells))):
+            raise ValueError(f"top1: {len(top1)} cell positions for {len(tboxes)} text boxes and {len(cells)} cells")
+    elif len(tboxes):
         cb = np.array([[c.x1, c.y1, c.x2, c.y2] for c in cells], np.float64)
         top1 = find_top1_match(tboxes, cb)
     else:
@@ -177,14 +182,29 @@ def cells_to_html(cells: List[TableCell]) -> Tuple[List[str], List[str]]:
 
 
 def page_table_html(polygons: np.ndarray, logi: np.ndarray, table_box: Sequence[float], text_quads: np.ndarray,
-                    texts: Sequence[str], post_process: bool = True) -> Tuple[List[str], List[str]]:
+                    texts: Sequence[str], post_process: bool = True, matched: Optional[np.ndarray] = None,
+                    matched_lines: Optional[np.ndarray] = None) -> Tuple[List[str], List[str]]:
     """One table of a page -> (table_html, db_table_html).  EVERYTHING is in page pixels: ``polygons`` are the cell quads
     after the reference's shift by the crop corner (convert_table_sep_to_merge, table_common.py:1811-1825), ``table_box``
     the layout box the crop was cut from, ``text_quads`` [t,8] the page's detected lines with their ``texts``.  Lines whose
-    centre is in the table box are assigned to cells; image pages use ocr_post_process=True (ocr_table_to_html_task.py:93)."""
+    centre is in the table box are assigned to cells; image pages use ocr_post_process=True (ocr_table_to_html_task.py:93).
+    ``matched``: per candidate line the INPUT row (of ``polygons``) of its cell, as the Lore stage's device match gives it
+    (TsrStage, pt_op_lore_match): find_top1_match is skipped.  ``matched_lines``: those candidates' indices on the page
+    (the stage's choice); None: chosen here with texts_in_table, which is what the stage does."""
     from .table_html import table_cells_from_logits
-    cells = table_cells_from_logits(polygons, logi)
+    cells, order = table_cells_from_logits(polygons, logi, return_order=True)
     tbx = text_boxes(text_quads) if len(text_quads) else np.zeros((0, 4))
-    inside = texts_in_table([float(v) for v in table_box], tbx, diff=2) if len(tbx) else np.zeros(0, np.int64)
-    res = match_table_cells_and_text(cells, tbx[inside], [texts[i] for i in inside], post_process=post_process)
+    if matched_lines is not None:
+        inside = np.asarray(matched_lines, np.int64)
+    else:
+        inside = texts_in_table([float(v) for v in table_box], tbx, diff=2) if len(tbx) else np.zeros(0, np.int64)
+    top1 = None
+    if matched is not None:
+        rows = np.asarray(matched, np.int64)
+        if len(rows) != len(inside) or (len(rows) and (rows.min() < 0 or rows.max() >= len(cells))):
+            raise ValueError(f"matched: {len(rows)} rows for {len(inside)} candidate lines of a table with {len(cells)} cells")
+        position = np.empty(len(cells), np.int64)              # input row -> position in the sorted cell list
+        position[np.asarray(order, np.int64)] = np.arange(len(cells))
+        top1 = position[rows]
+    res = match_table_cells_and_text(cells, tbx[inside], [texts[i] for i in inside], post_process=post_process, top1=top1)
     return cells_to_html(res)

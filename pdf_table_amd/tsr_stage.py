@@ -23,7 +23,7 @@ from .engine import TSR_TABLE_DTYPE, HipEngine
 from .table_html import structure_html
 
 __all__ = ["LoreConfig", "TsrStage", "lore_geometry", "affine_from_center_scale", "affine_upper_left", "invert_affine",
-           "transform_quads", "process_logic_output"]
+           "quad_inverse_map", "transform_quads", "process_logic_output"]
 
 
 @dataclass
@@ -135,10 +135,15 @@ def lore_geometry(crop_h: int, crop_w: int, inp_h: int, inp_w: int, upper_left: 
     return invert_affine(trans), meta
 
 
+def quad_inverse_map(meta: np.ndarray, upper_left: bool = False) -> np.ndarray:
+    """the float64 2x3 map transform_quads sends every vertex through (what pt_op_lore_match takes per table)"""
+    return (affine_upper_left if upper_left else affine_from_center_scale)(meta[:2], meta[2], (meta[6], meta[5]), inv=True)
+
+
 def transform_quads(quads: np.ndarray, meta: np.ndarray, upper_left: bool = False) -> np.ndarray:
     """ctdet_4ps_post_process[_upper_left] (lineless_table_process.py:489-533): the four vertices of every quad through
     the inverse map built from the int64 meta; float64 matrix x float32 point, stored back as float32."""
-    t = (affine_upper_left if upper_left else affine_from_center_scale)(meta[:2], meta[2], (meta[6], meta[5]), inv=True)
+    t = quad_inverse_map(meta, upper_left)
     p = quads.astype(np.float32).astype(np.float64).reshape(-1, 4, 2)
     out = np.empty_like(p)
     out[..., 0] = t[0, 0] * p[..., 0] + t[0, 1] * p[..., 1] + t[0, 2]
@@ -233,10 +238,60 @@ class TsrStage:
             out.append((i, nt, counts, dets, logi, host, ev))
         return out
 
-    def process(self, pending):
+    def match_input(self, tables: np.ndarray, metas: List[np.ndarray], boxes_per_page: Sequence[np.ndarray],
+                    text_boxes: Sequence[np.ndarray]) -> Dict:
+        """What process(match=...) needs to assign text lines to cells on the device (pt_op_lore_match): per table its candidate lines -- the
+        page's lines whose centre lies in the layout box the crop was cut from, grown by 2 (texts_in_table: what page_table_html chooses) --
+        with their float32 boxes, the inverse map transform_quads builds and the crop's corner.  ``tables`` / ``metas``: tables()'s;
+        ``boxes_per_page``: what tables() was given; ``text_boxes``: per page [t, 4] = (min x, min y, max x, max y) in page pixels
+        (table_text_match.text_boxes).  Host arithmetic only."""
+        from .table_text_match import texts_in_table
+        flat = [b for boxes in boxes_per_page for b in np.asarray(boxes).reshape(-1, 4)]
+        if len(flat) != len(tables):
+            raise ValueError(f"match_input: {len(flat)} table boxes for {len(tables)} table records")
+        per_page: Dict[int, Tuple[np.ndarray, np.ndarray]] = {}
+        lines, boxes = [], []
+        for r, box in zip(tables, flat):
+            pi = int(r["page"])
+            if pi not in per_page:
+                tb64 = np.asarray(text_boxes[pi], np.float64).reshape(-1, 4)
+                tb32 = tb64.astype(np.float32)
+                if not np.array_equal(tb32.astype(np.float64), tb64):
+                    raise ValueError("match_input: the text boxes must be exact in float32 (the device matches float32 boxes widened to double)")
+                per_page[pi] = (np.asarray(text_boxes[pi]).reshape(-1, 4), tb32)
+            tbx, tb32 = per_page[pi]
+            inside = texts_in_table([float(v) for v in box], tbx, diff=2) if len(tbx) else np.zeros(0, np.int64)
+            lines.append(inside)
+            boxes.append(tb32[inside])
+        affine = np.stack([quad_inverse_map(m, self.config.upper_left).reshape(6) for m in metas]) if len(metas) else np.zeros((0, 6))
+        offset = np.stack([tables["x0"], tables["y0"]], 1).astype(np.float64)
+        return {"lines": lines, "boxes": boxes, "affine": np.ascontiguousarray(affine, np.float64), "offset": offset}
+
+    def _queue_match(self, match: Dict, i: int, nt: int, counts_d, dets, axes):
+        """one pinned non-blocking upload (maps, corners, line boxes, per-table line offsets) and one pt_op_lore_match launch on the current stream for
+        tables i .. i + nt - 1 -> (candidate lines per table, int32 [lines] on the device or None without lines, what must stay alive)"""
+        lines_of = match["lines"][i:i + nt]
+        offs = np.zeros(nt + 1, np.int32)
+        offs[1:] = np.cumsum([len(c) for c in lines_of])
+        m = int(offs[-1])
+        if m == 0:
+            return lines_of, None, None
+        boxes = np.concatenate(match["boxes"][i:i + nt]).astype(np.float32).reshape(-1)
+        geom = np.concatenate([match["affine"][i:i + nt].reshape(-1), match["offset"][i:i + nt].reshape(-1)])
+        # float64 first, then the 16-byte boxes (nt * 64 bytes in), then the int32 offsets: every view below is aligned
+        buf = np.concatenate([geom.view(np.uint8), boxes.view(np.uint8), offs.view(np.uint8)])
+        up = torch.from_numpy(buf).pin_memory().to(self.eng._tdev, non_blocking=True)
+        a, b, c = nt * 48, nt * 64, nt * 64 + 16 * m
+        out = self.eng.op_lore_match(dets, axes, counts_d, up[:a].view(torch.float64).reshape(nt, 6), up[a:b].view(torch.float64).reshape(nt, 2),
+                                     up[b:c].view(torch.float32).reshape(m, 4), up[c:].view(torch.int32))
+        return lines_of, out, up
+
+    def process(self, pending, match: Optional[Dict] = None):
         """device half 2: cell counts from their pinned copy (waits for half 1 of these tables only when it is still running), the
         processor over all cells of each micro-batch, then the valid rows to pinned host memory on a copy stream behind
-        an event -- nothing here waits for work queued after start()."""
+        an event -- nothing here waits for work queued after start().  ``match`` (match_input()): behind the processor of every entry one
+        pt_op_lore_match launch assigns the tables' candidate lines to cells; its [lines] int32 rides on the same copy back and collect()
+        attaches it.  Without it: no new launch, copy or key."""
         cfg = self.config
         staged = []
         for (i, nt, counts_d, dets, logi, counts_h, counts_ev) in pending:
@@ -245,7 +300,8 @@ class TsrStage:
             self.wait_s += time.perf_counter() - t0      # host seconds spent waiting for the decode (diagnostics: pipeline.metric)
             counts = counts_h.numpy().copy()
             logic, stacked = self.eng.tsr_process(logi, dets, counts, use_2dpe=cfg.wiz_2dpe)
-            staged.append((i, nt, counts, dets, logic, stacked))
+            mt = self._queue_match(match, i, nt, counts_d, dets, stacked if cfg.wiz_stacking else logic) if match is not None else None
+            staged.append((i, nt, counts, dets, logic, stacked, mt))
         if not staged:
             return [], None
         if self._copy_stream is None:
@@ -255,7 +311,7 @@ class TsrStage:
         host = []
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(ready)
-            for (i, nt, counts, dets, logic, stacked) in staged:
+            for (i, nt, counts, dets, logic, stacked, mt) in staged:
                 nmax = max(1, int(counts.max()) if len(counts) else 1)
                 bufs = []
                 for src in (dets, logic, stacked):
@@ -263,7 +319,16 @@ class TsrStage:
                     dst.copy_(src[:, :nmax], non_blocking=True)
                     src.record_stream(self._copy_stream)
                     bufs.append(dst)
-                host.append((i, nt, counts, bufs))
+                if mt is None:
+                    host.append((i, nt, counts, bufs))
+                    continue
+                lines_of, rows_d, up = mt
+                rows_h = None
+                if rows_d is not None:
+                    rows_h = torch.empty(rows_d.shape, dtype=torch.int32, pin_memory=True)
+                    rows_h.copy_(rows_d, non_blocking=True)
+                    rows_d.record_stream(self._copy_stream)
+                host.append((i, nt, counts, bufs, (lines_of, rows_h, up)))      # up: alive until collect() has seen the copy
             done = torch.cuda.Event()
             done.record(self._copy_stream)
         return host, done
@@ -280,14 +345,26 @@ class TsrStage:
         if done is not None:
             done.synchronize()
         out: List[Dict] = []
-        for (i, nt, counts, bufs) in host:
+        for ent in host:
+            i, nt, counts, bufs = ent[:4]
             dets_h, logic_h, stacked_h = (b.numpy() for b in bufs)
+            # process(match=...): per table its candidate lines (page indices) and, per line, the input row of its cell
+            lines_of, rows_h = ent[4][:2] if len(ent) > 4 else (None, None)
+            rows = rows_h.numpy() if rows_h is not None else np.zeros(0, np.int32)
+            m0 = 0
             for k in range(nt):
                 n = int(counts[k])
+                if lines_of is not None:
+                    mk = len(lines_of[k])
+                    matched = {"matched_lines": np.asarray(lines_of[k], np.int64) if n else np.zeros(0, np.int64),
+                               "matched": rows[m0:m0 + mk].astype(np.int64) if n else np.zeros(0, np.int64)}
+                    m0 += mk
                 if n == 0:       # LoreModel.forward's empty case (modeling_lore.py:171-173)
                     out.append({"polygons": np.zeros((1, 8), np.float32), "logi": np.zeros((1, 4), np.float32),
                                 "logic_axis": np.zeros((1, 4), np.float32), "stacked_axis": np.zeros((1, 4), np.float32),
                                 "scores": np.zeros((0,), np.float32)})
+                    if lines_of is not None:
+                        out[-1].update(matched)
                     continue
                 final = stacked_h[k, :n] if cfg.wiz_stacking else logic_h[k, :n]
                 polys = transform_quads(dets_h[k, :n, :8], metas[i + k], cfg.upper_left)
@@ -299,14 +376,17 @@ class TsrStage:
                      "stacked_axis": stacked_h[k, :n].copy(), "scores": dets_h[k, :n, 8].copy()}
                 if self.with_html:       # table_html.table_cells_from_logits(polygons, logi) gives the cell objects on demand
                     r["structure_str_list"] = [structure_html(r["polygons"], r["logi"])]
+                if lines_of is not None:
+                    r.update(matched)
                 out.append(r)
         return out
 
-    def finish(self, pending, metas: List[np.ndarray], offsets: Optional[np.ndarray] = None) -> List[Dict]:
-        return self.collect(self.process(pending), metas, offsets)
+    def finish(self, pending, metas: List[np.ndarray], offsets: Optional[np.ndarray] = None, match: Optional[Dict] = None) -> List[Dict]:
+        return self.collect(self.process(pending, match) if match is not None else self.process(pending), metas, offsets)
 
-    def run(self, pages: torch.Tensor, tables: np.ndarray, metas: List[np.ndarray], offsets: Optional[np.ndarray] = None) -> List[Dict]:
-        return self.finish(self.start(pages, tables), metas, offsets)
+    def run(self, pages: torch.Tensor, tables: np.ndarray, metas: List[np.ndarray], offsets: Optional[np.ndarray] = None,
+            match: Optional[Dict] = None) -> List[Dict]:
+        return self.finish(self.start(pages, tables), metas, offsets, match)
 
     def regroup(self, flat: List[Dict], boxes_per_page: Sequence[np.ndarray]) -> List[List[Dict]]:
         res, o = [], 0
@@ -316,9 +396,15 @@ class TsrStage:
             o += k
         return res
 
-    def __call__(self, pages: torch.Tensor, boxes_per_page: Sequence[np.ndarray], page_frame: bool = False) -> List[List[Dict]]:
-        """page_frame=True: quads in page pixels (the crop's clamped x0, y0 added), like the reference's merged result"""
+    def __call__(self, pages: torch.Tensor, boxes_per_page: Sequence[np.ndarray], page_frame: bool = False,
+                 text_boxes: Optional[Sequence[np.ndarray]] = None) -> List[List[Dict]]:
+        """page_frame=True: quads in page pixels (the crop's clamped x0, y0 added), like the reference's merged result.  text_boxes (per page
+        [t, 4], table_text_match.text_boxes; needs page_frame=True): every table's candidate lines are assigned to its cells on the device ->
+        'matched_lines' / 'matched' in every table (process(match=...))"""
+        if text_boxes is not None and not page_frame:
+            raise ValueError("TsrStage: text lines are matched in page pixels: text_boxes needs page_frame=True")
         tables, metas = self.tables(tuple(pages.shape[1:3]), boxes_per_page)
         offs = np.stack([tables["x0"], tables["y0"]], 1).astype(np.float32) if page_frame and len(tables) else None
-        flat = self.run(pages, tables, metas, offs) if len(tables) else []
+        match = self.match_input(tables, metas, boxes_per_page, text_boxes) if text_boxes is not None and len(tables) else None
+        flat = self.run(pages, tables, metas, offs, match) if len(tables) else []
         return self.regroup(flat, boxes_per_page)
