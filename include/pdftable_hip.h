@@ -734,6 +734,21 @@ int pt_op_table_match(const float* d_loc, const int32_t* d_ids, const int32_t* d
  * setting) and returns PT_ERR_STATE inside a stream capture, so call once before capturing.  No allocation, no host synchronisation. */
 int pt_op_lore_match(const float* d_dets, const float* d_axes, const int32_t* d_counts, int B, const double* d_affine, const double* d_offset,
                      const float* d_lines, const int32_t* d_offsets, int M, int32_t* d_out, pt_stream stream);
+/* PicoDet post-processing behind the candidate records (csrc/layout_decode.hip, compiled once, engine-free; added under ABI 20: one new entry point, no
+ * existing signature changed, so the version stays): LayoutStage.decode_page on the device.  d_counts int32 [B] / d_cands fp32 [B, max_cands,
+ * PT_LAYOUT_CAND_FLOATS] as pt_layout_candidates / pt_op_pico_candidates write them (records in no defined order; a count above max_cands reads max_cands
+ * records; a record whose level is outside [0, levels) is dropped, its anchor is clamped to >= 0).  h_strides: `levels` ints on the HOST.  probs 0: the
+ * class columns are logits (sigmoid here), 1: probabilities.  Per page: per-level top nms_top_k by the largest class score, per class the scores >
+ * score_threshold (float32, strict; never a NaN), of those the candidate_size best, greedy hard NMS in float64 with pt_hard_nms's operation order (an entry
+ * stays when iou <= nms_threshold), at most keep_top_k picks per class (<= 0: no limit), clip to the page, division by fl32(inp / org).  Equal scores are
+ * ordered by (level, anchor) ascending -- the host's arg-sorts have no tie rule -- so the result does not depend on the records' order.
+ * d_ndet int32 [B]: every detection of the page, also those beyond max_dets; d_dets fp64 [B, max_dets, 6] = (x0, y0, x1, y1, score, class), classes
+ * ascending, within a class in pick order; rows at and beyond the page's count are left as they were.  1 <= ncls <= 14, 1 <= levels <= 4,
+ * 1 <= candidate_size <= 256, 1 <= max_cands <= 4096 (what the kernel's LDS plan holds), 1 <= B <= 65535, nms_top_k >= 1, max_dets >= 1: anything else is
+ * PT_ERR_INVALID with a message and nothing is launched.  One launch of one workgroup per page, no allocation, no host synchronisation (capturable). */
+int pt_op_layout_decode(const int32_t* d_counts, const float* d_cands, int B, int max_cands, int ncls, int levels, const int32_t* h_strides, int inp_h,
+                        int inp_w, int org_h, int org_w, int probs, float score_threshold, double nms_threshold, int nms_top_k, int candidate_size,
+                        int keep_top_k, int max_dets, int32_t* d_ndet, double* d_dets, pt_stream stream);
 
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------

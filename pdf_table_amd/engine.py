@@ -1150,6 +1150,40 @@ class HipEngine:
                                                int(max_cands), _ptr(counts), _ptr(cands), int(split), self._stream()), "pt_op_pico_candidates")
         return counts, cands
 
+    def op_layout_decode(self, counts: torch.Tensor, cands: torch.Tensor, ncls: int, strides, inp_h: int, inp_w: int, org_h: int, org_w: int,
+                         probs: bool, score_threshold: float, nms_threshold: float, nms_top_k: int = 1000, candidate_size: int = 200,
+                         keep_top_k: int = 100, max_dets: Optional[int] = None, out=None):
+        """LayoutStage.decode_page for every page of a batch in one launch (pt_op_layout_decode, csrc/layout_decode.hip).  counts int32 [B] / cands
+        float32 [B, max_cands, 48]: the candidate records of layout_forward / op_pico_candidates, in any order; probs: the class columns are
+        probabilities (an ONNX export) rather than logits -> (ndet int32 [B], dets float64 [B, max_dets, 6] = (x0, y0, x1, y1, score, class)) on the
+        device: per page classes ascending, within a class the greedy pick order; ndet counts every detection, dets holds the first max_dets
+        (default ncls * min(keep_top_k, candidate_size)); rows past a page's count are left as they were.  Equal scores: (level, anchor)
+        ascending.  out: (ndet, dets) to write into instead of new tensors.  Everything stays on the device; nothing synchronises."""
+        self._chk(counts, torch.int32, "counts")
+        self._chk(cands, torch.float32, "cands")
+        if cands.dim() != 3 or cands.shape[2] != L.PT_LAYOUT_CAND_FLOATS or counts.numel() != cands.shape[0]:
+            raise ValueError(f"op_layout_decode: counts [B] and cands [B, max_cands, {L.PT_LAYOUT_CAND_FLOATS}] expected, got {tuple(counts.shape)} "
+                             f"and {tuple(cands.shape)}")
+        B, max_cands = int(cands.shape[0]), int(cands.shape[1])
+        strides = [int(s) for s in strides]
+        if max_dets is None:
+            max_dets = int(ncls) * (min(int(keep_top_k), int(candidate_size)) if keep_top_k > 0 else int(candidate_size))
+        if out is None:
+            ndet = torch.empty((B,), dtype=torch.int32, device=self._tdev)
+            dets = torch.empty((B, max(int(max_dets), 1), 6), dtype=torch.float64, device=self._tdev)
+        else:
+            ndet, dets = out
+            self._chk(ndet, torch.int32, "ndet")
+            self._chk(dets, torch.float64, "dets")
+            if ndet.numel() < B or dets.numel() < B * int(max_dets) * 6:
+                raise ValueError("op_layout_decode: output buffers too small")
+        h_st = (C.c_int * max(len(strides), 1))(*strides)
+        L.check(self.lib.pt_op_layout_decode(_ptr(counts), _ptr(cands), B, max_cands, int(ncls), len(strides), h_st, int(inp_h), int(inp_w), int(org_h),
+                                             int(org_w), int(bool(probs)), float(score_threshold), float(nms_threshold), int(nms_top_k),
+                                             int(candidate_size), int(keep_top_k), int(max_dets), _ptr(ndet), _ptr(dets), self._stream()),
+                "pt_op_layout_decode")
+        return ndet, dets
+
     def slanet_preprocess(self, pages: torch.Tensor, tables: np.ndarray, size: int = 488) -> torch.Tensor:
         """SLANetPreprocessor on resident pages (pt_slanet_preprocess): pages uint8 [n_pages, h, w, 3], tables TSR_TABLE_DTYPE records (page, x0, y0,
         crop_w, crop_h) -> float32 NHWC [n, size, size, 3] in B, G, R order, zero-padded at the bottom and the right"""

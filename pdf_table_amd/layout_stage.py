@@ -88,8 +88,16 @@ def layout_tables(layout_result: List[Dict], label: str = "table", score_thresho
 
 
 class LayoutStage:
-    def __init__(self, eng: HipEngine, config: PicodetConfig = None, max_cands: int = 2048, precision: Optional[int] = None):
-        """``precision``: an L.PT_PRECISION_* for THIS stage's network, whatever the engine's is (None: the engine's).  The layout net is the
+    CANDIDATE_SIZE = 200      # hard_nms's candidate_size (processor_picodet.py:301), the [-200:] of decode_page
+
+    def __init__(self, eng: HipEngine, config: PicodetConfig = None, max_cands: int = 2048, precision: Optional[int] = None,
+                 device_decode: bool = False):
+        """``device_decode=True``: forward() queues pt_op_layout_decode (csrc/layout_decode.hip) behind the candidate compaction on the same stream
+        and lands (counts, detection counts, detections [n, ncls * min(keep_top_k, 200), 6] float64) instead of the records; finish() only
+        checks the counts and builds the dict lists.  Equal scores are ordered by (level, anchor) there -- decode_page's arg-sorts have no tie
+        rule -- and exp is the device's, so boxes and scores agree with decode_page to float32 rounding, not bit for bit.  Off by default.
+
+        ``precision``: an L.PT_PRECISION_* for THIS stage's network, whatever the engine's is (None: the engine's).  The layout net is the
         pipeline's smallest (3 % of a step) and its output is a DECISION the table stage inherits -- the crop of every table at the box's ROUNDED
         coordinates (ocr_system_task.py:184-198): in a 16-bit mode an edge that rounds one pixel differently is a different input to the table
         net.  ``precision=L.PT_PRECISION_BF16X3`` runs just this stage in the pair mode (its blob must then be a bf16 blob with the pair tiles,
@@ -101,6 +109,23 @@ class LayoutStage:
         self._copy_stream = None
         self._pinned = [None, None]          # two host landing buffers: a forward() may be queued while the previous finish() still reads
         self._turn = 0
+        self.device_decode = bool(device_decode)
+
+    PROBS = False      # the in-tree head hands back class LOGITS
+
+    def _max_dets(self) -> int:
+        cfg = self.config
+        return len(cfg.labels) * (min(int(cfg.keep_top_k), self.CANDIDATE_SIZE) if cfg.keep_top_k > 0 else self.CANDIDATE_SIZE)
+
+    def _decode_on_device(self, counts: torch.Tensor, cands: torch.Tensor, org, landing=None):
+        """device_decode=True: one pt_op_layout_decode launch on the current stream behind the kernels that wrote counts / cands, then the copy of
+        (counts, detection counts, detections) instead of the records"""
+        cfg = self.config
+        ndet, dets = self.eng.op_layout_decode(counts, cands, len(cfg.labels), cfg.strides, cfg.img_height, cfg.img_width, int(org[0]), int(org[1]),
+                                               probs=self.PROBS, score_threshold=cfg.score_threshold, nms_threshold=cfg.nms_threshold,
+                                               nms_top_k=cfg.nms_top_k, candidate_size=self.CANDIDATE_SIZE, keep_top_k=cfg.keep_top_k,
+                                               max_dets=self._max_dets())
+        return self._land_tensors((counts, ndet, dets), landing)
 
     def forward(self, pages: torch.Tensor, landing=None):
         """device half (asynchronous): network + candidate compaction on the current stream, then the D2H of the
@@ -113,10 +138,17 @@ class LayoutStage:
         with self.eng.precision_scope(self.precision):
             counts, cands = self.eng.layout_forward(pages, cfg.img_height, cfg.img_width, len(cfg.labels),
                                                     thr_lo=cfg.score_threshold - 1e-3, max_cands=self.max_cands)
+        if getattr(self, "device_decode", False):
+            return self._decode_on_device(counts, cands, pages.shape[1:3], landing)
         return self._land(counts, cands, landing)
 
     def _land(self, counts: torch.Tensor, cands: torch.Tensor, landing=None):
         """counts / records written on the current stream -> their copy into a pinned landing buffer on the copy stream behind an event: (n, ticket)"""
+        return self._land_tensors((counts, cands), landing)
+
+    def _land_tensors(self, dev, landing=None):
+        """device tensors [n, ...] written on the current stream (a stage always lands the same kinds) -> pinned copies, as _land()"""
+        counts = dev[0]
         n = counts.shape[0]
         if self._copy_stream is None:
             self._copy_stream = shared_stream(counts.device, "layout_copy")
@@ -128,20 +160,19 @@ class LayoutStage:
             slot = landing
             pinned = self.__dict__.setdefault("_pinned_extra", {})
         host = pinned.get(slot) if isinstance(pinned, dict) else pinned[slot]
-        if host is None or host[0].shape[0] < n:
-            host = (torch.empty((n,), dtype=torch.int32).pin_memory(),
-                    torch.empty((n, self.max_cands, L.PT_LAYOUT_CAND_FLOATS), dtype=torch.float32).pin_memory())
+        if host is None or host[0].shape[0] < n or len(host) != len(dev):
+            host = tuple(torch.empty((n,) + tuple(t.shape[1:]), dtype=t.dtype).pin_memory() for t in dev)
             pinned[slot] = host
         ready = torch.cuda.Event()
         ready.record()
         with torch.cuda.stream(self._copy_stream):
             self._copy_stream.wait_event(ready)
-            host[0][:n].copy_(counts, non_blocking=True)
-            host[1][:n].copy_(cands, non_blocking=True)
+            for h, t in zip(host, dev):
+                h[:n].copy_(t, non_blocking=True)
             done = torch.cuda.Event()
             done.record(self._copy_stream)
-        counts.record_stream(self._copy_stream)
-        cands.record_stream(self._copy_stream)
+        for t in dev:
+            t.record_stream(self._copy_stream)
         return n, (done, host)
 
     def decode_outputs(self, scores: Sequence[np.ndarray], dists: Sequence[np.ndarray], org_shape) -> List[Dict]:
@@ -252,9 +283,21 @@ class LayoutStage:
         counts = host[0][:n].numpy().copy()
         if (counts > self.max_cands).any():
             raise RuntimeError(f"layout: {int(counts.max())} candidate anchors on a page exceed max_cands={self.max_cands}")
+        if getattr(self, "device_decode", False):
+            return self._finish_decoded(n, host)
         kmax = int(counts.max()) if len(counts) else 0
         rec = host[1][:n, :max(kmax, 1)].numpy()
         return [self._decode_record_page(rec[i, :counts[i]], org) for i in range(len(counts))]
+
+    def _finish_decoded(self, n: int, host) -> List[List[Dict]]:
+        """device_decode=True: the landed (counts, detection counts, detections) -> the dict lists; nothing is computed here"""
+        cfg = self.config
+        ndet = host[1][:n].numpy().copy()
+        if (ndet > host[2].shape[1]).any():
+            raise RuntimeError(f"layout: {int(ndet.max())} detections on a page exceed max_dets={host[2].shape[1]}")
+        dets = host[2][:n].numpy()
+        return [[{"bbox": dets[i, k, :4].copy(), "label": cfg.id2label[int(dets[i, k, 5])], "score": dets[i, k, 4], "category_id": int(dets[i, k, 5])}
+                 for k in range(int(ndet[i]))] for i in range(n)]
 
     def _decode_record_page(self, rec: np.ndarray, org) -> List[Dict]:
         """one page's landed records -> its result list (the in-tree head hands back class LOGITS)"""
@@ -278,8 +321,11 @@ class OnnxLayoutStage(LayoutStage):
     MAX_LEVELS = 4
     MAX_CLASSES = L.PT_LAYOUT_CAND_FLOATS - 2 - 32
 
-    def __init__(self, eng: HipEngine, executor, config: PicodetConfig = None, max_cands: int = 2048):
-        super().__init__(eng, config, max_cands=max_cands, precision=None)      # the executor computes in the engine's arithmetic
+    PROBS = True      # an export's class rows went through the Sigmoid already
+
+    def __init__(self, eng: HipEngine, executor, config: PicodetConfig = None, max_cands: int = 2048, device_decode: bool = False):
+        # the executor computes in the engine's arithmetic; device_decode as in LayoutStage (the host fallback for outputs the tail cannot read is unchanged)
+        super().__init__(eng, config, max_cands=max_cands, precision=None, device_decode=device_decode)
         self.exec = executor
         self._tail_ok: Dict[tuple, bool] = {}       # pre-processed input shape -> True: device tail, False: host route
 
@@ -330,6 +376,8 @@ class OnnxLayoutStage(LayoutStage):
         half = len(acts) // 2
         counts, cands = self.eng.op_pico_candidates([a.t for a in acts[:half]], [a.t for a in acts[half:]], len(cfg.labels),
                                                     thr_lo=cfg.score_threshold - 1e-3, max_cands=self.max_cands, split=self.exec.split)
+        if getattr(self, "device_decode", False):
+            return self._decode_on_device(counts, cands, pages.shape[1:3], landing)
         return self._land(counts, cands, landing)
 
     def finish(self, n: int, ticket, org) -> List[List[Dict]]:

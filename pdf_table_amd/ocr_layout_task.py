@@ -34,7 +34,9 @@ __all__ = ["OcrLayoutTask"]
 
 
 class OcrLayoutTask(BaseInferTask):
-    def __init__(self, task="ocr_layout", model="picodet", engine: HipEngine = None, **kwargs):
+    def __init__(self, task="ocr_layout", model="picodet", engine: HipEngine = None, device_decode: bool = False, **kwargs):
+        # device_decode=True: the stage decodes, cuts and suppresses on the device (LayoutStage(device_decode=True), pt_op_layout_decode)
+        self._device_decode = bool(device_decode)
         super().__init__(task=task, model=model, **kwargs)
         if model not in ["picodet", "DocXLayout"]:
             raise RuntimeError(f"current model is not supported: {model}")
@@ -90,9 +92,9 @@ class OcrLayoutTask(BaseInferTask):
     def _build_processor(self):
         if getattr(self, "_exec", None) is not None:
             # the graph file behind LayoutStage's contract: forward() / finish() halves, candidate compaction on the device (pt_op_pico_candidates)
-            self._stage = OnnxLayoutStage(self._engine, self._exec, self._config)
+            self._stage = OnnxLayoutStage(self._engine, self._exec, self._config, device_decode=self._device_decode)
             return
-        self._stage = LayoutStage(self._engine, self._config, precision=getattr(self, "_stage_precision", None))
+        self._stage = LayoutStage(self._engine, self._config, precision=getattr(self, "_stage_precision", None), device_decode=self._device_decode)
 
     def _predict(self, images: List[np.ndarray]) -> List[List[Dict]]:
         out = []

@@ -78,7 +78,11 @@ class OcrTablePipeline:
                  precision: str = "bf16", layout_precision: Optional[str] = None, deskew: bool = False,
                  sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
                  table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
-                 rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, device_match: bool = False, **kwargs):
+                 rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, device_match: bool = False,
+                 layout_device_decode: bool = False, **kwargs):
+        if layout_device_decode and not layout:
+            raise ValueError("layout_device_decode=True decodes the layout stage's candidates on the device (pt_op_layout_decode); layout=False builds no "
+                             "layout stage")
         if table_structure_model == "SLANet" and not tsr_task_path:
             # the ONNX-only model has no in-tree (seeded) weights: without its directory there is nothing to serve.  Refused here, before any
             # engine exists, not on the first page
@@ -157,6 +161,8 @@ class OcrTablePipeline:
             if layout_precision:      # the layout net alone in the pair mode ("fp32"): exact table crops under a 16-bit engine (LayoutStage.precision)
                 # with an ONNX file under layout_task_path it has NO effect: the executor computes in the engine's arithmetic (``precision``)
                 lk["stage_precision"] = layout_precision
+            if layout_device_decode:      # off: the key is not handed on at all.  One stage serves predict(), predict_stream(), aux_layout and the vote's second pass
+                lk["device_decode"] = True
             self.layout_task = OcrLayoutTask(model=layout_model, engine=self.engine, task_type=layout_task_type, **lk)
         self.table_html = table_html      # structure + recognised text -> HTML per table (OcrTableToHtmlTask, section 8f-2)
         self.orientation_task = None
