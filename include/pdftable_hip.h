@@ -882,6 +882,29 @@ int pt_op_mtl_self_attention(pt_engine* e, const uint16_t* d_cache, const int32_
                              int nb, long long cache_bs, long long att_bs, pt_stream stream);
 int pt_op_mtl_kv_fp8(pt_engine* e, const uint16_t* d_kv, long long n_elems, uint8_t* d_out, pt_stream stream);
 
+/* The Lore processor's kernels one at a time (csrc/lore_processor.hip; since ABI 21): the launches of pt_tsr_process on caller-owned buffers, for
+ * op-level tests.  The engine handle and the stream only: no model is loaded.  No allocation on the device, no host synchronisation.  16-bit tensors
+ * are in the engine's storage format; split: rows [hi C | lo C] (PT_PRECISION_BF16X3).  h_counts: HOST int32 [n_tables], 0 <= count <=
+ * PT_TSR_MAX_CELLS; N = their sum; token t of the batch is row r of table b in the order of the tables.  Npad: rows of the token matrices, a
+ * multiple of 128, >= N.  N == 0 launches nothing.  Arguments a kernel cannot take return PT_ERR_INVALID, and nothing is launched.
+ * pt_op_lore_tok_prepare: token t = d_logi[b][r][0:256] (fp32 [n_tables, PT_TSR_MAX_CELLS, 256]) + with use_pe the four position rows
+ *   x_pe[p0] + y_pe[p1] + x_pe[p2] + y_pe[p5], p_i = clamp((int) d_dets[b][r][i], 0, 255) (d_dets fp32 [n_tables, PT_TSR_MAX_CELLS, 9], tables fp32
+ *   [256, 256]) -> d_x0 [Npad, 256] and channels [256, 512) of d_cat [Npad, 512]; rows [N, Npad) are written as 0.  d_tok: device int32 [2 N], receives
+ *   the (table, row) map of the tokens, which pt_op_lore_scatter4 reads.
+ * pt_op_lore_norm: alpha (x - mean) / (std + 1e-6) + bias over the 256 channels of fp32 rows (unbiased std) -> 16-bit [rows, 256]; alpha == bias ==
+ *   NULL: the conversion alone.
+ * pt_op_lore_cvt_logic: fp32 [Npad, 8] (4 valid) -> 16-bit [Npad, 32], channels 4 .. 31 zero.
+ * pt_op_lore_attention: d_qkv [Npad, 768] = [q | k | v] of 8 heads x 32 -> d_out [Npad, 256] = softmax(q k^T / sqrt(32)) v over the cells of the
+ *   token's own table; rows [N, Npad) are neither read nor written.  d_tiles: device int32 [3 * sum ceil(count / 32)], receives the tile list.
+ * pt_op_lore_scatter4: d_out[b][r][0:4] (fp32 [n_tables, PT_TSR_MAX_CELLS, 4]) = d_x[t][0:4] (fp32 [>= N, 8]) for the N tokens of d_tok. */
+int pt_op_lore_tok_prepare(pt_engine* e, const float* d_logi, const float* d_dets, const int32_t* h_counts, int n_tables, int use_pe, const float* d_x_pe,
+                           const float* d_y_pe, int Npad, int32_t* d_tok, uint16_t* d_x0, uint16_t* d_cat, int split, pt_stream stream);
+int pt_op_lore_norm(pt_engine* e, const float* d_x, int rows, const float* d_alpha, const float* d_bias, uint16_t* d_out, int split, pt_stream stream);
+int pt_op_lore_cvt_logic(pt_engine* e, const float* d_x, uint16_t* d_out, int Npad, int split, pt_stream stream);
+int pt_op_lore_attention(pt_engine* e, const uint16_t* d_qkv, const int32_t* h_counts, int n_tables, int Npad, int32_t* d_tiles, uint16_t* d_out, int split,
+                         pt_stream stream);
+int pt_op_lore_scatter4(pt_engine* e, const float* d_x, const int32_t* d_tok, int N, float* d_out, pt_stream stream);
+
 
 /* ---- image-page straightening before detection (OcrSystemTask.image_pre_process, ocr_system_task.py:441-491) ----------------
  * Engine-free: these read and write uint8 RGB pages [n, h, w, 3] only (csrc/page_pre.hip, compiled once).

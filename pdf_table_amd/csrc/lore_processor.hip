@@ -207,6 +207,58 @@ __global__ __launch_bounds__(256) void scatter4_kernel(const float* __restrict__
   out[((size_t)tok[2 * t] * PT_TSR_MAX_CELLS + tok[2 * t + 1]) * 4 + c] = x[(size_t)t * 8 + c];
 }
 
+// Token map (table, row) of every cell and the attention's tile list (first token of the table, query offset inside it, cells in
+// the table: one tile per 32 queries) of a batch of tables; *N = the token count.  pt_lore_process and pt_op_lore_* both get them here.
+int build_maps(const char* who, const int32_t* h_counts, int n_tables, std::vector<int>& tok, std::vector<int>& tiles, int* N) {
+  tok.clear();
+  tiles.clear();
+  int n = 0;
+  for (int t = 0; t < n_tables; ++t) {
+    const int c = h_counts[t];
+    PT_REQUIRE(c >= 0 && c <= PT_TSR_MAX_CELLS, "%s: bad cell count %d", who, c);
+    for (int q0 = 0; q0 < c; q0 += 32) { tiles.push_back(n); tiles.push_back(q0); tiles.push_back(c); }
+    for (int r = 0; r < c; ++r) { tok.push_back(t); tok.push_back(r); }
+    n += c;
+  }
+  *N = n;
+  return PT_OK;
+}
+
+// ... to the device (either destination may be null: not wanted) through an engine-owned pinned slot: the vectors die with the call, and a
+// stream synchronise here would make the host wait for everything queued on s
+int upload_maps(pt_engine* e, const char* who, const std::vector<int>& tok, const std::vector<int>& tiles, int* d_tok, int* d_tiles,
+                hipStream_t s) {
+  const size_t nt = d_tok ? tok.size() * 4 : 0, nl = d_tiles ? tiles.size() * 4 : 0;
+  if (nt + nl == 0) return PT_OK;
+  char* hs = static_cast<char*>(e->stage_ring.acquire(nt + nl));
+  PT_REQUIRE(hs, "%s: pinned staging (%s)", who, hipGetErrorString(hipGetLastError()));
+  if (nt) memcpy(hs, tok.data(), nt);
+  if (nl) memcpy(hs + nt, tiles.data(), nl);
+  if (nt) PT_HIP_CHECK(hipMemcpyAsync(d_tok, hs, nt, hipMemcpyHostToDevice, s));
+  if (nl) PT_HIP_CHECK(hipMemcpyAsync(d_tiles, hs + nt, nl, hipMemcpyHostToDevice, s));
+  PT_REQUIRE(e->stage_ring.release(s) == 0, "%s: event record failed", who);
+  return PT_OK;
+}
+
+// the five launches, shared by pt_lore_process and the op-level entry points
+void launch_tok_prepare(const float* logi, const float* dets, const int* d_tok, int N, int Npad, int use_pe, const float* x_pe,
+                        const float* y_pe, bf16_t* x0, bf16_t* cat, int x3, hipStream_t s) {
+  hipLaunchKernelGGL(tok_prepare_kernel, dim3(Npad), dim3(256), 0, s, logi, dets, d_tok, N, use_pe, x_pe, y_pe, x0, cat, x3);
+}
+void launch_norm(const float* x, const float* alpha, const float* bias, bf16_t* out, int rows, int x3, hipStream_t s) {
+  hipLaunchKernelGGL(norm_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, alpha, bias, out, rows, x3);
+}
+void launch_cvt_logic(const float* x, bf16_t* out, int Npad, int x3, hipStream_t s) {
+  hipLaunchKernelGGL(cvt_logic_kernel, dim3((Npad * 32 + 255) / 256), dim3(256), 0, s, x, out, Npad, x3);
+}
+void launch_attention(const bf16_t* qkv, const int* d_tiles, int ntiles, bf16_t* out, int x3, hipStream_t s) {
+  if (x3) hipLaunchKernelGGL(attention_kernel<1>, dim3(ntiles, 8), dim3(64), 0, s, qkv, d_tiles, out);
+  else hipLaunchKernelGGL(attention_kernel<0>, dim3(ntiles, 8), dim3(64), 0, s, qkv, d_tiles, out);
+}
+void launch_scatter4(const float* x, const int* d_tok, int N, float* out, hipStream_t s) {
+  hipLaunchKernelGGL(scatter4_kernel, dim3((N * 4 + 255) / 256), dim3(256), 0, s, x, d_tok, N, out);
+}
+
 struct P : NetCtx {
   int Npad;
   // y = x W^T + b over all tokens: x bf16 [Npad, cin] -> bf16 [Npad, out_c] at channel out_coff, or fp32 [Npad, f32_cs]
@@ -236,13 +288,7 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
   if (!M) return PT_ERR_STATE;
   std::vector<int> tok, tiles;
   int N = 0;
-  for (int t = 0; t < n_tables; ++t) {
-    const int c = h_counts[t];
-    PT_REQUIRE(c >= 0 && c <= PT_TSR_MAX_CELLS, "tsr process: bad cell count %d", c);
-    for (int q0 = 0; q0 < c; q0 += 32) { tiles.push_back(N); tiles.push_back(q0); tiles.push_back(c); }
-    for (int r = 0; r < c; ++r) { tok.push_back(t); tok.push_back(r); }
-    N += c;
-  }
+  if (int rc = build_maps("tsr process", h_counts, n_tables, tok, tiles, &N)) return rc;
   if (N == 0) return PT_OK;
   P p;
   p.init(e, M, "Lore processor", s, 1, PT_ARENA_TSRP);      // n = 1: every GEMM sees the tokens as one [Npad / 32, 32] map
@@ -277,32 +323,21 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
     d_tiles = reinterpret_cast<int*>(take(tiles.size() * 4));
   });
   if (prc != PT_OK) return prc;
-  {
-    // token and tile maps go through an engine-owned pinned slot (the vectors die with this call, and a stream synchronise here would
-    // make the host wait for everything queued on s)
-    char* hs = static_cast<char*>(e->stage_ring.acquire((tok.size() + tiles.size()) * 4));
-    PT_REQUIRE(hs, "tsr process: pinned staging (%s)", hipGetErrorString(hipGetLastError()));
-    memcpy(hs, tok.data(), tok.size() * 4);
-    memcpy(hs + tok.size() * 4, tiles.data(), tiles.size() * 4);
-    PT_HIP_CHECK(hipMemcpyAsync(d_tok, hs, tok.size() * 4, hipMemcpyHostToDevice, s));
-    PT_HIP_CHECK(hipMemcpyAsync(d_tiles, hs + tok.size() * 4, tiles.size() * 4, hipMemcpyHostToDevice, s));
-    PT_REQUIRE(e->stage_ring.release(s) == 0, "tsr process: event record failed");
-  }
+  if (int rc = upload_maps(e, "tsr process", tok, tiles, d_tok, d_tiles, s)) return rc;
 
   const PtTensor *xpe = p.get("x_pe"), *ype = p.get("y_pe");
   if (p.rc != PT_OK) return p.rc;
   const int ntiles = (int)tiles.size() / 3;
   {
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr tok prepare");
-    hipLaunchKernelGGL(tok_prepare_kernel, dim3(Npad), dim3(256), 0, s, d_logi, d_dets, d_tok, N, use_2dpe,
-                       F(xpe), F(ype), x0, cat, x3);
+    launch_tok_prepare(d_logi, d_dets, d_tok, N, Npad, use_2dpe, F(xpe), F(ype), x0, cat, x3, s);
   }
   auto norm = [&](const std::string& q) {
     const PtTensor* a = q.empty() ? nullptr : p.get(q + ".alpha");
     const PtTensor* b = q.empty() ? nullptr : p.get(q + ".bias");
     if (p.rc != PT_OK) return;
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr norm");
-    hipLaunchKernelGGL(norm_kernel, dim3((Npad + 3) / 4), dim3(256), 0, s, x, a ? F(a) : nullptr, b ? F(b) : nullptr, xb, Npad, x3);
+    launch_norm(x, a ? F(a) : nullptr, b ? F(b) : nullptr, xb, Npad, x3, s);
   };
   auto transformer = [&](const std::string& q, const bf16_t* in, int cin, int nl, float* out4) {
     p.gemm(in, cin, q + ".linear", 256, 0, nullptr, 0, 0, x, 256);
@@ -312,8 +347,7 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
       p.gemm(xb, 256, lq + ".qkv", 768, 0, qkv, 768, 0);
       if (p.rc == PT_OK) {
         PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr attention");
-        if (x3) hipLaunchKernelGGL(attention_kernel<1>, dim3(ntiles, 8), dim3(64), 0, s, qkv, d_tiles, att);
-        else hipLaunchKernelGGL(attention_kernel<0>, dim3(ntiles, 8), dim3(64), 0, s, qkv, d_tiles, att);
+        launch_attention(qkv, d_tiles, ntiles, att, x3, s);
       }
       p.gemm(att, 256, lq + ".out", 256, 0, nullptr, 0, 0, x, 256, x);
       norm(lq + ".norm_2");
@@ -329,16 +363,89 @@ int pt_lore_process(pt_engine* e, const float* d_logi, const float* d_dets, cons
   transformer("axis", x0, 256, layers[0], lg);
   {
     PtProfScope ps(e, s, PT_PROF_OTHER, 0, "tsr cvt logic");
-    hipLaunchKernelGGL(cvt_logic_kernel, dim3((Npad * 32 + 255) / 256), dim3(256), 0, s, lg, l32, Npad, x3);
+    launch_cvt_logic(lg, l32, Npad, x3, s);
   }
   p.gemm(l32, 32, "stk.le0", 256, 1, le, 256, 0);
   p.gemm(le, 256, "stk.le2", 256, 1, cat, 512, 0);                    // channels [0, 256) of the concat (:385)
   transformer("stk", cat, 512, layers[1], sk);
   if (p.rc != PT_OK) return p.rc;
-  hipLaunchKernelGGL(scatter4_kernel, dim3((N * 4 + 255) / 256), dim3(256), 0, s, lg, d_tok, N, d_logic);
-  hipLaunchKernelGGL(scatter4_kernel, dim3((N * 4 + 255) / 256), dim3(256), 0, s, sk, d_tok, N, d_stacked);
+  launch_scatter4(lg, d_tok, N, d_logic, s);
+  launch_scatter4(sk, d_tok, N, d_stacked, s);
   PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }
+
+// ---- the kernels above one at a time (tests/test_gpu_lore_proc_ops.py): engine handle and stream only, no model loaded, the launch helpers and
+// the map builder of pt_lore_process on caller-owned buffers.  No allocation on the device and no host synchronisation.  Everything a kernel
+// would index with is checked here: a refused call launches nothing.
+namespace api {
+
+namespace {
+int op_counts(const char* who, const int32_t* h_counts, int n_tables, int Npad, std::vector<int>& tok, std::vector<int>& tiles, int* N) {
+  PT_REQUIRE(h_counts && n_tables >= 1 && n_tables <= 65535, "%s: n_tables = %d (1 .. 65535) with its host counts", who, n_tables);
+  if (int rc = build_maps(who, h_counts, n_tables, tok, tiles, N)) return rc;
+  PT_REQUIRE(Npad >= 128 && Npad % 128 == 0 && Npad >= *N && Npad <= (1 << 24), "%s: Npad = %d must be a multiple of 128 and hold the %d tokens", who, Npad, *N);
+  return PT_OK;
+}
+}  // namespace
+
+int pt_op_lore_tok_prepare(pt_engine* e, const float* d_logi, const float* d_dets, const int32_t* h_counts, int n_tables, int use_pe, const float* d_x_pe,
+                           const float* d_y_pe, int Npad, int32_t* d_tok, uint16_t* d_x0, uint16_t* d_cat, int split, pt_stream stream) {
+  PT_REQUIRE(e && d_logi && d_tok && d_x0 && d_cat, "pt_op_lore_tok_prepare: null argument");
+  PT_REQUIRE(!use_pe || (d_dets && d_x_pe && d_y_pe), "pt_op_lore_tok_prepare: position embeddings need the cell quads and both tables");
+  std::vector<int> tok, tiles;
+  int N = 0;
+  if (int rc = op_counts("pt_op_lore_tok_prepare", h_counts, n_tables, Npad, tok, tiles, &N)) return rc;
+  if (N == 0) return PT_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = upload_maps(e, "pt_op_lore_tok_prepare", tok, tiles, d_tok, nullptr, s)) return rc;
+  launch_tok_prepare(d_logi, d_dets, d_tok, N, Npad, use_pe ? 1 : 0, d_x_pe, d_y_pe, reinterpret_cast<bf16_t*>(d_x0), reinterpret_cast<bf16_t*>(d_cat), split ? 1 : 0, s);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_lore_norm(pt_engine* e, const float* d_x, int rows, const float* d_alpha, const float* d_bias, uint16_t* d_out, int split, pt_stream stream) {
+  PT_REQUIRE(e && d_x && d_out, "pt_op_lore_norm: null argument");
+  PT_REQUIRE((d_alpha == nullptr) == (d_bias == nullptr), "pt_op_lore_norm: alpha and bias go together (both null: conversion only)");
+  PT_REQUIRE(rows >= 1 && rows <= (1 << 24), "pt_op_lore_norm: rows = %d", rows);
+  PT_REQUIRE(((uintptr_t)d_x & 15) == 0, "pt_op_lore_norm: unaligned pointer");
+  launch_norm(d_x, d_alpha, d_bias, reinterpret_cast<bf16_t*>(d_out), rows, split ? 1 : 0, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_lore_cvt_logic(pt_engine* e, const float* d_x, uint16_t* d_out, int Npad, int split, pt_stream stream) {
+  PT_REQUIRE(e && d_x && d_out, "pt_op_lore_cvt_logic: null argument");
+  PT_REQUIRE(Npad >= 128 && Npad % 128 == 0 && Npad <= (1 << 24), "pt_op_lore_cvt_logic: Npad = %d must be a positive multiple of 128", Npad);
+  launch_cvt_logic(d_x, reinterpret_cast<bf16_t*>(d_out), Npad, split ? 1 : 0, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_lore_attention(pt_engine* e, const uint16_t* d_qkv, const int32_t* h_counts, int n_tables, int Npad, int32_t* d_tiles, uint16_t* d_out, int split,
+                         pt_stream stream) {
+  PT_REQUIRE(e && d_qkv && d_tiles && d_out, "pt_op_lore_attention: null argument");
+  PT_REQUIRE(((uintptr_t)d_qkv & 15) == 0, "pt_op_lore_attention: unaligned pointer");
+  std::vector<int> tok, tiles;
+  int N = 0;
+  if (int rc = op_counts("pt_op_lore_attention", h_counts, n_tables, Npad, tok, tiles, &N)) return rc;
+  if (N == 0) return PT_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (int rc = upload_maps(e, "pt_op_lore_attention", tok, tiles, nullptr, d_tiles, s)) return rc;
+  launch_attention(reinterpret_cast<const bf16_t*>(d_qkv), d_tiles, (int)tiles.size() / 3, reinterpret_cast<bf16_t*>(d_out), split ? 1 : 0, s);
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+int pt_op_lore_scatter4(pt_engine* e, const float* d_x, const int32_t* d_tok, int N, float* d_out, pt_stream stream) {
+  PT_REQUIRE(e && d_x && d_tok && d_out, "pt_op_lore_scatter4: null argument");
+  PT_REQUIRE(N >= 0 && N <= (1 << 24), "pt_op_lore_scatter4: N = %d", N);
+  if (N == 0) return PT_OK;
+  launch_scatter4(d_x, d_tok, N, d_out, reinterpret_cast<hipStream_t>(stream));
+  PT_HIP_CHECK(hipGetLastError());
+  return PT_OK;
+}
+
+}  // namespace api
 
 }  // namespace PT_FMT_NS

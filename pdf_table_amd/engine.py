@@ -1415,6 +1415,79 @@ class HipEngine:
         L.check(self.lib.pt_op_mtl_kv_fp8(self._h, _ptr(kv), kv.numel(), _ptr(out), self._stream()), "pt_op_mtl_kv_fp8")
         return out
 
+    # ---- the Lore processor's kernels one at a time (pt_op_lore_* in include/pdftable_hip.h): outputs are the caller's, so that a test can pre-fill them
+    @staticmethod
+    def _lore_counts(counts):
+        import numpy as np
+        hc = np.ascontiguousarray(counts, dtype=np.int32)
+        return hc, int(hc.clip(0, L.PT_TSR_MAX_CELLS).sum()), int(((hc.clip(0, L.PT_TSR_MAX_CELLS) + 31) // 32).sum())
+
+    def op_lore_tok_prepare(self, logi: torch.Tensor, dets: Optional[torch.Tensor], counts, x_pe: Optional[torch.Tensor], y_pe: Optional[torch.Tensor],
+                            x0: torch.Tensor, cat: torch.Tensor, use_pe: bool, split: bool = False) -> torch.Tensor:
+        """pt_op_lore_tok_prepare into the caller's x0 [Npad, 256] and cat [Npad, 512] (x 2 when split) -> the device token map int32 [N, 2]"""
+        hc, N, _ = self._lore_counts(counts)
+        m = 2 if split else 1
+        self._chk(logi, torch.float32, "logi")
+        self._chk(x0, self.act_dtype, "x0")
+        self._chk(cat, self.act_dtype, "cat")
+        for t, name in ((dets, "dets"), (x_pe, "x_pe"), (y_pe, "y_pe")):
+            if t is not None:
+                self._chk(t, torch.float32, name)
+        Npad = x0.shape[0]
+        if (logi.shape != (len(hc), L.PT_TSR_MAX_CELLS, 256) or (dets is not None and dets.shape != (len(hc), L.PT_TSR_MAX_CELLS, 9)) or x0.shape != (Npad, 256 * m)
+                or cat.shape != (Npad, 512 * m) or any(t is not None and t.shape != (256, 256) for t in (x_pe, y_pe))):
+            raise ValueError("op_lore_tok_prepare: operands do not fit the counts")
+        tok = torch.full((max(N, 1), 2), -1, dtype=torch.int32, device=self._tdev)
+        L.check(self.lib.pt_op_lore_tok_prepare(self._h, _ptr(logi), _ptr(dets), hc.ctypes.data, len(hc), int(use_pe), _ptr(x_pe), _ptr(y_pe), Npad, _ptr(tok),
+                                                _ptr(x0), _ptr(cat), int(split), self._stream()), "pt_op_lore_tok_prepare")
+        return tok[:N]
+
+    def op_lore_norm(self, x: torch.Tensor, alpha: Optional[torch.Tensor], bias: Optional[torch.Tensor], out: torch.Tensor, split: bool = False) -> torch.Tensor:
+        """pt_op_lore_norm of fp32 rows [rows, 256] into the caller's `out` (at least rows x 256, x 2 when split); alpha = bias = None: conversion only"""
+        self._chk(x, torch.float32, "x")
+        self._chk(out, self.act_dtype, "out")
+        for t in (alpha, bias):
+            if t is not None:
+                self._chk(t, torch.float32, "alpha / bias")
+        if x.dim() != 2 or x.shape[1] != 256 or out.numel() < x.numel() * (2 if split else 1) or any(t is not None and t.numel() != 256 for t in (alpha, bias)):
+            raise ValueError("op_lore_norm: x must be [rows, 256], out at least as large, alpha / bias [256]")
+        L.check(self.lib.pt_op_lore_norm(self._h, _ptr(x), x.shape[0], _ptr(alpha), _ptr(bias), _ptr(out), int(split), self._stream()), "pt_op_lore_norm")
+        return out
+
+    def op_lore_cvt_logic(self, x: torch.Tensor, out: torch.Tensor, split: bool = False) -> torch.Tensor:
+        """pt_op_lore_cvt_logic: fp32 [Npad, 8] into the caller's `out` [Npad, 32] (x 2 when split)"""
+        self._chk(x, torch.float32, "x")
+        self._chk(out, self.act_dtype, "out")
+        if x.dim() != 2 or x.shape[1] != 8 or out.numel() < x.shape[0] * 32 * (2 if split else 1):
+            raise ValueError("op_lore_cvt_logic: x must be [Npad, 8], out at least [Npad, 32]")
+        L.check(self.lib.pt_op_lore_cvt_logic(self._h, _ptr(x), _ptr(out), x.shape[0], int(split), self._stream()), "pt_op_lore_cvt_logic")
+        return out
+
+    def op_lore_attention(self, qkv: torch.Tensor, counts, out: torch.Tensor, split: bool = False) -> torch.Tensor:
+        """pt_op_lore_attention: qkv [Npad, 768] (x 2 when split) into the caller's `out` [Npad, 256] (x 2 when split) -> the device tile list int32 [tiles, 3]"""
+        hc, _, ntiles = self._lore_counts(counts)
+        m = 2 if split else 1
+        self._chk(qkv, self.act_dtype, "qkv")
+        self._chk(out, self.act_dtype, "out")
+        Npad = qkv.shape[0]
+        if qkv.dim() != 2 or qkv.shape[1] != 768 * m or out.shape != (Npad, 256 * m):
+            raise ValueError(f"op_lore_attention: qkv must be [Npad, {768 * m}] and out [Npad, {256 * m}]")
+        tiles = torch.full((max(ntiles, 1), 3), -1, dtype=torch.int32, device=self._tdev)
+        L.check(self.lib.pt_op_lore_attention(self._h, _ptr(qkv), hc.ctypes.data, len(hc), Npad, _ptr(tiles), _ptr(out), int(split), self._stream()),
+                "pt_op_lore_attention")
+        return tiles[:ntiles]
+
+    def op_lore_scatter4(self, x: torch.Tensor, tok: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        """pt_op_lore_scatter4: fp32 token rows [>= N, 8] -> the caller's `out` [n_tables, PT_TSR_MAX_CELLS, 4] at the (table, row) pairs of tok int32 [N, 2]"""
+        self._chk(x, torch.float32, "x")
+        self._chk(tok, torch.int32, "tok")
+        self._chk(out, torch.float32, "out")
+        N = tok.shape[0]
+        if x.dim() != 2 or x.shape[1] != 8 or x.shape[0] < N or out.dim() != 3 or out.shape[1:] != (L.PT_TSR_MAX_CELLS, 4):
+            raise ValueError("op_lore_scatter4: x must be [>= N, 8], out [n_tables, PT_TSR_MAX_CELLS, 4]")
+        L.check(self.lib.pt_op_lore_scatter4(self._h, _ptr(x), _ptr(tok), N, _ptr(out), self._stream()), "pt_op_lore_scatter4")
+        return out
+
     def op_lstm(self, pregates: torch.Tensor, r_packed: torch.Tensor, hidden: int, dirs: int, reverse: bool, out_c: int, split: bool = False) -> torch.Tensor:
         """The recurrence of an ONNX LSTM layer (pt_op_lstm; hidden <= 128, zero initial states).  pregates [B, 1, T, dirs * 4 * Hp] (x m halves
         when split) = X W^T + Wb + Rb, gates i, o, f, c per direction; r_packed: weights.pack_lstm_r(R) on the device -> token rows

@@ -43,7 +43,7 @@ PT_CENTERNET_MAX_CELLS = 1000
 PT_ROTATE_90_CLOCKWISE, PT_ROTATE_180, PT_ROTATE_90_COUNTERCLOCKWISE = 0, 1, 2   # cv2.rotate codes (pt_page_quarter_turn)
 PT_REC_H, PT_REC_W, PT_REC_T, PT_REC_NCLS = 32, 640, 160, 7644
 PT_PROF_CLASSES = ("conv3x3", "conv1x1", "stem", "other")
-EXPECTED_ABI = 20         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h).  20: pt_op_mtl_*.  19: pt_op_cvit_*.  pt_op_affine_act /
+EXPECTED_ABI = 21         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h).  21: pt_op_lore_tok_prepare .. scatter4.  20: pt_op_mtl_*.  19: pt_op_cvit_*.  pt_op_affine_act /
 #                           pt_op_db_tail were ADDED under 18: no existing signature changed, and a library without them fails to bind by name (_proto);
 #                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large / pt_op_lore_hm_head / pt_op_ctc_greedy / pt_op_sla_* / pt_op_table_match / pt_op_pico_candidates under 19, pt_op_lore_match / pt_op_layout_decode under 20
 
@@ -157,6 +157,11 @@ def _proto(lib):
         "pt_op_mtl_cross_attention": (i, [vp, i, vp, vp, i, i, i, vp, i, vp, i, i, i, i, i, vp, vp, vp, i, i, C.c_longlong, C.c_longlong, C.c_longlong, vp]),
         "pt_op_mtl_self_attention": (i, [vp, vp, vp, i, i, i, i, i, vp, i, i, C.c_longlong, C.c_longlong, vp]),
         "pt_op_mtl_kv_fp8": (i, [vp, vp, C.c_longlong, vp, vp]),
+        "pt_op_lore_tok_prepare": (i, [vp, vp, vp, vp, i, i, vp, vp, i, vp, vp, vp, i, vp]),
+        "pt_op_lore_norm": (i, [vp, vp, i, vp, vp, vp, i, vp]),
+        "pt_op_lore_cvt_logic": (i, [vp, vp, vp, i, i, vp]),
+        "pt_op_lore_attention": (i, [vp, vp, vp, i, i, vp, vp, i, vp]),
+        "pt_op_lore_scatter4": (i, [vp, vp, vp, i, vp, vp]),
         "pt_op_conv2d_rect": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, i, i, vp, i, i, i, i, i, vp]),
         "pt_op_conv2d_large": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, vp, i, i, i, i, i, vp]),
         "pt_op_dwconv_rect": (i, [vp, vp, i, i, i, i, vp, vp, i, i, i, i, vp, i, vp]),

@@ -75,6 +75,6 @@ def test_binding_has_the_large_convolution():
     from pdf_table_amd.build import build
     build(verbose=False)
     L.load()
-    assert L.EXPECTED_ABI == 20 and "pt_op_conv2d_large" in L.EXPORTS
+    assert L.EXPECTED_ABI == 21 and "pt_op_conv2d_large" in L.EXPORTS
     from pdf_table_amd.engine import HipEngine
     assert callable(getattr(HipEngine, "op_conv2d_large"))

@@ -94,7 +94,7 @@ def test_new_entry_point_in_header_library_and_binding():
     lib = ctypes.CDLL(build(verbose=False))
     assert hasattr(lib, "pt_op_ctc_greedy")
     bound = L.load()
-    assert "pt_op_ctc_greedy" in L.EXPORTS and L.EXPECTED_ABI == 20 == lib.pt_abi_version()     # added under ABI 19; 20 added pt_op_mtl_*
+    assert "pt_op_ctc_greedy" in L.EXPORTS and L.EXPECTED_ABI == 21 == lib.pt_abi_version()     # added under ABI 19; 20 added pt_op_mtl_*, 21 pt_op_lore_tok_prepare .. scatter4
     # bad arguments are refused before anything is launched (no device needed: the engine pointer is checked first)
     assert bound.pt_op_ctc_greedy(None, None, 1, 8, 1, None, None, 0, None) != 0
     assert b"pt_op_ctc_greedy" in bound.pt_last_error()

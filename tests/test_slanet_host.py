@@ -134,7 +134,7 @@ def test_header_declares_the_entry_points():
         assert f"int {name}(" in hdr
     from pdf_table_amd import lib as L
     L.load()
-    assert L.EXPECTED_ABI == 20 and {"pt_op_sla_decode", "pt_slanet_preprocess"} <= set(L.EXPORTS)    # added under ABI 19; 20 added pt_op_mtl_*
+    assert L.EXPECTED_ABI == 21 and {"pt_op_sla_decode", "pt_slanet_preprocess"} <= set(L.EXPORTS)    # added under ABI 19; 20 added pt_op_mtl_*, 21 the Lore processor's op entries
 
 
 def test_refusals_without_a_device(tmp_path):
