@@ -121,6 +121,7 @@ enum {
   PT_MODEL_MTL_BACKBONE = 17, /* table/mtl_tabnet/table_resnet_extra.py:205-318 (TableResNetExtra, backbone of MtlTabNet) */
   PT_MODEL_MTL_DECODER = 18,  /* table/mtl_tabnet/master_decoder.py:194-531 (MtlTabNetDecoder: structure, box and cell-content decoders) */
   PT_MODEL_CENTERNET_DLA34 = 19, /* center_net/modeling_centernet.py:609-661 (DLASeg on dla34, no DCN: CenterNet table cells) */
+  PT_MODEL_DOCX_DLA34 = 20,      /* docx_layout/model_dla.py:543-652 (DLASeg on dla34, eight heads: DocXLayout page layout) */
 };
 int pt_weights_load(pt_engine* e, int model_kind, const void* h_blob, size_t nbytes);
 /* Same, but the blob already sits in device memory (e.g. after an RCCL broadcast from rank 0). */
@@ -437,6 +438,45 @@ int pt_centernet_forward_net(pt_engine* e, const uint16_t* d_input_bf16, int n, 
 #define PT_CENTERNET_MAX_CELLS 1000
 int pt_centernet_decode(pt_engine* e, const float* d_hm, const float* d_v2c, const float* d_c2v, const float* d_reg, int n, int h, int w,
                         const double* d_affine, int32_t* d_counts, float* d_cells, pt_stream stream);
+
+/* ---- DocXLayout page layout (DocXLayoutModel = DLASeg('dla34', down_ratio 4, head_conv 256) with eight heads, docx_layout/model_dla.py:543-652;
+ * weights PT_MODEL_DOCX_DLA34).  Entry points added by name under the current ABI number: no existing signature changed. ------------------- */
+/* pt_tsr_preprocess's warp (cv2.warpAffine INTER_LINEAR fixed-point arithmetic, zero border, pt_tsr_table records, bgr flag) with the normalisation
+ * ((v / 255.) - mean[c]) / std[c] (fp64, rounded to fp32 once, as numpy evaluates it) for constants handed in: mean3 / std3 are HOST float32 [3] in
+ * the order of the OUTPUT channels (after the bgr flip).  DocXLayout's are {0.40789655, 0.44719303, 0.47026116} / {0.2886383, 0.27408165,
+ * 0.27809834} (docx_layout/image_processing_docxlayout.py:110-145).  A change of constants between calls rebuilds the engine's table behind a
+ * device synchronisation. */
+int pt_docx_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* d_tables, int n, int inp_h,
+                       int inp_w, int bgr, const float* mean3, const float* std3, uint16_t* d_out_bf16, pt_stream stream);
+
+/* Detector network: d_input_bf16 as pt_docx_preprocess writes it (H, W multiples of 32).  Outputs: fp32 NHWC head maps at H/4 x W/4, pre-sigmoid;
+ * d_hm has channel stride 16 (11 valid), every other head stride 8: cls (4 valid), ftype (3), hm_sub (2), reg (2), reg_sub (2), wh (8), wh_sub (8).
+ * Activations live in the layout stage's arena, so a table-structure net of the same engine may be in flight on another stream. */
+int pt_docx_forward_net(pt_engine* e, const uint16_t* d_input_bf16, int n, int H, int W, float* d_cls, float* d_ftype, float* d_hm, float* d_hm_sub,
+                        float* d_reg, float* d_reg_sub, float* d_wh, float* d_wh_sub, pt_stream stream);
+
+/* Device half of DocXLayoutImagePostProcessor.post_process_model + pnms (docx_layout/image_processing_docxlayout.py:265-308, processor_utils.py:22-158)
+ * for n pages' head maps (h x w, layouts as pt_docx_forward_net writes them), one launch, no engine.  Per page two branches: 0 = main (d_hm: ncls_main
+ * classes at channel stride 16, d_wh, d_reg, d_cls, d_ftype), 1 = sub (d_hm_sub: ncls_sub classes at stride 8, d_wh_sub, d_reg_sub).
+ *   peaks    : fp32 sigmoid; a pixel of class c is a peak when its sigmoid equals the maximum of class c's sigmoids over its 3 x 3 window (outside
+ *              the map does not count)
+ *   list     : the first K peaks with sigmoid >= thr_lo over all classes of the branch, by (score descending, class * h * w + pixel ascending) --
+ *              exactly that list whatever the number of peaks
+ *   d_counts : int32 [n][2]      entries of each list (<= K)
+ *   d_recs   : float32 [n][2][K][PT_DOCX_REC_FLOATS]  rows [0, count): x0, y0 .. x3, y3 in head-map pixels (xs = x + reg[0], ys = y + reg[1], corner i =
+ *              (xs - wh[2i], ys - wh[2i + 1])), score, class (0-based in its branch), then for branch 0 the index of the first maximum of the 4 cls
+ *              sigmoids and of the 3 ftype sigmoids at the pixel; branch 1 writes 0 in both (the reference copies branch 0's columns of the same
+ *              rank there, and nothing reads them)
+ *   d_inds   : int32 [n][2][K]   class * h * w + pixel of each row; may be null
+ *   d_keep   : uint8 [n][2][K]   pnms: 1 when (double)score >= 0.3 and no other row of the list with (double)score >= 0.3 and a larger score has the
+ *              row's centre strictly inside its quad (fp64, products and sums unfused); 0 otherwise
+ * Rows at and behind `count` are not written.  PT_ERR_INVALID without a launch: K > PT_DOCX_MAX_K, a branch with more than 16 classes (or more than
+ * its channel stride), a map above 512 x 512. */
+#define PT_DOCX_REC_FLOATS 12
+#define PT_DOCX_MAX_K 128
+int pt_docx_decode(const float* d_hm, const float* d_wh, const float* d_reg, const float* d_cls, const float* d_ftype, const float* d_hm_sub,
+                   const float* d_wh_sub, const float* d_reg_sub, int n, int h, int w, int ncls_main, int ncls_sub, int K, float thr_lo,
+                   int32_t* d_counts, float* d_recs, int32_t* d_inds, uint8_t* d_keep, pt_stream stream);
 
 /* Logical-location processor (LoreProcessModel.forward, lore/lore_processor.py:465-514, evaluation branch) for the
  * cells of n_tables tables at once.

@@ -95,6 +95,7 @@ void pt_engine_destroy(pt_engine* e) {
   if (e->zero_page) (void)hipFree(e->zero_page);
   if (e->tsr_scratch) (void)hipFree(e->tsr_scratch);
   if (e->tsr_lut) (void)hipFree(e->tsr_lut);
+  if (e->docx_lut) (void)hipFree(e->docx_lut);
   for (int i = 0; i < 4; ++i) {
     if (e->tsr_pad_l2[i]) (void)hipFree(e->tsr_pad_l2[i]);
     if (e->tsr_pad_l2_ready[i]) (void)hipEventDestroy(e->tsr_pad_l2_ready[i]);
@@ -365,6 +366,35 @@ int pt_tsr_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int
   if (rc != PT_OK) return rc;
   return pt_launch_tsr_preprocess(d_pages_rgb, ph, pw, d_tables, n, inp_h, inp_w, bgr, lut, d_out_bf16,
                                   pt_split(e), reinterpret_cast<hipStream_t>(stream));
+}
+
+// pt_tsr_preprocess's warp (the same kernel) with a normalisation table built from the caller's constants: lut[c][v] = float(((v / 255.) - mean[c]) /
+// std[c]) in fp64 with the float32 constants widened, as numpy evaluates image_processing_docxlayout.py:145.  The table is the engine's, rebuilt (a
+// blocking copy, like pt_lore_norm_lut's first call) only when the constants change
+int pt_docx_preprocess(pt_engine* e, const uint8_t* d_pages_rgb, int n_pages, int ph, int pw, const pt_tsr_table* d_tables, int n, int inp_h,
+                       int inp_w, int bgr, const float* mean3, const float* std3, uint16_t* d_out_bf16, pt_stream stream) {
+  PT_REQUIRE(e && d_pages_rgb && d_tables && d_out_bf16 && mean3 && std3 && n > 0 && n_pages > 0, "pt_docx_preprocess: bad arguments");
+  PT_REQUIRE(std3[0] > 0.f && std3[1] > 0.f && std3[2] > 0.f, "pt_docx_preprocess: std must be positive");
+  PT_HIP_CHECK(hipSetDevice(e->device));
+  float key[6] = {mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]};
+  if (!e->docx_lut || memcmp(key, e->docx_lut_key, sizeof(key)) != 0) {
+    float lut[768];
+    for (int c = 0; c < 3; ++c)
+      for (int v = 0; v < 256; ++v) lut[c * 256 + v] = (float)(((double)v / 255.0 - (double)mean3[c]) / (double)std3[c]);
+    if (!e->docx_lut) PT_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&e->docx_lut), sizeof(lut)));
+    else PT_HIP_CHECK(hipDeviceSynchronize());      // a launch in flight may still read the old table
+    PT_HIP_CHECK(hipMemcpy(e->docx_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
+    memcpy(e->docx_lut_key, key, sizeof(key));
+  }
+  return pt_launch_tsr_preprocess(d_pages_rgb, ph, pw, d_tables, n, inp_h, inp_w, bgr, e->docx_lut, d_out_bf16, pt_split(e),
+                                  reinterpret_cast<hipStream_t>(stream));
+}
+
+int pt_docx_forward_net(pt_engine* e, const uint16_t* d_input_bf16, int n, int H, int W, float* d_cls, float* d_ftype, float* d_hm, float* d_hm_sub,
+                        float* d_reg, float* d_reg_sub, float* d_wh, float* d_wh_sub, pt_stream stream) {
+  PT_REQUIRE(e && d_input_bf16 && n > 0, "pt_docx_forward_net: bad arguments");
+  PT_HIP_CHECK(hipSetDevice(e->device));
+  return pt_docx_net(e, d_input_bf16, n, H, W, d_cls, d_ftype, d_hm, d_hm_sub, d_reg, d_reg_sub, d_wh, d_wh_sub, reinterpret_cast<hipStream_t>(stream));
 }
 
 int pt_tsr_band_radius(void) { return pt_lore_band_radius(); }

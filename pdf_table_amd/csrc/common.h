@@ -173,6 +173,8 @@ struct pt_engine {
   void* tsr_scratch = nullptr; size_t tsr_scratch_cap = 0;   // candidate lists of the Lore decode
   void* layout_scratch = nullptr; size_t layout_scratch_cap = 0;   // layout input + head maps (pt_layout_forward)
   float* tsr_lut = nullptr;                                  // [3][256] normalisation table of the Lore pre-process
+  float* docx_lut = nullptr;                                 // [3][256] normalisation table of pt_docx_preprocess, built for docx_lut_key
+  float docx_lut_key[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};    // (mean[3], std[3]) the table holds; std 0 = none yet
   float* cls_lut = nullptr;                                  // [3][256] ... of the PP-LCNet pre-process
   void* cls_direct_in = nullptr; size_t cls_direct_in_cap = 0;   // network input of pt_cls_forward_lines_direct (one micro-batch)
   float* rec_pp_lut = nullptr;                               // [256] (v / 255 - 0.5) / 0.5 of the PP-OCR recognition pre-process
@@ -519,6 +521,8 @@ constexpr int PT_HEAT_CAP = 16384;      // peak candidates per (table, class) li
 int pt_heat_peaks_topk(const float* hm, int B, int H, int W, float thr0, float thr1, int k0, int k1, float* sig, unsigned long long* keys,
                        int* cnt, unsigned long long* sorted, int* kept, hipStream_t s);
 int pt_centernet_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* hm, float* v2c, float* c2v, float* reg, hipStream_t s);
+int pt_docx_net(pt_engine* e, const bf16_t* x, int n, int H, int W, float* cls, float* ftype, float* hm, float* hm_sub, float* reg, float* reg_sub,
+                float* wh, float* wh_sub, hipStream_t s);
 int pt_centernet_decode_maps(pt_engine* e, const float* hm, const float* v2c, const float* c2v, const float* reg, int B, int H, int W,
                              const double* affine, int* d_counts, float* d_cells, hipStream_t s);
 

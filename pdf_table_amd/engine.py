@@ -387,6 +387,65 @@ class HipEngine:
                                              _ptr(cells), self._stream()), "pt_centernet_decode")
         return (counts.cpu().numpy() if sync else counts), cells
 
+    DOCX_HEADS = {"cls": 4, "ftype": 3, "hm": 11, "hm_sub": 2, "reg": 2, "reg_sub": 2, "wh": 8, "wh_sub": 8}     # configuration_docxlayout.py:45-46
+
+    def docx_preprocess(self, pages: torch.Tensor, tables, inp_h: int = 768, inp_w: int = 768, bgr: bool = True,
+                        mean=(0.40789655, 0.44719303, 0.47026116), std=(0.2886383, 0.27408165, 0.27809834)):
+        """tsr_preprocess's warp with ``((v / 255) - mean) / std`` for the constants given (float32, in the order of the output channels):
+        pages uint8 [np,h,w,3] on the device, tables numpy TSR_TABLE_DTYPE -> 16-bit NHWC4 [n,inp_h,inp_w,4|8] (pt_docx_preprocess)."""
+        self._chk(pages, torch.uint8, "pages")
+        npg, ph, pw, _ = pages.shape
+        n = len(tables)
+        tb = _upload(tables.view(np.uint8).reshape(n, -1), self._tdev)
+        out = torch.empty((n, inp_h, inp_w, 8 if self.split else 4), dtype=self.act_dtype, device=self._tdev)
+        m3 = (C.c_float * 3)(*[float(v) for v in mean])
+        s3 = (C.c_float * 3)(*[float(v) for v in std])
+        L.check(self.lib.pt_docx_preprocess(self._h, _ptr(pages), npg, ph, pw, _ptr(tb), n, inp_h, inp_w, int(bgr), m3, s3, _ptr(out),
+                                            self._stream()), "pt_docx_preprocess")
+        return out
+
+    def docx_forward_net(self, x: torch.Tensor, out=None):
+        """DocXLayout layout detector (DLA-34 + DLAUp + eight heads, PT_MODEL_DOCX_DLA34): x 16-bit NHWC4 [n,H,W,4] (pair modes: 8 channels) ->
+        dict of fp32 NHWC head maps at H/4 x W/4, pre-sigmoid: 'hm' [n,h,w,16] (11 valid), every other head [n,h,w,8] (DOCX_HEADS valid).
+        out: such a dict to write into (slices of a larger allocation: several micro-batches then feed ONE decode launch)."""
+        self._chk(x, self.act_dtype, "x")
+        n, H, W, c = x.shape
+        assert c == (8 if self.split else 4)
+        if out is None:
+            out = {k: torch.empty((n, H // 4, W // 4, 16 if k == "hm" else 8), dtype=torch.float32, device=self._tdev) for k in self.DOCX_HEADS}
+        for k in self.DOCX_HEADS:
+            self._chk(out[k], torch.float32, k)
+            assert tuple(out[k].shape) == (n, H // 4, W // 4, 16 if k == "hm" else 8), (k, tuple(out[k].shape))
+        L.check(self.lib.pt_docx_forward_net(self._h, _ptr(x), n, H, W, *[_ptr(out[k]) for k in ("cls", "ftype", "hm", "hm_sub", "reg", "reg_sub", "wh",
+                                                                                                "wh_sub")], self._stream()), "pt_docx_forward_net")
+        return out
+
+    def docx_decode(self, heads, top_k: int = 100, thr_lo: float = 0.3 - 1e-3, ncls_main: int = 11, ncls_sub: int = 2, out=None, with_inds: bool = True):
+        """heads: the dict of docx_forward_net -> (counts int32 [n,2], records f32 [n,2,K,12], flat indices int32 [n,2,K] or None, keep uint8 [n,2,K]),
+        all on the device (pt_docx_decode: peaks, joint top-K, corners, arg-max columns and the polygon NMS of both branches in one launch).  Rows at
+        and behind a count are not written.  out: the four tensors to write into."""
+        n, h, w, _ = heads["hm"].shape
+        for k in self.DOCX_HEADS:
+            self._chk(heads[k], torch.float32, k)
+            assert tuple(heads[k].shape) == (n, h, w, 16 if k == "hm" else 8), (k, tuple(heads[k].shape))
+        K = int(top_k)
+        if out is None:
+            out = (torch.zeros((n, 2), dtype=torch.int32, device=self._tdev),
+                   torch.zeros((n, 2, max(K, 1), L.PT_DOCX_REC_FLOATS), dtype=torch.float32, device=self._tdev),
+                   torch.zeros((n, 2, max(K, 1)), dtype=torch.int32, device=self._tdev) if with_inds else None,
+                   torch.zeros((n, 2, max(K, 1)), dtype=torch.uint8, device=self._tdev))
+        counts, recs, inds, keep = out
+        kb = max(K, 1)      # an out-of-range K is refused by the library; the buffers must hold whatever K it may accept
+        assert tuple(counts.shape) == (n, 2) and counts.dtype == torch.int32 and counts.is_contiguous()
+        assert tuple(recs.shape) == (n, 2, recs.shape[2], L.PT_DOCX_REC_FLOATS) and recs.dtype == torch.float32 and recs.is_contiguous()
+        assert tuple(keep.shape) == (n, 2, recs.shape[2]) and keep.dtype == torch.uint8 and keep.is_contiguous()
+        assert inds is None or (tuple(inds.shape) == (n, 2, recs.shape[2]) and inds.dtype == torch.int32 and inds.is_contiguous())
+        assert recs.shape[2] == kb or not 1 <= K <= L.PT_DOCX_MAX_K, (recs.shape, K)
+        L.check(self.lib.pt_docx_decode(_ptr(heads["hm"]), _ptr(heads["wh"]), _ptr(heads["reg"]), _ptr(heads["cls"]), _ptr(heads["ftype"]),
+                                        _ptr(heads["hm_sub"]), _ptr(heads["wh_sub"]), _ptr(heads["reg_sub"]), n, h, w, int(ncls_main), int(ncls_sub), K,
+                                        float(thr_lo), _ptr(counts), _ptr(recs), _ptr(inds), _ptr(keep), self._stream()), "pt_docx_decode")
+        return counts, recs, inds, keep
+
     def tsr_process(self, logi: torch.Tensor, dets: torch.Tensor, counts, use_2dpe: bool = False):
         """logic features of pt_tsr_decode -> (logic_axis, stacked_axis) f32 [n,3000,4]; rows [0, counts[i]) valid."""
         import numpy as np

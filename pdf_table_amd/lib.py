@@ -24,6 +24,7 @@ PT_MODEL_CONVNEXT_VIT = 16
 PT_MODEL_MTL_BACKBONE = 17
 PT_MODEL_MTL_DECODER = 18
 PT_MODEL_CENTERNET_DLA34 = 19
+PT_MODEL_DOCX_DLA34 = 20
 PT_CVIT_W, PT_CVIT_CHUNK_W, PT_CVIT_CHUNK_STEP, PT_CVIT_T, PT_CVIT_NCLS = 804, 300, 252, 201, 7644
 PT_CLS_SLOTS = 4
 PT_CLS_MAX_CLASSES = 16
@@ -40,12 +41,13 @@ PT_DET_POST_DB_TORCH = 1
 PT_MTL_ATTN_STREAM, PT_MTL_ATTN_STREAM8, PT_MTL_ATTN_MFMA = 0, 1, 2
 PT_TSR_MAX_CELLS = 3000
 PT_CENTERNET_MAX_CELLS = 1000
+PT_DOCX_REC_FLOATS, PT_DOCX_MAX_K = 12, 128
 PT_ROTATE_90_CLOCKWISE, PT_ROTATE_180, PT_ROTATE_90_COUNTERCLOCKWISE = 0, 1, 2   # cv2.rotate codes (pt_page_quarter_turn)
 PT_REC_H, PT_REC_W, PT_REC_T, PT_REC_NCLS = 32, 640, 160, 7644
 PT_PROF_CLASSES = ("conv3x3", "conv1x1", "stem", "other")
 EXPECTED_ABI = 21         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h).  21: pt_op_lore_tok_prepare .. scatter4.  20: pt_op_mtl_*.  19: pt_op_cvit_*.  pt_op_affine_act /
 #                           pt_op_db_tail were ADDED under 18: no existing signature changed, and a library without them fails to bind by name (_proto);
-#                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large / pt_op_lore_hm_head / pt_op_ctc_greedy / pt_op_sla_* / pt_op_table_match / pt_op_pico_candidates under 19, pt_op_lore_match / pt_op_layout_decode under 20
+#                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large / pt_op_lore_hm_head / pt_op_ctc_greedy / pt_op_sla_* / pt_op_table_match / pt_op_pico_candidates under 19, pt_op_lore_match / pt_op_layout_decode under 20, pt_docx_preprocess / pt_docx_forward_net / pt_docx_decode under 21
 
 _lib = None
 
@@ -112,6 +114,9 @@ def _proto(lib):
         "pt_tsr_process": (i, [vp, vp, vp, vp, i, i, vp, vp, vp]),
         "pt_centernet_forward_net": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp]),
         "pt_centernet_decode": (i, [vp, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp]),
+        "pt_docx_preprocess": (i, [vp, vp, i, i, i, vp, i, i, i, i, C.POINTER(f), C.POINTER(f), vp, vp]),      # added under ABI 21, bound by name
+        "pt_docx_forward_net": (i, [vp, vp, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]),      # likewise
+        "pt_docx_decode": (i, [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp, vp, vp]),      # likewise
         "pt_hard_nms": (i, [vp, vp, vp, i, C.c_double, i, vp, vp]),
         "pt_page_line_mask": (i, [vp, i, i, i, vp, vp]),
         "pt_page_line_angles": (i, [vp, i, i, i, i, i, vp, i, vp]),

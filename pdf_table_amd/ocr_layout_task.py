@@ -4,7 +4,12 @@ Reference: src/pdftable/model/ocr_pdf/ocr_layout_task.py:30-157.  Same construct
 result: one list per input image of ``{"bbox": ndarray [4] (x1, y1, x2, y2 in source pixels; float64 holding float32-rounded corners divided by the scale, as in the reference), "label", "score",
 "category_id"}`` (:125-141, picodet/processor_picodet.py:286-296).  The reference runs an ONNX export of PaddleDetection's
 picodet_lcnet_x1_0 layout model; here the in-tree LCNet + CSP-PAN + PicoHead graph (assumed hyper-parameters, see
-pdf_table_amd.synth_weights.picodet_state_dict) runs on the engine.  ``DocXLayout`` is not built and fails loudly.
+pdf_table_amd.synth_weights.picodet_state_dict) runs on the engine.
+
+``model="DocXLayout"`` (the reference's only torch layout model, ocr_layout_task.py:45-68) serves a checkpoint given as ``task_path=<file or
+directory>`` (docxlayout_stage.load_checkpoint) through ``DocXLayoutStage``: same result shape, labels of ``DocXLayoutConfig``.  There are no
+seeded in-tree weights for it: without a checkpoint the constructor raises ``RuntimeError``, also when ``synthetic_seed`` is set.  ``device_decode``
+is PicoDet's decode and raises ``ValueError`` for this model (its decode always runs on the device).
 
 ONNX door (the reference's layout stage is ONNX-only: "pytorch model not support yet!", ocr_layout_task.py:82-123): a ``model.onnx`` /
 ``inference.onnx`` under ``task_path`` (or ``task_path`` = the file) is parsed by ``pdf_table_amd.onnx_import`` and run layer by layer by
@@ -40,8 +45,22 @@ class OcrLayoutTask(BaseInferTask):
         super().__init__(task=task, model=model, **kwargs)
         if model not in ["picodet", "DocXLayout"]:
             raise RuntimeError(f"current model is not supported: {model}")
-        if model != "picodet":
-            raise RuntimeError(f"layout model '{model}' is not built on the HIP engine; only 'picodet' is")
+        if model == "DocXLayout":
+            if self._device_decode:
+                raise ValueError("device_decode=True selects PicoDet's device decode; DocXLayout's decode (pt_docx_decode) always runs on the device")
+            from .docxlayout_stage import DocXLayoutConfig
+            self._config = DocXLayoutConfig()
+            self.model_provider = "model_scope"
+            self._engine = engine
+            tp = kwargs.get("task_path")
+            if not tp or not os.path.exists(str(tp)):
+                raise RuntimeError("layout model 'DocXLayout' has no in-tree (seeded) weights: pass task_path=<checkpoint file (.pth / .bin / .pt) or "
+                                   "directory holding pytorch_model.bin> (synthetic_seed= does not apply)")
+            self._config.model_path = str(tp)
+            if "resolution" in kwargs:      # the network input; the reference's is fixed at 768 x 768 (tests use smaller ones)
+                self._config.resolution = tuple(int(v) for v in kwargs["resolution"])
+            self._get_inference_model()
+            return
         tt = kwargs.get("task_type", "en")
         self._config = PicodetConfig(task_type="ch" if tt == "zh" else tt)
         self.model_provider = "PaddleOCR"
@@ -52,9 +71,24 @@ class OcrLayoutTask(BaseInferTask):
             self._config.model_path = self._task_path
         self._get_inference_model()
 
+    def _construct_docxlayout(self):
+        from .docxlayout_stage import load_checkpoint
+        from .weights import pack_docxlayout_dla34
+        sd = load_checkpoint(self._config.model_path)
+        sp = str(self.kwargs.get("stage_precision") or "").lower()
+        self._stage_precision = L.PT_PRECISION_BF16X3 if sp in ("fp32", "bf16x3", "float32") else None
+        if sp and self._stage_precision is None:
+            raise ValueError(f"stage_precision={sp!r}: only 'fp32' (the pair mode for this stage alone) is supported")
+        fmt = "bf16" if self._stage_precision is not None else self._engine.weight_fmt
+        self._engine.load_weights(L.PT_MODEL_DOCX_DLA34, pack_docxlayout_dla34(sd, x3=True, fmt=fmt))
+        self._exec = None
+        self._model = self._predict
+
     def _construct_model(self, model):
         if self._engine is None:
             self._engine = self._new_engine()
+        if model == "DocXLayout":
+            return self._construct_docxlayout()
         ncls = len(self._config.labels)
         self._exec = None
         onnx_path = self._onnx_file()
@@ -90,6 +124,11 @@ class OcrLayoutTask(BaseInferTask):
         self._model = self._predict
 
     def _build_processor(self):
+        if self.model == "DocXLayout":
+            from .docxlayout_stage import DocXLayoutStage
+            # images reach the stage as RGB (files are read as RGB, arrays are taken as RGB: the CenterNet task's convention); the network eats BGR
+            self._stage = DocXLayoutStage(self._engine, self._config, bgr=True, precision=getattr(self, "_stage_precision", None))
+            return
         if getattr(self, "_exec", None) is not None:
             # the graph file behind LayoutStage's contract: forward() / finish() halves, candidate compaction on the device (pt_op_pico_candidates)
             self._stage = OnnxLayoutStage(self._engine, self._exec, self._config, device_decode=self._device_decode)

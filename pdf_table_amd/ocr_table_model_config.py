@@ -127,4 +127,5 @@ TABLE_MODEL_DICT = {"model_scope": _model_scope(), "PaddleOCR": _paddle(), "Othe
 HIP_SUPPORTED = {
     ("model_scope", "detection", "resnet18"): "PT_MODEL_DB_RESNET18",
     ("model_scope", "recognition", "CRNN"): "PT_MODEL_CRNN",
+    ("model_scope", "layout", "DocXLayout"): "PT_MODEL_DOCX_DLA34",
 }

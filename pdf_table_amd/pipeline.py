@@ -65,7 +65,12 @@ class OcrTablePipeline:
     """``layout=True, layout_task_path=<dir with model.onnx>`` serves that PicoDet export in ``predict()`` and in ``predict_stream()`` (main
     stream, ``aux_layout=True``, the second layout pass of ``orientation_vote=True``) through ``OnnxLayoutStage``; ``synthetic_seed`` is then
     not handed to the layout task (the file is served beside seeded stages), and ``layout_precision`` has no effect: the ONNX executor
-    computes in the engine's arithmetic (``precision``).  Without a graph file the in-tree LCNet graph runs as ``LayoutStage``."""
+    computes in the engine's arithmetic (``precision``).  Without a graph file the in-tree LCNet graph runs as ``LayoutStage``.
+
+    ``layout=True, layout_model="DocXLayout", layout_task_path=<checkpoint file or directory>`` serves that DocXLayout checkpoint through
+    ``DocXLayoutStage`` (same ``forward`` / ``finish`` contract, so ``predict()`` and ``predict_stream()`` treat it like the other two); the
+    model has no seeded weights, so the path is required (``ValueError`` before an engine exists) and the seed is not handed to the layout
+    task.  ``layout_precision`` and ``layout_device_decode`` are PicoDet's knobs and raise ``ValueError`` for this model."""
 
     def __init__(self, device: int = 0, detect_model: str = "db", recognizer: str = "CRNN", thresh: float = 0.2,
                  synthetic_seed: Optional[int] = None, det_task_path: Optional[str] = None,
@@ -83,6 +88,16 @@ class OcrTablePipeline:
         if layout_device_decode and not layout:
             raise ValueError("layout_device_decode=True decodes the layout stage's candidates on the device (pt_op_layout_decode); layout=False builds no "
                              "layout stage")
+        if layout and layout_model == "DocXLayout":
+            # no in-tree (seeded) weights for this model either: refused here, before any engine exists
+            if not layout_task_path:
+                raise ValueError("layout_model='DocXLayout' without layout_task_path=<checkpoint file or directory holding pytorch_model.bin> is out of "
+                                 "scope for OcrTablePipeline: there are no seeded weights for it")
+            if layout_precision:
+                raise ValueError("layout_precision runs the PicoDet layout net alone in the pair mode; layout_model='DocXLayout' computes in the "
+                                 "pipeline's precision")
+            if layout_device_decode:
+                raise ValueError("layout_device_decode=True selects PicoDet's device decode; DocXLayout's decode always runs on the device")
         if table_structure_model == "SLANet" and not tsr_task_path:
             # the ONNX-only model has no in-tree (seeded) weights: without its directory there is nothing to serve.  Refused here, before any
             # engine exists, not on the first page
@@ -156,7 +171,8 @@ class OcrTablePipeline:
                 lk["synthetic_seed"] = synthetic_seed + 4
             if layout_task_path:
                 lk["task_path"] = layout_task_path
-                if onnx_file_under(layout_task_path):      # a graph file is served as it is (OnnxLayoutStage), beside seeded stages of the same pipeline
+                # a graph file is served as it is (OnnxLayoutStage), beside seeded stages of the same pipeline; so is a DocXLayout checkpoint
+                if onnx_file_under(layout_task_path) or layout_model == "DocXLayout":
                     lk.pop("synthetic_seed", None)
             if layout_precision:      # the layout net alone in the pair mode ("fp32"): exact table crops under a 16-bit engine (LayoutStage.precision)
                 # with an ONNX file under layout_task_path it has NO effect: the executor computes in the engine's arithmetic (``precision``)

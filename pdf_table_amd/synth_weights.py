@@ -20,7 +20,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-__all__ = ["db_resnet18_state_dict", "crnn_state_dict", "CRNN_NUM_CLASSES", "lore_dla34_state_dict", "centernet_dla34_state_dict", "CENTERNET_HEADS",
+__all__ = ["db_resnet18_state_dict", "crnn_state_dict", "CRNN_NUM_CLASSES", "lore_dla34_state_dict", "centernet_dla34_state_dict", "CENTERNET_HEADS", "docxlayout_dla34_state_dict", "DOCX_HEADS",
            "lore_processor_state_dict", "LORE_HEADS", "picodet_state_dict", "LCNET_CONFIG", "PICODET_STANDIN", "lore_wireless_state_dict", "db_nas_state_dict", "pplcnet_state_dict", "convnext_vit_state_dict", "mtl_tabnet_backbone_state_dict", "mtl_tabnet_decoder_state_dict"]
 
 CRNN_NUM_CLASSES = 7644  # crnn/modeling_crnn.py:90
@@ -607,6 +607,77 @@ def centernet_dla34_state_dict(seed: int = 0, hm_bias=(2.0, -12.0), hm_gain: flo
         else:
             g.conv(f"{h}.2", k, 256, 1, 1, bias=False, gain=0.02)
             g.put(f"{h}.2.bias", np.array([0.5, 0.5]))
+    return g.sd
+
+
+DOCX_HEADS = {"cls": 4, "ftype": 3, "hm": 11, "hm_sub": 2, "reg": 2, "reg_sub": 2, "wh": 8, "wh_sub": 8}      # docx_layout/configuration_docxlayout.py:45-46
+
+
+def docxlayout_dla34_state_dict(seed: int = 0, hm_bias: float = -3.2, hm_gain: float = 0.2, table_bias: float = 0.5, sub_bias: float = -1.9,
+                                half=(14.0, 9.0), sub_half=(60.0, 70.0), wh_gain: float = 0.0005):
+    """state_dict of DocXLayout's ``DLASeg('dla34', heads, down_ratio=4, head_conv=256)`` (docx_layout/model_dla.py:543-652): the ``dla34``
+    base of Lore and CenterNet (one generator, ``_dla34_base``), the plain ``DLAUp`` exactly as ``centernet_dla34_state_dict`` draws it, and the
+    eight heads of ``DOCX_HEADS``, each ``<head>.0`` (3x3, 64 -> 256, bias) and ``<head>.2`` (1x1, 256 -> k, bias).
+
+    A random net has no notion of a page, so the heads are conditioned on the CPU to give a page-like result at 768 x 768 on a synthetic page
+    (``synth_pages``): ``hm`` / ``hm_sub`` get zero-sum weights (the maps centre on their biases, as Lore's do) with a gain that leaves a handful
+    to a few dozen peaks above 0.3, class 7 ("table") ``table_bias`` above the others, the sub-field map on its own bias.  ``wh`` points from
+    the centre to the four corners (corner i = centre - wh[2i:2i+2]: top-left, top-right, bottom-right, bottom-left) at +-``half`` head-map
+    pixels (sub-fields: ``sub_half``), wide enough that neighbouring peaks nest and the polygon NMS has pairs to remove."""
+    g = _Gen(seed)
+    ch = DLA34_CHANNELS
+    _dla34_base(g)
+
+    def conv_bn(p, cout, cin, k):
+        g.conv(p + ".0", cout, cin, k, k)
+        g.bn(p + ".1", cout)
+
+    def ida(p, o, channels, up_f):
+        for i, c in enumerate(channels):
+            if c != o:
+                conv_bn(f"{p}.proj_{i}", o, c, 1)
+            if int(up_f[i]) != 1:
+                _bilinear_up(g, f"{p}.up_{i}", o, int(up_f[i]))
+        for i in range(1, len(channels)):
+            conv_bn(f"{p}.node_{i}", o, 2 * o, 3)
+
+    channels = ch[2:]
+    in_channels = list(channels)
+    scales = np.array([1, 2, 4, 8])
+    for i in range(len(channels) - 1):
+        j = -i - 2
+        ida(f"dla_up.ida_{i}", channels[j], in_channels[j:], scales[j:] // scales[j])
+        scales[j + 1:] = scales[j]
+        in_channels[j + 1:] = [channels[j] for _ in channels[j + 1:]]
+
+    def corners(hw, hh):
+        return np.array([hw, hh, -hw, hh, -hw, -hh, hw, -hh])
+
+    for h, k in DOCX_HEADS.items():
+        g.conv(f"{h}.0", 256, ch[2], 3, 3, bias=True)
+        if h in ("hm", "hm_sub"):
+            g.conv(f"{h}.2", k, 256, 1, 1, bias=False, gain=hm_gain)
+            # A map that centres on its bias whatever the seed: the hidden units come in pairs (filter f, weight w) and (-f, -w), so that
+            # w relu(f.x) - w relu(-f.x) = w f.x is linear in the feature patch, and every filter sums to zero over its nine taps, so that the
+            # (positive, slowly varying) features average out.  What is left responds to local structure: peaks sit on the page's content
+            f3 = g.sd[f"{h}.0.weight"]
+            f3[:128] -= f3[:128].mean(dim=(2, 3), keepdim=True)
+            f3[128:] = -f3[:128]
+            g.sd[f"{h}.0.bias"][:] = 0.0
+            w = g.sd[f"{h}.2.weight"]
+            w[:, 128:] = -w[:, :128]
+            b = np.full((k,), hm_bias if h == "hm" else sub_bias, dtype=np.float64)
+            if h == "hm":
+                b[7] += table_bias
+            g.put(f"{h}.2.bias", b)
+        elif h in ("wh", "wh_sub"):
+            g.conv(f"{h}.2", k, 256, 1, 1, bias=False, gain=wh_gain)
+            g.put(f"{h}.2.bias", corners(*(half if h == "wh" else sub_half)))
+        elif h in ("reg", "reg_sub"):
+            g.conv(f"{h}.2", k, 256, 1, 1, bias=False, gain=wh_gain * 0.01)
+            g.put(f"{h}.2.bias", np.array([0.5, 0.5]))
+        else:
+            g.conv(f"{h}.2", k, 256, 1, 1, bias=True, gain=0.5)
     return g.sd
 
 

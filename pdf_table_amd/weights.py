@@ -29,7 +29,7 @@ import torch
 BN_EPS = 1e-5
 _DT = {"bf16": 0, "f32": 1, "i32": 2}
 
-__all__ = ["pack_db_resnet18", "pack_crnn", "pack_lore_dla34", "pack_centernet_dla34", "pack_lore_processor", "pack_picodet", "pack_lore_wireless", "pack_db_nas", "pack_pplcnet", "pack_convnext_vit", "pack_cvit_mlp", "pack_mtl_backbone", "pack_mtl_decoder", "pack_sla_head", "write_blob", "fold_conv_bn", "to_bf16_bits"]
+__all__ = ["pack_db_resnet18", "pack_crnn", "pack_lore_dla34", "pack_centernet_dla34", "pack_docxlayout_dla34", "DOCX_HEADS", "pack_lore_processor", "pack_picodet", "pack_lore_wireless", "pack_db_nas", "pack_pplcnet", "pack_convnext_vit", "pack_cvit_mlp", "pack_mtl_backbone", "pack_mtl_decoder", "pack_sla_head", "write_blob", "fold_conv_bn", "to_bf16_bits"]
 
 
 FORMATS = {"bf16": torch.bfloat16, "f16": torch.float16}      # 16-bit storage formats of the engine (csrc/act16.h): PT_PRECISION_BF16* / PT_PRECISION_F16
@@ -473,6 +473,31 @@ def pack_lore_dla34(sd: Dict[str, torch.Tensor], x3: bool = True, fmt: str = "bf
     return bl.tobytes()
 
 
+def _pack_dla_up_plain(bl: "_Blob", sd: Dict[str, torch.Tensor], need) -> None:
+    """the plain DLAUp (IDAUp without DCN) CenterNet's and DocXLayout's DLASeg share: ``.proj_i`` 1x1 conv with its BN folded; ``.up_i`` the
+    depthwise ConvTranspose2d as fp32 ``[k*k][C]``; ``.node_i`` the 3x3 conv over the channel concat [running output, up-sampled layer] with its BN
+    folded (K order of that concat).  ``need(key)`` returns the key or raises, naming the model."""
+    for name, o, chans in (("dla_up.ida_0", 256, (256, 512)), ("dla_up.ida_1", 128, (128, 256, 256)),
+                           ("dla_up.ida_2", 64, (64, 128, 128, 128))):
+        for j in range(1, len(chans)):
+            if chans[j] != o:
+                bl.add_conv(f"{name}.proj_{j}", *fold_conv_bn(sd, need(f"{name}.proj_{j}.0.weight")[:-7], f"{name}.proj_{j}.1"))
+            wu = sd[need(f"{name}.up_{j}.weight")]                                # [C, 1, 4, 4]
+            k = wu.shape[2]
+            bl.add(f"{name}.up_{j}.wf32", wu[:, 0].permute(1, 2, 0).reshape(k * k, -1).contiguous().numpy().astype(np.float32), "f32")
+            bl.add_conv(f"{name}.node_{j}", *fold_conv_bn(sd, need(f"{name}.node_{j}.0.weight")[:-7], f"{name}.node_{j}.1"))
+
+
+def _pack_heads_256(bl: "_Blob", sd: Dict[str, torch.Tensor], need, heads) -> None:
+    """heads of a DLASeg with head_conv 256: 3x3 64 -> 256 + bias, then 1x1 -> k + bias padded to 64 outputs"""
+    for h, k in heads:
+        need(f"{h}.0.bias"), need(f"{h}.2.bias")          # the heads' convs have biases (modeling_centernet.py:622-640, model_dla.py:572-578)
+        bl.add_conv(f"{h}.0", *fold_conv_bn(sd, need(f"{h}.0.weight")[:-7], None))
+        w, b = fold_conv_bn(sd, need(f"{h}.2.weight")[:-7], None)
+        assert w.shape[0] == k, (h, tuple(w.shape), k)
+        bl.add_conv(f"{h}.2", *_pad_conv(w, b, 64, 256))
+
+
 def pack_centernet_dla34(sd: Dict[str, torch.Tensor], x3: bool = True, fmt: str = "bf16") -> bytes:
     """CenterNet's ``DLASeg`` state_dict (center_net/modeling_centernet.py:609-661; a ``recognizer.`` prefix, as in the reference's
     checkpoints, is stripped like modeling_table_structure.py:39 does) -> blob for PT_MODEL_CENTERNET_DLA34.
@@ -490,20 +515,32 @@ def pack_centernet_dla34(sd: Dict[str, torch.Tensor], x3: bool = True, fmt: str 
             raise KeyError(f"CenterNet DLA-34 state_dict lacks '{k}'")
         return k
 
-    for name, o, chans in (("dla_up.ida_0", 256, (256, 512)), ("dla_up.ida_1", 128, (128, 256, 256)),
-                           ("dla_up.ida_2", 64, (64, 128, 128, 128))):
-        for j in range(1, len(chans)):
-            if chans[j] != o:
-                bl.add_conv(f"{name}.proj_{j}", *fold_conv_bn(sd, need(f"{name}.proj_{j}.0.weight")[:-7], f"{name}.proj_{j}.1"))
-            wu = sd[need(f"{name}.up_{j}.weight")]                                # [C, 1, 4, 4]
-            k = wu.shape[2]
-            bl.add(f"{name}.up_{j}.wf32", wu[:, 0].permute(1, 2, 0).reshape(k * k, -1).contiguous().numpy().astype(np.float32), "f32")
-            bl.add_conv(f"{name}.node_{j}", *fold_conv_bn(sd, need(f"{name}.node_{j}.0.weight")[:-7], f"{name}.node_{j}.1"))
-    for h, k in (("hm", 2), ("v2c", 8), ("c2v", 8), ("reg", 2)):
-        need(f"{h}.0.bias"), need(f"{h}.2.bias")          # the heads' convs have biases (modeling_centernet.py:622-640)
-        bl.add_conv(f"{h}.0", *fold_conv_bn(sd, need(f"{h}.0.weight")[:-7], None))
-        w, b = fold_conv_bn(sd, need(f"{h}.2.weight")[:-7], None)
-        bl.add_conv(f"{h}.2", *_pad_conv(w, b, 64, 256))
+    _pack_dla_up_plain(bl, sd, need)
+    _pack_heads_256(bl, sd, need, (("hm", 2), ("v2c", 8), ("c2v", 8), ("reg", 2)))
+    return bl.tobytes()
+
+
+DOCX_HEADS = (("cls", 4), ("ftype", 3), ("hm", 11), ("hm_sub", 2), ("reg", 2), ("reg_sub", 2), ("wh", 8), ("wh_sub", 8))      # configuration_docxlayout.py:45-46
+
+
+def pack_docxlayout_dla34(sd: Dict[str, torch.Tensor], x3: bool = True, fmt: str = "bf16") -> bytes:
+    """DocXLayout's ``DLASeg('dla34', heads, down_ratio=4, head_conv=256)`` state_dict (docx_layout/model_dla.py:543-652; a leading ``module.``
+    is stripped) -> blob for PT_MODEL_DOCX_DLA34: the ``dla34`` base and the plain DLAUp exactly as pack_centernet_dla34 packs them, then the
+    eight heads cls / ftype / hm / hm_sub / reg / reg_sub / wh / wh_sub.  A state dict of another DLASeg (CenterNet's has no ``cls`` head) is
+    refused by the first key it lacks."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+
+    def need(k):
+        if k not in sd:
+            raise KeyError(f"DocXLayout DLA-34 state_dict lacks '{k}'")
+        return k
+
+    for h, _ in DOCX_HEADS:      # before anything is packed: the refusal names a head, not a tensor both models have
+        need(f"{h}.0.weight"), need(f"{h}.2.weight")
+    bl = _Blob(x3, fmt)
+    _pack_dla34_base(bl, sd)
+    _pack_dla_up_plain(bl, sd, need)
+    _pack_heads_256(bl, sd, need, DOCX_HEADS)
     return bl.tobytes()
 
 
