@@ -790,6 +790,33 @@ int pt_op_layout_decode(const int32_t* d_counts, const float* d_cands, int B, in
                         int inp_w, int org_h, int org_w, int probs, float score_threshold, double nms_threshold, int nms_top_k, int candidate_size,
                         int keep_top_k, int max_dets, int32_t* d_ndet, double* d_dets, pt_stream stream);
 
+/* The TEDS table metric's two hot parts (csrc/teds.hip, compiled once, engine-free; added under ABI 21: new entry points, no existing signature
+ * changed, so the version stays).  pdf_table_amd/table_metric.py packs these arrays and states the same arithmetic on the host.
+ * pt_op_teds_cost: C = levenshtein(a, b) / max(len a, len b) in float64 (0 where both are empty) for every (row content, column content) of P table
+ *   pairs.  d_tok int32 [n_tok]: token ids, compared as whole int32 values; d_coff / h_coff int32 [n_cont + 1]: content k owns tokens coff[k] ..
+ *   coff[k + 1] - 1 (from 0, non-decreasing, at most 1024 tokens per content); d_pairs / h_pairs int64 [P, 5] = (first row content, row contents nr,
+ *   first column content, column contents nc, offset of the pair's nr x nc row-major matrix in d_C, in elements); the two ranges may overlap, and a
+ *   content against itself is 0 without a token read.  d_C fp64 [c_elems].  The h_ arrays are the HOST copies of the d_ arrays: every limit is checked
+ *   on them, and anything outside (a content above 1024 tokens among them) is PT_ERR_INVALID with a message, nothing launched, nothing written.
+ *   The quotient is one division of two exact integers.  0 <= P <= 65535.  One launch, no allocation, no host synchronisation (capturable).
+ * pt_op_teds_dist: d_out fp64 [P] = the ordered tree edit distance (insert = delete = 1) of each pair, one workgroup per pair.  Trees are flattened in
+ *   postorder.  d_node int32 [n_nodes, 4] = (tag id, colspan, rowspan, content id; spans -1 and content id -1 where the node carries none), 16-byte
+ *   aligned; d_lml int32 [n_nodes]: the node's leftmost leaf, as an index inside its tree; d_kr int32 [n_kr]: per tree its keyroots, ordered by
+ *   (height, size descending); d_grp int32 [n_grp]: per tree ngrp + 1 offsets into its keyroot list, one group per height that has a keyroot.
+ *   d_pairs / h_pairs int64 [P, 16] = (n1, first node of tree 1, n2, first node of tree 2, first keyroot 1, keyroots 1, first group offset 1, groups
+ *   1, the same four of tree 2, offset of the pair's cost matrix in d_C, its rows, its columns, offset of the pair's scratch in doubles).  Renaming
+ *   node i into node j costs 1 where tag, colspan or rowspan differ, else C[content i, content j] where both carry a content, else 0.  1 <= n <=
+ *   4096 per tree; a pair's scratch is pt_op_teds_scratch_bytes(n1, n2) bytes (two n1 x n2 fp64 planes), the pairs' regions ascending and disjoint.
+ *   Checked on the host copies: anything outside (4097 nodes, a scratch too small) is PT_ERR_INVALID with a message, nothing launched.  The kernel
+ *   clamps every index it reads from device memory all the same.  No atomics, no state shared between workgroups.  One launch, no allocation, no host
+ *   synchronisation (capturable). */
+int pt_op_teds_scratch_bytes(int n1, int n2, long long* bytes);
+int pt_op_teds_cost(const int32_t* d_tok, long long n_tok, const int32_t* d_coff, const int32_t* h_coff, int n_cont, const int64_t* d_pairs,
+                    const int64_t* h_pairs, int P, double* d_C, long long c_elems, pt_stream stream);
+int pt_op_teds_dist(const int64_t* d_pairs, const int64_t* h_pairs, int P, const int32_t* d_node, const int32_t* d_lml, long long n_nodes,
+                    const int32_t* d_kr, long long n_kr, const int32_t* d_grp, long long n_grp, const double* d_C, long long c_elems, double* d_scratch,
+                    long long scratch_bytes, double* d_out, pt_stream stream);
+
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------
  * Replaces ClsImagePulcTask._preprocess/_run_model (ocr_pdf/cls_image_pulc_task.py:48-84): PPLCNetImageProcessor

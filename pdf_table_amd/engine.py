@@ -48,6 +48,14 @@ def mtl_pick_split(ntiles: int, hw: int) -> Tuple[int, int]:
     return ns.value, kps.value
 
 
+def teds_scratch_bytes(n1: int, n2: int) -> int:
+    """pt_op_teds_scratch_bytes: the scratch pt_op_teds_dist needs for one pair of trees with n1 and n2 nodes (1 .. 4096 each).  Host arithmetic of the
+    library: needs no device and no engine."""
+    n = C.c_longlong()
+    L.check(L.load().pt_op_teds_scratch_bytes(int(n1), int(n2), C.byref(n)), "pt_op_teds_scratch_bytes")
+    return int(n.value)
+
+
 class HipEngine:
     def __init__(self, device: int = 0):
         self.lib = L.load()
@@ -1351,6 +1359,68 @@ class HipEngine:
         out = torch.empty((M,), dtype=torch.int32, device=self._tdev)
         L.check(self.lib.pt_op_lore_match(_ptr(dets), _ptr(axes), _ptr(counts), B, _ptr(affine), _ptr(offset), _ptr(lines), _ptr(offsets), M,
                                           _ptr(out), self._stream()), "pt_op_lore_match")
+        return out
+
+    # ---- the TEDS table metric's kernels (csrc/teds.hip, engine-free; pdf_table_amd/table_metric.py packs their arrays) ----
+    def op_teds_cost(self, tok: torch.Tensor, coff: torch.Tensor, pairs: torch.Tensor, h_coff, h_pairs, out: Optional[torch.Tensor] = None,
+                     c_elems: Optional[int] = None) -> torch.Tensor:
+        """Cell contents -> rename costs, in one launch (pt_op_teds_cost): levenshtein / max(len) in float64 for every (row content, column content)
+        of every table pair.  tok int32 [n_tok] token ids; coff int32 [n_cont + 1] CSR offsets of the contents (at most 1024 tokens each); pairs int64
+        [P, 5] = (first row content, rows, first column content, columns, offset in `out`); h_coff / h_pairs: the same two arrays as numpy arrays on
+        the host, which every limit is checked on (PtError, nothing launched, where one is broken).  out float64 [>= c_elems] (default: allocated to
+        fit) receives each pair's rows x columns matrix; c_elems: how much of `out` the call may write (default: all of it)."""
+        import numpy as np
+        self._chk(tok, torch.int32, "tok")
+        self._chk(coff, torch.int32, "coff")
+        self._chk(pairs, torch.int64, "pairs")
+        h_coff = np.ascontiguousarray(h_coff, dtype=np.int32)
+        h_pairs = np.ascontiguousarray(h_pairs, dtype=np.int64).reshape(-1, 5)
+        P = h_pairs.shape[0]
+        if pairs.numel() != 5 * P or coff.numel() != h_coff.size or h_coff.size < 1:
+            raise ValueError(f"op_teds_cost: the host copies do not fit the device arrays: pairs {tuple(pairs.shape)} / {h_pairs.shape}, coff "
+                             f"{tuple(coff.shape)} / {h_coff.shape}")
+        if out is None:
+            need = int((h_pairs[:, 4] + h_pairs[:, 1] * h_pairs[:, 3]).max()) if P else 0
+            out = torch.empty((max(need, 1),), dtype=torch.float64, device=self._tdev)
+        self._chk(out, torch.float64, "out")
+        c_elems = out.numel() if c_elems is None else int(c_elems)
+        if c_elems > out.numel():
+            raise ValueError(f"op_teds_cost: c_elems {c_elems} above the {out.numel()} elements of out")
+        L.check(self.lib.pt_op_teds_cost(_ptr(tok), tok.numel(), _ptr(coff), C.c_void_p(h_coff.ctypes.data), h_coff.size - 1, _ptr(pairs),
+                                         C.c_void_p(h_pairs.ctypes.data), P, _ptr(out), c_elems, self._stream()), "pt_op_teds_cost")
+        return out
+
+    def op_teds_dist(self, pairs: torch.Tensor, h_pairs, node: torch.Tensor, lml: torch.Tensor, kr: torch.Tensor, grp: torch.Tensor,
+                     costs: torch.Tensor, scratch: torch.Tensor, out: Optional[torch.Tensor] = None, c_elems: Optional[int] = None,
+                     scratch_bytes: Optional[int] = None) -> torch.Tensor:
+        """Flattened table trees -> ordered tree edit distances (insert = delete = 1), one workgroup per table pair in one launch (pt_op_teds_dist).
+        pairs int64 [P, 16] and its host copy h_pairs (numpy), node int32 [n_nodes, 4], lml int32 [n_nodes], kr int32 [n_kr], grp int32 [n_grp],
+        costs float64 (op_teds_cost's output): see include/pdftable_hip.h.  scratch: uint8 or float64 device buffer, table_metric.scratch_bytes(n1, n2)
+        bytes per pair at the pairs' own offsets.  -> float64 [>= P] (`out`, or a new tensor): the distances.  A tree above 4096 nodes or a scratch too
+        small is refused (PtError) and nothing is launched."""
+        import numpy as np
+        self._chk(pairs, torch.int64, "pairs")
+        for t, n in ((node, "node"), (lml, "lml"), (kr, "kr"), (grp, "grp")):
+            self._chk(t, torch.int32, n)
+        self._chk(costs, torch.float64, "costs")
+        self._chk(scratch, torch.float64 if scratch.dtype == torch.float64 else torch.uint8, "scratch")
+        h_pairs = np.ascontiguousarray(h_pairs, dtype=np.int64).reshape(-1, 16)
+        P = h_pairs.shape[0]
+        if pairs.numel() != 16 * P or node.numel() != 4 * lml.numel():
+            raise ValueError(f"op_teds_dist: pairs {tuple(pairs.shape)} / host {h_pairs.shape}, node {tuple(node.shape)}, lml {tuple(lml.shape)} do not fit")
+        if out is None:
+            out = torch.empty((max(P, 1),), dtype=torch.float64, device=self._tdev)
+        self._chk(out, torch.float64, "out")
+        if out.numel() < P:
+            raise ValueError(f"op_teds_dist: out holds {out.numel()} distances, {P} pairs")
+        c_elems = costs.numel() if c_elems is None else int(c_elems)
+        have = scratch.numel() * scratch.element_size()
+        scratch_bytes = have if scratch_bytes is None else int(scratch_bytes)
+        if c_elems > costs.numel() or scratch_bytes > have:
+            raise ValueError("op_teds_dist: c_elems / scratch_bytes above the buffers' sizes")
+        L.check(self.lib.pt_op_teds_dist(_ptr(pairs), C.c_void_p(h_pairs.ctypes.data), P, _ptr(node), _ptr(lml), lml.numel(), _ptr(kr), kr.numel(),
+                                         _ptr(grp), grp.numel(), _ptr(costs), c_elems, _ptr(scratch), scratch_bytes, _ptr(out), self._stream()),
+                "pt_op_teds_dist")
         return out
 
     def op_attention(self, qkv: torch.Tensor, heads: int, d: int, scale: float, out_c: int, split: bool = False) -> torch.Tensor:

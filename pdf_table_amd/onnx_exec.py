@@ -58,6 +58,8 @@ from __future__ import annotations
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence
 
+import contextlib
+import gc
 import os
 import threading
 
@@ -149,6 +151,23 @@ def lstm_gemm_operands(W: np.ndarray, Bv: Optional[np.ndarray], cin_pad: int):
 
 
 _CAPTURE_LOCK = threading.Lock()      # graph capture is serialised across executors and host threads (see HipGraphExecutor._graphed)
+
+
+@contextlib.contextmanager
+def _garbage_collected_first():
+    """Around a stream capture: collect cyclic garbage BEFORE it begins and keep the collector off until it has ended.  torch.cuda.graph() no longer
+    collects on entry (current torch does so only with torch.compiler.config.force_cudagraph_gc), so an automatic collection could otherwise land
+    inside the capture and run the finaliser of a dead engine, pipeline or captured graph of an earlier use there (HipEngine.__del__ ->
+    pt_engine_destroy: hipDeviceSynchronize, hipFree) -- calls a capturing thread must not make; where in the walk the collector fires depends on
+    the process's allocation count, not on the graph.  gc.disable() is process-wide, so other host threads' allocations cannot start one either."""
+    was_on = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 class HipGraphExecutor:
@@ -782,7 +801,8 @@ class HipGraphExecutor:
         Only CAPTURED graphs count against MAX_GRAPHS, and the least recently used one is dropped for a new shape -- a dynamic-shape detector does not
         run eagerly for the rest of the process after its first eight page sizes.  Capture is serialised (one lock for all executors:
         capture is a property of the device's allocator) in thread-local capture mode, so allocations of other host threads (the pipeline's
-        enqueue / collect threads) do not invalidate it; a capture that raises anyway falls back to the eager walk for that shape."""
+        enqueue / collect threads) do not invalidate it, and with the garbage collector held off (_garbage_collected_first); a capture that raises anyway
+        falls back to the eager walk for that shape."""
         if os.environ.get("PT_ONNX_GRAPH", "1") == "0":
             return walk(nhwc)
         ent = self._graphs.get(key)
@@ -796,7 +816,7 @@ class HipGraphExecutor:
             static_in = nhwc.clone()
             g = torch.cuda.CUDAGraph()
             try:
-                with _CAPTURE_LOCK:
+                with _CAPTURE_LOCK, _garbage_collected_first():
                     with torch.cuda.graph(g, capture_error_mode="thread_local"):
                         outs = walk(static_in)
             except Exception:      # noqa: BLE001 -- the capture is an optimisation: the eager walk is always available
