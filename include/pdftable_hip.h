@@ -817,6 +817,28 @@ int pt_op_teds_dist(const int64_t* d_pairs, const int64_t* h_pairs, int P, const
                     const int32_t* d_kr, long long n_kr, const int32_t* d_grp, long long n_grp, const double* d_C, long long c_elems, double* d_scratch,
                     long long scratch_bytes, double* d_out, pt_stream stream);
 
+/* The WTW cell metric's matching (csrc/cell_metric.hip, compiled once, engine-free; added under ABI 21: a new entry point, no existing signature
+ * changed, so the version stays): TableEval.bubble_sort + PairTable.matching / eval_axis (utils/eval/eval_utils.py:23-113,
+ * entity/table_entity.py:630-656) for P (prediction, truth) table pairs in one launch, one workgroup per pair.  pdf_table_amd/cell_metric.py packs
+ * these arrays and states the same rule on the host.
+ *   d_boxes fp64 [N, 4] = (x1, y1, x3, y3) of every cell of every table of the chunk (points 1 and 3 of the quad: the only ones compute_iou reads),
+ *   16-byte aligned, finite; d_axes int32 [N, 4] = the cell's logical axes as the files list them, 16-byte aligned.
+ *   d_pairs / h_pairs int64 [P, 4] = (first prediction cell, prediction cells, first truth cell, truth cells); the ranges may overlap.
+ *   d_moff / h_moff int64 [P]: where the pair's matches start in d_match, ascending and disjoint (the prefix sum of the truth counts, or wider).
+ *   d_match int32 [match_elems]: per truth cell, in the truth's input order, the input index (inside its table) of the FIRST prediction cell with
+ *   iou >= iou_threshold, or -1 -- first in the order a stable sort of the predictions by (axis[2], axis[0], axis[3], axis[1]) leaves, never the best
+ *   IoU; a prediction may serve several truth cells.  d_counts int32 [P, 2] = (matches, matches whose four axes equal the truth cell's).
+ *   IoU in float64, the reference's operations in its order: 0 where max(x1) >= min(x3) or min(y3) <= max(y1), else Sx / ((S1 + S2) - Sx).
+ * The h_ arrays are the HOST copies of the d_ arrays; every limit is checked on them: a count outside 0 .. PT_CELL_METRIC_MAX, a range outside
+ * [0, N], matches outside d_match or a threshold that is not positive is PT_ERR_INVALID with a message, nothing launched, nothing written.  The kernel
+ * clamps every index it reads from device memory all the same.  A pair with no truth cell writes its counts only; one with no prediction cell writes
+ * -1.  P == 0 launches nothing.  0 <= P <= 65535.  No scratch, no atomics, no state shared between workgroups.  One launch, no allocation, no host
+ * synchronisation (capturable). */
+#define PT_CELL_METRIC_MAX 4096
+int pt_op_cell_metric(const double* d_boxes, const int32_t* d_axes, long long N, const int64_t* d_pairs, const int64_t* h_pairs, int P,
+                      const int64_t* d_moff, const int64_t* h_moff, double iou_threshold, int32_t* d_match, long long match_elems, int32_t* d_counts,
+                      pt_stream stream);
+
 /* ---- introspection used by bench.py (HIP-event timing of the dominant kernel) ------------------ */
 /* ---- image classification (PP-LCNet) ------------------------------------------------------------
  * Replaces ClsImagePulcTask._preprocess/_run_model (ocr_pdf/cls_image_pulc_task.py:48-84): PPLCNetImageProcessor

@@ -1423,6 +1423,51 @@ class HipEngine:
                 "pt_op_teds_dist")
         return out
 
+    # ---- the WTW cell metric's matching (csrc/cell_metric.hip, engine-free; pdf_table_amd/cell_metric.py packs its arrays) ----
+    def op_cell_metric(self, boxes: torch.Tensor, axes: torch.Tensor, pairs: torch.Tensor, h_pairs, iou_threshold: float = 0.5,
+                       moff: Optional[torch.Tensor] = None, h_moff=None, match: Optional[torch.Tensor] = None,
+                       counts: Optional[torch.Tensor] = None, match_elems: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Cells of (prediction, truth) table pairs -> per truth cell the first prediction cell at iou >= iou_threshold, one workgroup per pair in
+        one launch (pt_op_cell_metric).  boxes float64 [N, 4] = (x1, y1, x3, y3), axes int32 [N, 4], pairs int64 [P, 4] = (first prediction cell,
+        prediction cells, first truth cell, truth cells) and its host copy h_pairs (numpy), which every limit is checked on (PtError, nothing
+        launched, where one is broken: more than 4096 cells, a range outside N).  moff int64 [P] / h_moff: where each pair's matches start in
+        `match` (default: the prefix sum of the truth counts, uploaded here; pass both to stay free of allocation and upload).  -> (match int32
+        [>= match_elems]: input index of the prediction cell inside its table or -1, truth cells in input order; counts int32 [P, 2] = (matches,
+        matches with four equal axes)); `match` / `counts`: buffers to write into, match_elems: how much of `match` the call may write."""
+        import numpy as np
+        self._chk(boxes, torch.float64, "boxes")
+        self._chk(axes, torch.int32, "axes")
+        self._chk(pairs, torch.int64, "pairs")
+        h_pairs = np.ascontiguousarray(h_pairs, dtype=np.int64).reshape(-1, 4)
+        P = h_pairs.shape[0]
+        N = boxes.numel() // 4
+        if pairs.numel() != 4 * P or boxes.numel() != 4 * N or axes.numel() != 4 * N:
+            raise ValueError(f"op_cell_metric: pairs {tuple(pairs.shape)} / host {h_pairs.shape}, boxes {tuple(boxes.shape)}, axes {tuple(axes.shape)} do not fit")
+        if (moff is None) != (h_moff is None):
+            raise ValueError("op_cell_metric: moff and h_moff go together")
+        if h_moff is None:
+            h_moff = np.concatenate([[0], np.cumsum(np.clip(h_pairs[:, 3], 0, None))[:-1]]).astype(np.int64) if P else np.zeros(0, np.int64)
+            moff = torch.from_numpy(h_moff).to(self._tdev)
+        h_moff = np.ascontiguousarray(h_moff, dtype=np.int64).reshape(-1)
+        self._chk(moff, torch.int64, "moff")
+        if moff.numel() != P or h_moff.size != P:
+            raise ValueError(f"op_cell_metric: {P} pairs, moff {tuple(moff.shape)} / host {h_moff.shape}")
+        if match is None:
+            need = int((h_moff + np.clip(h_pairs[:, 3], 0, None)).max()) if P else 0
+            match = torch.empty((max(need, 1),), dtype=torch.int32, device=self._tdev)
+        if counts is None:
+            counts = torch.empty((max(P, 1), 2), dtype=torch.int32, device=self._tdev)
+        self._chk(match, torch.int32, "match")
+        self._chk(counts, torch.int32, "counts")
+        match_elems = match.numel() if match_elems is None else int(match_elems)
+        if match_elems > match.numel() or counts.numel() < 2 * P:
+            raise ValueError(f"op_cell_metric: match_elems {match_elems} above the {match.numel()} elements of match, or counts {tuple(counts.shape)} "
+                             f"below {P} pairs")
+        L.check(self.lib.pt_op_cell_metric(_ptr(boxes), _ptr(axes), N, _ptr(pairs), C.c_void_p(h_pairs.ctypes.data), P, _ptr(moff),
+                                           C.c_void_p(h_moff.ctypes.data), float(iou_threshold), _ptr(match), match_elems, _ptr(counts),
+                                           self._stream()), "pt_op_cell_metric")
+        return match, counts
+
     def op_attention(self, qkv: torch.Tensor, heads: int, d: int, scale: float, out_c: int, split: bool = False) -> torch.Tensor:
         """qkv bf16 [B, 1, T, >= 3 heads d] rows of [q | k | v] -> bf16 [B, 1, T, out_c] (channels heads * d .. out_c are zero); split: both tensors
         carry [hi | lo] halves of that width"""
