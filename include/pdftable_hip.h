@@ -789,6 +789,26 @@ int pt_op_lore_match(const float* d_dets, const float* d_axes, const int32_t* d_
 int pt_op_layout_decode(const int32_t* d_counts, const float* d_cands, int B, int max_cands, int ncls, int levels, const int32_t* h_strides, int inp_h,
                         int inp_w, int org_h, int org_w, int probs, float score_threshold, double nms_threshold, int nms_top_k, int candidate_size,
                         int keep_top_k, int max_dets, int32_t* d_ndet, double* d_dets, pt_stream stream);
+/* DocXLayout's region list and reading order behind pt_docx_decode (csrc/docx_order.hip, compiled once, engine-free; added under ABI 21: one new entry
+ * point, no existing signature changed, so the version stays): docx_page_result (pdf_table_amd/docxlayout_stage.py) on the device, step for step.
+ * d_counts int32 [B][2], d_recs fp32 [B][2][K][PT_DOCX_REC_FLOATS], d_keep uint8 [B][2][K] as pt_docx_decode writes them (a count outside [0, K] is
+ * clamped; use_nms 0: every row below the count is read, whatever its keep flag).  a00 .. a12: the float64 map from head-map to page pixels
+ * (centernet_decode_affine), applied as (a x + b y) + c and stored as float32.  Rows of a class with float32 score > scores_thresh, one zero placeholder
+ * per empty class, sub-branch classes shifted by n_main; above top_k rows the (rows - top_k)-th smallest score is the cut and ties at it stay;
+ * vertices through rintf; every region (class < n_main) goes to the sub-field (class >= n_main) that covers most of it when that is more than a
+ * tenth (float64 convex clipping in the host's operation order: the rate is the host's bit for bit), and fields, regions in a field and regions
+ * outside all fields are put in order by CPython's list.sort for fewer than 64 elements, replayed on the bits of the comparator's `<`.
+ *   d_nout int32 [B]          regions of the page (0 when flagged)
+ *   d_flag int32 [B]          0: served.  1: the page needs the host route -- a list of 64 or more blocks in one of the sorts, scores_thresh <= 0, a vertex
+ *                             that is not finite, or a comparison in which the host divides by zero
+ *   d_rows fp32 [B][2 K][6]   (x0, y0, x2, y2 of the rounded vertices, the float32 score, the 0-based class) in reading order; rows at and behind
+ *                             d_nout are not written
+ * atan2 / sin / cos of a list's main angle are the device library's: exact for an axis-aligned list (angle 0), last-bit differences from the host's
+ * libm otherwise.  PT_ERR_INVALID with a message and nothing launched: K > PT_DOCX_MAX_K, num_classes > 16, n_main >= num_classes, B < 1 (or any of them
+ * below its lower bound, top_k < 1).  One launch of one workgroup per page, 32 KB of LDS at most, no allocation, no host synchronisation (capturable). */
+int pt_op_docx_order(const int32_t* d_counts, const float* d_recs, const uint8_t* d_keep, int B, int K, double a00, double a01, double a02, double a10,
+                     double a11, double a12, float scores_thresh, int top_k, int num_classes, int n_main, int use_nms, int32_t* d_nout, int32_t* d_flag,
+                     float* d_rows, pt_stream stream);
 
 /* The TEDS table metric's two hot parts (csrc/teds.hip, compiled once, engine-free; added under ABI 21: new entry points, no existing signature
  * changed, so the version stays).  pdf_table_amd/table_metric.py packs these arrays and states the same arithmetic on the host.

@@ -6,7 +6,8 @@ Replaces, for a batch of equally sized resident pages, the reference's per-page 
 ``DocXLayoutImagePostProcessor.post_process`` (:223-459).  The device half ends in ``pt_docx_decode``: per page and branch (main: 11
 classes, sub-fields: 2) the first ``top_k`` peaks at or above a threshold just below ``scores_thresh`` in (score, index) order, their quads
 in head-map pixels, the ``cls`` / ``ftype`` arg-max columns and the keep flags of ``pnms``.  The host half maps the kept quads to page
-pixels, applies the reference's exact threshold rules, and orders the regions with its comparator sort.
+pixels, applies the reference's exact threshold rules, and orders the regions with its comparator sort.  ``DocXLayoutStage(device_order=True)``
+moves that half into one more launch (``pt_op_docx_order``, csrc/docx_order.hip); the host code here stays its specification and its fallback.
 
 Deviations, both in code the reference cannot run here (``shapely`` is not installed) or would raise in:
   * ``quad_intersection_rate`` restates ``pts_intersection_rate`` for convex quads (Sutherland-Hodgman clipping, shoelace areas, float64).
@@ -324,10 +325,19 @@ class DocXLayoutStage(LayoutStage):
     """``LayoutStage``'s contract -- ``forward(pages, landing=None) -> (n, ticket)``, ``finish(n, ticket, org)``, ``__call__`` -- for DocXLayout, so that
     ``OcrTablePipeline.predict_stream()`` pipelines it like PicoDet.  forward(): per micro-batch of pages the warp (``pt_docx_preprocess``: the whole
     page is the crop) and the network (``pt_docx_forward_net``) into one set of head maps, then ONE ``pt_docx_decode`` launch for the batch; counts,
-    records and keep flags (about 10 KB a page) land through the parent's alternating pinned buffers.  No host synchronisation of its own."""
+    records and keep flags (about 10 KB a page) land through the parent's alternating pinned buffers.  No host synchronisation of its own.
+
+    ``device_order=True`` (off by default): forward() queues one ``pt_op_docx_order`` launch (csrc/docx_order.hip: docx_page_result on the device,
+    a workgroup per page) behind the decode on the same stream and lands its (n_out, flag, rows) together with the three tensors above (about
+    16 KB a page); finish() only builds the dicts from the rows.  A page the kernel flags (a list of 64 or more blocks in one of the sorts) goes
+    through docx_page_result on its landed records as without the knob; ``last_fallback`` lists the pages of the last finish() that did.  Integers,
+    labels and scores equal the host route's for an axis-aligned page with no condition; for turned quads the main angle's atan2 / sin / cos are
+    the device library's (tests/docx_order_ref.py states the stability rule the tests use)."""
 
     def __init__(self, eng: HipEngine, config: Optional[DocXLayoutConfig] = None, micro_batch: Optional[int] = None, bgr: bool = True,
-                 precision: Optional[int] = None):
+                 precision: Optional[int] = None, device_order: bool = False):
+        self.device_order = bool(device_order)
+        self.last_fallback: List[int] = []
         self.eng = eng
         self.precision = precision
         self.config = config or DocXLayoutConfig()
@@ -360,23 +370,64 @@ class DocXLayoutStage(LayoutStage):
                 self.eng.docx_forward_net(x, out={k: v[i:i + self.micro_batch] for k, v in heads.items()})
             counts, recs, _, keep = self.eng.docx_decode(heads, top_k=cfg.top_k, thr_lo=cfg.scores_thresh - 1e-3, ncls_main=N_MAIN,
                                                          ncls_sub=cfg.num_classes - N_MAIN, with_inds=False)
+            if self.device_order:
+                return self._land_tensors((counts, recs, keep) + self._order_launch(counts, recs, keep, (ph, pw)), landing)
         return self._land_tensors((counts, recs, keep), landing)
+
+    def _order_launch(self, counts: torch.Tensor, recs: torch.Tensor, keep: torch.Tensor, page_hw):
+        """one pt_op_docx_order launch on the current stream behind whatever wrote the records -> (n_out, flag, rows) on the device"""
+        cfg = self.config
+        inp_h, inp_w = cfg.resolution
+        inv = centernet_decode_affine(int(page_hw[0]), int(page_hw[1]), inp_h // 4, inp_w // 4)
+        return self.eng.op_docx_order(counts, recs, keep, inv, scores_thresh=cfg.scores_thresh, top_k=cfg.top_k, num_classes=cfg.num_classes,
+                                      n_main=N_MAIN, use_nms=cfg.use_nms)
+
+    def order_records(self, counts, recs, keep, page_hw) -> List[List[Dict]]:
+        """the device half of ``device_order=True`` on given records (counts int32 [B,2], recs float32 [B,2,K,12], keep uint8 [B,2,K]; tensors or
+        arrays) of pages of ``page_hw`` pixels: the launch, a blocking copy, the dict lists -- flagged pages through the host route, as finish()
+        does (``last_fallback``).  For records that come from no network."""
+        dev = self.eng._tdev
+        c, r, k = (torch.as_tensor(np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v).to(dev).contiguous() for v in (counts, recs, keep))
+        host = tuple(t.cpu() for t in (c, r, k) + self._order_launch(c, r, k, page_hw))
+        return self._finish_ordered(c.shape[0], host, page_hw)
+
+    def _page_host(self, counts, recs, keep, i: int, org) -> List[Dict]:
+        """page i's landed records -> docx_page_result on the kept rows of both lists"""
+        inp_h, inp_w = self.config.resolution
+        rows = []
+        for b in range(2):
+            m = int(counts[i, b])
+            r = recs[i, b, :m]
+            rows.append(r[keep[i, b, :m] != 0] if self.config.use_nms else r)
+        return docx_page_result(rows[0], rows[1], (int(org[0]), int(org[1])), (inp_h // 4, inp_w // 4), self.config)
+
+    def _finish_ordered(self, n: int, host, org) -> List[List[Dict]]:
+        """device_order=True: the landed (counts, recs, keep, n_out, flag, rows) -> the dict lists; only the two-decimal score is computed here"""
+        cfg = self.config
+        counts, recs, keep, n_out, flag, rows = (h[:n].numpy() for h in host)
+        self.last_fallback = [i for i in range(n) if flag[i] != 0]
+        out = []
+        for i in range(n):
+            if flag[i] != 0:
+                out.append(self._page_host(counts, recs, keep, i, org))
+                continue
+            m = int(n_out[i])
+            box = rows[i, :m, :4].astype(np.float64)
+            page = []
+            for k in range(m):
+                label = cfg.id2label[int(rows[i, k, 5])]
+                page.append({"bbox": box[k].copy(), "label": label, "score": float("{:.2f}".format(rows[i, k, 4])), "category_id": cfg.label2id[label]})
+            out.append(page)
+        return out
 
     def finish(self, n: int, ticket, org) -> List[List[Dict]]:
         """host half: wait for that forward()'s copy, then per page the kept rows of both lists -> docx_page_result"""
         done, host = ticket
         done.synchronize()
+        if len(host) == 6:      # a forward() with device_order=True
+            return self._finish_ordered(n, host, org)
         counts, recs, keep = (h[:n].numpy() for h in host)
-        inp_h, inp_w = self.config.resolution
-        out = []
-        for i in range(n):
-            rows = []
-            for b in range(2):
-                m = int(counts[i, b])
-                r = recs[i, b, :m]
-                rows.append(r[keep[i, b, :m] != 0] if self.config.use_nms else r)
-            out.append(docx_page_result(rows[0], rows[1], (int(org[0]), int(org[1])), (inp_h // 4, inp_w // 4), self.config))
-        return out
+        return [self._page_host(counts, recs, keep, i, org) for i in range(n)]
 
     def __call__(self, pages: torch.Tensor) -> List[List[Dict]]:
         n, ticket = self.forward(pages)

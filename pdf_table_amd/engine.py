@@ -454,6 +454,37 @@ class HipEngine:
                                         float(thr_lo), _ptr(counts), _ptr(recs), _ptr(inds), _ptr(keep), self._stream()), "pt_docx_decode")
         return counts, recs, inds, keep
 
+    def op_docx_order(self, counts: torch.Tensor, recs: torch.Tensor, keep: torch.Tensor, affine, scores_thresh: float = 0.3, top_k: int = 100,
+                      num_classes: int = 13, n_main: int = 11, use_nms: bool = True, out=None):
+        """docx_page_result for every page of a batch in one launch (pt_op_docx_order, csrc/docx_order.hip).  counts int32 [B,2] / recs float32
+        [B,2,K,12] / keep uint8 [B,2,K]: what docx_decode returns; affine: the float64 [2,3] of centernet_decode_affine(page_h, page_w, map_h, map_w)
+        -> (n_out int32 [B], flag int32 [B], rows float32 [B,2K,6] = (x0, y0, x2, y2 of the rounded vertices, score, 0-based class) in reading
+        order) on the device.  flag != 0: the page needs the host route (a list of 64 or more blocks in a sort, ...) and has no rows; rows at and
+        behind n_out are left as they were.  out: (n_out, flag, rows) to write into.  Everything stays on the device; nothing synchronises."""
+        import numpy as np
+        self._chk(counts, torch.int32, "counts")
+        self._chk(recs, torch.float32, "recs")
+        self._chk(keep, torch.uint8, "keep")
+        if recs.dim() != 4 or recs.shape[1] != 2 or recs.shape[3] != L.PT_DOCX_REC_FLOATS or tuple(counts.shape) != (recs.shape[0], 2) \
+                or tuple(keep.shape) != tuple(recs.shape[:3]):
+            raise ValueError(f"op_docx_order: counts [B,2], recs [B,2,K,{L.PT_DOCX_REC_FLOATS}] and keep [B,2,K] expected, got {tuple(counts.shape)}, "
+                             f"{tuple(recs.shape)} and {tuple(keep.shape)}")
+        B, K = int(recs.shape[0]), int(recs.shape[2])
+        m = np.asarray(affine, np.float64).reshape(6)
+        if out is None:
+            out = (torch.zeros((B,), dtype=torch.int32, device=self._tdev), torch.zeros((B,), dtype=torch.int32, device=self._tdev),
+                   torch.zeros((B, 2 * K, 6), dtype=torch.float32, device=self._tdev))
+        n_out, flag, rows = out
+        self._chk(n_out, torch.int32, "n_out")
+        self._chk(flag, torch.int32, "flag")
+        self._chk(rows, torch.float32, "rows")
+        if n_out.numel() < B or flag.numel() < B or rows.numel() < B * 2 * K * 6:
+            raise ValueError("op_docx_order: output buffers too small")
+        L.check(self.lib.pt_op_docx_order(_ptr(counts), _ptr(recs), _ptr(keep), B, K, *[float(v) for v in m], float(scores_thresh), int(top_k),
+                                          int(num_classes), int(n_main), int(bool(use_nms)), _ptr(n_out), _ptr(flag), _ptr(rows), self._stream()),
+                "pt_op_docx_order")
+        return n_out, flag, rows
+
     def tsr_process(self, logi: torch.Tensor, dets: torch.Tensor, counts, use_2dpe: bool = False):
         """logic features of pt_tsr_decode -> (logic_axis, stacked_axis) f32 [n,3000,4]; rows [0, counts[i]) valid."""
         import numpy as np

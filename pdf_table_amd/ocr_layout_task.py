@@ -9,7 +9,8 @@ pdf_table_amd.synth_weights.picodet_state_dict) runs on the engine.
 ``model="DocXLayout"`` (the reference's only torch layout model, ocr_layout_task.py:45-68) serves a checkpoint given as ``task_path=<file or
 directory>`` (docxlayout_stage.load_checkpoint) through ``DocXLayoutStage``: same result shape, labels of ``DocXLayoutConfig``.  There are no
 seeded in-tree weights for it: without a checkpoint the constructor raises ``RuntimeError``, also when ``synthetic_seed`` is set.  ``device_decode``
-is PicoDet's decode and raises ``ValueError`` for this model (its decode always runs on the device).
+is PicoDet's decode and raises ``ValueError`` for this model (its decode always runs on the device).  ``device_order=True`` is this model's own
+knob (``DocXLayoutStage(device_order=True)``: region list and reading order on the device) and raises ``ValueError`` for any other model.
 
 ONNX door (the reference's layout stage is ONNX-only: "pytorch model not support yet!", ocr_layout_task.py:82-123): a ``model.onnx`` /
 ``inference.onnx`` under ``task_path`` (or ``task_path`` = the file) is parsed by ``pdf_table_amd.onnx_import`` and run layer by layer by
@@ -39,9 +40,14 @@ __all__ = ["OcrLayoutTask"]
 
 
 class OcrLayoutTask(BaseInferTask):
-    def __init__(self, task="ocr_layout", model="picodet", engine: HipEngine = None, device_decode: bool = False, **kwargs):
+    def __init__(self, task="ocr_layout", model="picodet", engine: HipEngine = None, device_decode: bool = False, device_order: bool = False, **kwargs):
         # device_decode=True: the stage decodes, cuts and suppresses on the device (LayoutStage(device_decode=True), pt_op_layout_decode)
         self._device_decode = bool(device_decode)
+        # device_order=True (DocXLayout only): the region list and the reading order on the device (DocXLayoutStage(device_order=True), pt_op_docx_order)
+        self._device_order = bool(device_order)
+        if self._device_order and model != "DocXLayout":
+            raise ValueError(f"device_order=True puts DocXLayout's region list and reading order on the device (pt_op_docx_order); model={model!r} has "
+                             "no such route")
         super().__init__(task=task, model=model, **kwargs)
         if model not in ["picodet", "DocXLayout"]:
             raise RuntimeError(f"current model is not supported: {model}")
@@ -127,7 +133,8 @@ class OcrLayoutTask(BaseInferTask):
         if self.model == "DocXLayout":
             from .docxlayout_stage import DocXLayoutStage
             # images reach the stage as RGB (files are read as RGB, arrays are taken as RGB: the CenterNet task's convention); the network eats BGR
-            self._stage = DocXLayoutStage(self._engine, self._config, bgr=True, precision=getattr(self, "_stage_precision", None))
+            self._stage = DocXLayoutStage(self._engine, self._config, bgr=True, precision=getattr(self, "_stage_precision", None),
+                                          device_order=self._device_order)
             return
         if getattr(self, "_exec", None) is not None:
             # the graph file behind LayoutStage's contract: forward() / finish() halves, candidate compaction on the device (pt_op_pico_candidates)

@@ -70,7 +70,9 @@ class OcrTablePipeline:
     ``layout=True, layout_model="DocXLayout", layout_task_path=<checkpoint file or directory>`` serves that DocXLayout checkpoint through
     ``DocXLayoutStage`` (same ``forward`` / ``finish`` contract, so ``predict()`` and ``predict_stream()`` treat it like the other two); the
     model has no seeded weights, so the path is required (``ValueError`` before an engine exists) and the seed is not handed to the layout
-    task.  ``layout_precision`` and ``layout_device_decode`` are PicoDet's knobs and raise ``ValueError`` for this model."""
+    task.  ``layout_precision`` and ``layout_device_decode`` are PicoDet's knobs and raise ``ValueError`` for this model;
+    ``layout_device_order=True`` is this model's own (``DocXLayoutStage(device_order=True)``: the region list and the reading order on the device,
+    flagged pages through the host route) and raises ``ValueError`` for any other layout model or with ``layout=False``."""
 
     def __init__(self, device: int = 0, detect_model: str = "db", recognizer: str = "CRNN", thresh: float = 0.2,
                  synthetic_seed: Optional[int] = None, det_task_path: Optional[str] = None,
@@ -84,7 +86,12 @@ class OcrTablePipeline:
                  sideways_check: bool = False, page_orientation: bool = False, page_orientation_task_path: Optional[str] = None,
                  table_attribute: bool = False, table_attribute_task_path: Optional[str] = None, page_preprocess: bool = False,
                  rec_batch_num: int = 6, rec_width_bucket: Optional[int] = None, device_match: bool = False,
-                 layout_device_decode: bool = False, **kwargs):
+                 layout_device_decode: bool = False, layout_device_order: bool = False, **kwargs):
+        if layout_device_order and not layout:
+            raise ValueError("layout_device_order=True puts DocXLayout's region list and reading order on the device (pt_op_docx_order); layout=False "
+                             "builds no layout stage")
+        if layout_device_order and layout_model != "DocXLayout":
+            raise ValueError(f"layout_device_order=True is DocXLayout's knob (pt_op_docx_order); layout_model={layout_model!r} has no such route")
         if layout_device_decode and not layout:
             raise ValueError("layout_device_decode=True decodes the layout stage's candidates on the device (pt_op_layout_decode); layout=False builds no "
                              "layout stage")
@@ -179,6 +186,8 @@ class OcrTablePipeline:
                 lk["stage_precision"] = layout_precision
             if layout_device_decode:      # off: the key is not handed on at all.  One stage serves predict(), predict_stream(), aux_layout and the vote's second pass
                 lk["device_decode"] = True
+            if layout_device_order:       # likewise: DocXLayoutStage(device_order=True)
+                lk["device_order"] = True
             self.layout_task = OcrLayoutTask(model=layout_model, engine=self.engine, task_type=layout_task_type, **lk)
         self.table_html = table_html      # structure + recognised text -> HTML per table (OcrTableToHtmlTask, section 8f-2)
         self.orientation_task = None
