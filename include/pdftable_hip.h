@@ -810,6 +810,37 @@ int pt_op_docx_order(const int32_t* d_counts, const float* d_recs, const uint8_t
                      double a11, double a12, float scores_thresh, int top_k, int num_classes, int n_main, int use_nms, int32_t* d_nout, int32_t* d_flag,
                      float* d_rows, pt_stream stream);
 
+/* DBPostProcess score_mode "slow" (db_pp/processor_ocr_db_pp.py:270-289, box_score_slow): the candidates with their traced contours, and the mean of the
+ * probability map over each contour's own polygon (csrc/det_poly_score.hip, compiled once, engine-free; added under ABI 21: two new entry points, no
+ * existing signature changed, so the version stays).
+ * pt_db_contour_candidates_batch (HOST): pt_db_candidates_batch -- same tracer, same max_candidates cut before the min_size test, same order, h_boxes /
+ *   h_sside / n_out bit for bit -- which also returns the contour of every kept candidate: the CHAIN_APPROX_SIMPLE vertices as the tracer emits them
+ *   (hole contours included: RETR_LIST returns them and the reference scores them), int32 (x, y) in map pixels, flat in h_points [point_cap][2],
+ *   page-major, in candidate order; h_offsets int32 [n * cap + 1]: candidate j (counted over all pages) owns points h_offsets[j] .. h_offsets[j + 1] - 1,
+ *   sum(n_out) + 1 entries are written.  *n_points_needed: the points there are.  Where that is more than point_cap NO point is written, the rest of the
+ *   output is complete and the call returns PT_OK: grow the buffer and call again.  Pages run on n_threads threads inside the library (0: all).
+ * pt_op_det_poly_scores: d_prob fp32 [n, net_h, net_w]; d_points int32 [n_points][2]; d_offsets / h_offsets int32 [nb + 1]; d_pages / h_pages int32 [nb]:
+ *   the page of each candidate.  The h_ arrays are the HOST copies of the d_ arrays: every limit is checked on them before anything is launched.
+ *   Per candidate: the bounding rectangle of its points clipped to the map; the mask cv2.fillPoly(mask, [points - (xmin, ymin)], 1) -- the 8-connected
+ *   Bresenham outline of every edge (left to right, exact halves toward the start) united with the scan-line interior for ymin <= y < ymax (edges in
+ *   16.16 fixed point with a truncated slope, sorted crossings paired, spans [(xa + 0x8000) >> 16, (xb + 0x8000) >> 16]); points may lie outside the
+ *   map.  d_scores fp32 [nb] = (float)(sum / count) of the map under the mask, added in double, or 0 when count == 0 (pt_det_box_scores's contract: a
+ *   drop-in for pt_db_finalize_batch); d_sums fp64 [nb] / d_counts int32 [nb]: the sum and the pixel count themselves, either may be NULL.
+ *   d_work: nb * PT_DET_POLY_WORK_BYTES bytes, 8-byte aligned (per-band partial results); work_bytes: its size.  A candidate's rows are split over up to
+ *   PT_DET_POLY_BANDS workgroups and added in band order by a second kernel: two launches, no atomics on floating point, the same bits in every call.
+ *   PT_ERR_INVALID with a message, nothing launched and nothing written: nb < 0, offsets that are not non-decreasing or leave [0, n_points], a page
+ *   outside [0, n), net_w > PT_DET_POLY_MAX_W (the kernel keeps one int32 per pixel of a row and wave in 64 KiB of LDS), a work buffer too small.
+ *   nb == 0 launches nothing.  No allocation, no host synchronisation (capturable). */
+#define PT_DET_POLY_MAX_W 4096
+#define PT_DET_POLY_BANDS 16
+#define PT_DET_POLY_WORK_BYTES (PT_DET_POLY_BANDS * 12)
+int pt_db_contour_candidates_batch(const uint32_t* h_bitmaps, int n, int net_h, int net_w, int max_candidates, float min_size, int n_threads,
+                                   float* h_boxes, float* h_sside, int cap, int* n_out, int32_t* h_points, long long point_cap,
+                                   int32_t* h_offsets, long long* n_points_needed);
+int pt_op_det_poly_scores(const float* d_prob, int n, int net_h, int net_w, const int32_t* d_points, int n_points, const int32_t* d_offsets,
+                          const int32_t* h_offsets, const int32_t* d_pages, const int32_t* h_pages, int nb, float* d_scores, double* d_sums,
+                          int32_t* d_counts, void* d_work, long long work_bytes, pt_stream stream);
+
 /* The TEDS table metric's two hot parts (csrc/teds.hip, compiled once, engine-free; added under ABI 21: new entry points, no existing signature
  * changed, so the version stays).  pdf_table_amd/table_metric.py packs these arrays and states the same arithmetic on the host.
  * pt_op_teds_cost: C = levenshtein(a, b) / max(len a, len b) in float64 (0 where both are empty) for every (row content, column content) of P table

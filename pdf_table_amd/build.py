@@ -23,9 +23,9 @@ HIP_SOURCES = ["conv_igemm.hip", "det_kernels.hip", "db_model.hip", "rec_kernels
                "graph_ops.hip", "rect_ops.hip", "large_conv.hip", "det_ops.hip", "ctc_ops.hip", "layout_ops.hip", "sla_head.hip", "lstm_op.hip", "cvit_model.hip", "mtl_model.hip", "mtl_decoder.hip", "c_api.hip"]
 # compiled ONCE: host-only post-processing and the format-independent corner of the ABI
 CPP_SOURCES = ["db_post.cpp", "api_common.cpp"]
-# HIP compiled ONCE (as namespace pt_bf16): kernels on uint8 pages (page_pre) or fp32 / fp64 / int32 arrays (table_match, lore_match, layout_decode, docx_decode, docx_order) or int32 / int64 / fp64 arrays (teds, cell_metric) only, no activation format; their
+# HIP compiled ONCE (as namespace pt_bf16): kernels on uint8 pages (page_pre) or fp32 / fp64 / int32 arrays (table_match, lore_match, layout_decode, docx_decode, docx_order, det_poly_score) or int32 / int64 / fp64 arrays (teds, cell_metric) only, no activation format; their
 # entry points take no engine, so the generated dispatchers call pt_bf16::api only
-ONCE_HIP_SOURCES = ["page_pre.hip", "table_match.hip", "lore_match.hip", "layout_decode.hip", "docx_decode.hip", "docx_order.hip", "teds.hip", "cell_metric.hip"]
+ONCE_HIP_SOURCES = ["page_pre.hip", "table_match.hip", "lore_match.hip", "layout_decode.hip", "docx_decode.hip", "docx_order.hip", "teds.hip", "cell_metric.hip", "det_poly_score.hip"]
 HEADERS = ["common.h", "act16.h", "dla_net.h", "dla_up.h", "net_ctx.h", os.path.join("..", "..", "include", "pdftable_hip.h")]
 # Every HIP translation unit is compiled once per 16-bit activation format (csrc/act16.h): namespace pt_bf16, and namespace pt_f16 with -DPT_ACT_F16=1
 FORMATS = [("bf16", []), ("f16", ["-DPT_ACT_F16=1"])]

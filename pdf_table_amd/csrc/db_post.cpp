@@ -394,18 +394,12 @@ static void clipper_offset_round(const cInt sx[], const cInt sy[], int len_in, d
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int pt_db_candidates(const uint32_t* h_bitmap, int net_h, int net_w, int max_candidates, float min_size, float* h_boxes,
-                     float* h_sside, int cap, int* n_out) {
-  if (!h_bitmap || !h_boxes || !n_out || net_h <= 0 || net_w <= 0 || net_w % 32 != 0) {
-    pt_set_error("pt_db_candidates: bad arguments");
-    return PT_ERR_INVALID;
-  }
+// boxes_from_bitmap up to the score (processor_ocr_db_pp.py:174-197) for one page: the first max_candidates contours, the mini-box of each, the
+// min_size gate.  kept (optional): the traced contour of every candidate that passes, in candidate order -- what box_score_slow scores.
+static int page_candidates(const uint32_t* bitmap, int net_h, int net_w, int max_candidates, float min_size, float* h_boxes, float* h_sside,
+                           int cap, std::vector<std::vector<Pt>>* kept) {
   std::vector<std::vector<Pt>> contours;
-  find_contours(h_bitmap, net_h, net_w, contours);
+  find_contours(bitmap, net_h, net_w, contours);
   const int nc = std::min((int)contours.size(), max_candidates);
   int n = 0;
   std::vector<Pf> pts;
@@ -420,9 +414,23 @@ int pt_db_candidates(const uint32_t* h_bitmap, int net_h, int net_w, int max_can
       h_boxes[(size_t)n * 8 + 2 * k + 1] = box[k].y;
     }
     if (h_sside) h_sside[n] = sside;
+    if (kept) kept->push_back(std::move(contours[i]));
     ++n;
   }
-  *n_out = n;
+  return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pt_db_candidates(const uint32_t* h_bitmap, int net_h, int net_w, int max_candidates, float min_size, float* h_boxes,
+                     float* h_sside, int cap, int* n_out) {
+  if (!h_bitmap || !h_boxes || !n_out || net_h <= 0 || net_w <= 0 || net_w % 32 != 0) {
+    pt_set_error("pt_db_candidates: bad arguments");
+    return PT_ERR_INVALID;
+  }
+  *n_out = page_candidates(h_bitmap, net_h, net_w, max_candidates, min_size, h_boxes, h_sside, cap, nullptr);
   return PT_OK;
 }
 
@@ -536,6 +544,47 @@ int pt_db_candidates_batch(const uint32_t* h_bitmaps, int n, int net_h, int net_
 }
 
 }  // extern "C"
+
+// pt_db_contour_candidates_batch (det_poly_score.hip) -- not extern "C": the exported symbol is the generated dispatcher.  pt_db_candidates_batch plus
+// the contour of every kept candidate (score_mode "slow" scores the contour's own polygon): the pages trace on the library's threads into vectors of
+// their own, then one thread lays the points out flat, page-major, in candidate order.  A point buffer that is too small gets no point at all; the
+// offsets and *n_points_needed are complete either way, so the caller can grow the buffer and call again.
+int db_contour_candidates_batch(const uint32_t* h_bitmaps, int n, int net_h, int net_w, int max_candidates, float min_size, int n_threads,
+                                float* h_boxes, float* h_sside, int cap, int* n_out, int32_t* h_points, long long point_cap, int32_t* h_offsets,
+                                long long* n_points_needed) {
+  if (!h_bitmaps || !h_boxes || !n_out || !h_offsets || !n_points_needed || (point_cap > 0 && !h_points) || point_cap < 0 || n < 0 || cap <= 0 ||
+      net_h <= 0 || net_w <= 0 || net_w % 32 != 0) {
+    pt_set_error("pt_db_contour_candidates_batch: bad arguments");
+    return PT_ERR_INVALID;
+  }
+  const size_t words = (size_t)net_h * (net_w / 32);
+  std::vector<std::vector<std::vector<Pt>>> kept(n);
+  parallel_pages(n, n_threads, [&](int i) {
+    n_out[i] = page_candidates(h_bitmaps + (size_t)i * words, net_h, net_w, max_candidates, min_size, h_boxes + (size_t)i * cap * 8,
+                               h_sside ? h_sside + (size_t)i * cap : nullptr, cap, &kept[i]);
+  });
+  long long total = 0;
+  for (const auto& page : kept)
+    for (const auto& c : page) total += (long long)c.size();
+  *n_points_needed = total;
+  if (total > 0x7fffffffLL) {
+    pt_set_error("pt_db_contour_candidates_batch: %lld contour points do not fit int32 offsets", total);
+    return PT_ERR_INVALID;
+  }
+  const bool fits = total <= point_cap;
+  int32_t off = 0;
+  size_t k = 0;
+  h_offsets[0] = 0;
+  for (const auto& page : kept)
+    for (const auto& c : page) {
+      if (fits)
+        for (const Pt& q : c) { h_points[2 * (size_t)off] = q.x; h_points[2 * (size_t)off + 1] = q.y; ++off; }
+      else
+        off += (int32_t)c.size();
+      h_offsets[++k] = off;
+    }
+  return PT_OK;
+}
 
 // filter_tag_det_res of PPOcrDetectionPostProcessor (db_pp/processor_ocr_db_pp.py:344-386) on one page's int boxes, in
 // place: order_points_clockwise (sort by x -- numpy's argsort on 4 elements is an insertion sort, i.e. stable --, the two

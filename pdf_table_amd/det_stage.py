@@ -33,8 +33,17 @@ class DetConfig:
     max_candidates: int = 1000
     min_size: float = 3.0
     use_dilation: bool = False
+    score_mode: str = "fast"        # DbPPConfig.score_mode: "fast" scores the min-area rectangle, "slow" the contour's own polygon (db_pp only)
+
+    def __post_init__(self):
+        if self.score_mode not in ("fast", "slow"):      # the reference asserts (processor_ocr_db_pp.py:164-166)
+            raise ValueError(f"score_mode must be one of 'fast' and 'slow', got {self.score_mode!r}")
+        if self.score_mode == "slow" and self.flavour == "db":
+            raise ValueError("score_mode='slow' is DBPostProcess's (flavour 'db_pp'); the torch flavour 'db' (db_net/ocr_detection_utils.py) scores "
+                             "the min-area rectangle only")
 
     def resolved(self):
+        self.__post_init__()        # a field set after construction: "slow" with the torch flavour raises here, it is not reset below
         if self.flavour == "db":    # hard-coded constants of db_net/ocr_detection_utils.py:183-196
             return DetConfig("db", self.thresh, 0.3, 1.5, 1000, 3.0, False)
         return self
@@ -178,6 +187,14 @@ class DetStage:
         bm = hb.numpy()
         t1 = _t.perf_counter()
         tm["copy"] += t1 - t0
+        if cfg.score_mode == "slow":
+            cand, counts, scores, t2 = self._slow_scores(prob, bm, ev, t1)
+            t3 = _t.perf_counter()
+            tm["score"] += t3 - t2
+            try:
+                return self._finalize(cand, scores, counts, nh, nw, src_hw)
+            finally:
+                tm["final"] += _t.perf_counter() - t3
         # contour candidates of all pages: one call, pages on threads inside the library (no Python per page)
         cand, counts = E.db_candidates_batch(bm, cfg.max_candidates, cfg.min_size, self.workers)
         t2 = _t.perf_counter()
@@ -202,6 +219,50 @@ class DetStage:
             return self._finalize(cand, scores, counts, nh, nw, src_hw)
         finally:
             tm["final"] += _t.perf_counter() - t3
+
+    def _poly_alloc(self, n_pages, cap):
+        """-> alloc(k) for db_contour_candidates_batch: room for k points in ONE pinned int32 buffer that also holds, behind the points, the offsets
+        and the page index of every candidate -- what goes to the device in one copy"""
+        def alloc(k):
+            k = k + k // 4                      # a batch with a few more points does not allocate again
+            t = self._pinned("poly", (2 * k + 2 * n_pages * cap + 1,), torch.int32)
+            return t.numpy()[:2 * k].reshape(k, 2)
+        return alloc
+
+    def _slow_scores(self, prob, bm, ev, t1):
+        """score_mode "slow": the candidates WITH their contours (one host call), one pinned upload of points, offsets and page indices and one
+        pt_op_det_poly_scores launch on the side stream behind the event the box-score launch waits for -> (cand, counts, scores [n, cap], t2)"""
+        import time as _t
+        cfg = self.cfg
+        n = prob.shape[0]
+        cap = cfg.max_candidates
+        buf = self._pin.get("poly")
+        alloc = self._poly_alloc(n, cap)
+        have = None
+        if buf is not None and buf.numel() > 2 * n * cap + 1:
+            k = (buf.numel() - 2 * n * cap - 1) // 2
+            have = buf.numpy()[:2 * k].reshape(k, 2)
+        cand, counts, pts, offs = E.db_contour_candidates_batch(bm, cfg.max_candidates, cfg.min_size, self.workers, points=have, alloc=alloc)
+        t2 = _t.perf_counter()
+        self.timing["cand"] += t2 - t1
+        tot = int(counts.sum())
+        valid = np.arange(cap)[None, :] < counts[:, None]                 # [n, cap]
+        scores = np.zeros((n, cap), np.float32)
+        if tot:
+            npts = pts.shape[0]
+            flat = self._pin["poly"].numpy()                               # [points | offsets | pages], contiguous
+            h_offs = flat[2 * npts:2 * npts + tot + 1]
+            h_pages = flat[2 * npts + tot + 1:2 * npts + 2 * tot + 1]
+            h_offs[:] = offs
+            h_pages[:] = np.repeat(np.arange(n, dtype=np.int32), counts)
+            with torch.cuda.stream(self.side):
+                if isinstance(ev, torch.cuda.Event):
+                    self.side.wait_event(ev)
+                dev = self._pin["poly"][:2 * npts + 2 * tot + 1].to(prob.device, non_blocking=True)
+                got = self.eng.op_det_poly_scores(prob, dev[:2 * npts].view(npts, 2), dev[2 * npts:2 * npts + tot + 1], dev[2 * npts + tot + 1:],
+                                                  h_offs, h_pages)
+                scores[valid] = got.cpu().numpy()
+        return cand, counts, scores, t2
 
     def _finalize(self, cand, scores, counts, nh, nw, src_hw):
         cfg = self.cfg

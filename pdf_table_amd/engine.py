@@ -518,6 +518,41 @@ class HipEngine:
                                                self._stream()), "pt_det_box_scores")
         return scores
 
+    def op_det_poly_scores(self, prob: torch.Tensor, points: torch.Tensor, offsets: torch.Tensor, pages: torch.Tensor, h_offsets, h_pages,
+                           sums: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None, scores: Optional[torch.Tensor] = None,
+                           work: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """box_score_slow for nb contours in one call (pt_op_det_poly_scores, csrc/det_poly_score.hip): the mean of prob f32 [n, H, W] over the
+        cv2.fillPoly mask of each contour inside its clipped bounding rectangle.  points int32 [np, 2] (x, y), offsets int32 [nb + 1], pages int32
+        [nb] on the device; h_offsets / h_pages: their host copies (numpy), which every limit is checked on (PtError, nothing launched, nothing
+        written).  -> scores f32 [nb] = float32(sum / count), 0 for an empty mask.  sums f64 [nb] / counts int32 [nb]: buffers that also receive the
+        sum and the pixel count; scores / work (uint8, nb * PT_DET_POLY_WORK_BYTES): buffers to use instead of allocating."""
+        self._chk(prob, torch.float32, "prob")
+        for t, name in ((points, "points"), (offsets, "offsets"), (pages, "pages")):
+            self._chk(t, torch.int32, name)
+        h_offsets = np.ascontiguousarray(h_offsets, dtype=np.int32).reshape(-1)
+        h_pages = np.ascontiguousarray(h_pages, dtype=np.int32).reshape(-1)
+        n, H, W = prob.shape
+        nb = h_pages.shape[0]
+        if h_offsets.shape[0] != nb + 1 or offsets.numel() < nb + 1 or pages.numel() < nb or points.numel() % 2:
+            raise ValueError(f"op_det_poly_scores: offsets {tuple(offsets.shape)} / host {h_offsets.shape} and pages {tuple(pages.shape)} / host "
+                             f"{h_pages.shape} do not fit, or points {tuple(points.shape)} is not [np, 2]")
+        if scores is None:
+            scores = torch.empty((nb,), dtype=torch.float32, device=self._tdev)
+        if work is None:
+            work = torch.empty((max(nb, 1) * L.PT_DET_POLY_WORK_BYTES,), dtype=torch.uint8, device=self._tdev)
+        self._chk(scores, torch.float32, "scores")
+        self._chk(work, torch.uint8, "work")
+        if sums is not None:
+            self._chk(sums, torch.float64, "sums")
+        if counts is not None:
+            self._chk(counts, torch.int32, "counts")
+        if scores.numel() < nb or (sums is not None and sums.numel() < nb) or (counts is not None and counts.numel() < nb):
+            raise ValueError("op_det_poly_scores: output buffers too small")
+        L.check(self.lib.pt_op_det_poly_scores(_ptr(prob), n, H, W, _ptr(points), points.numel() // 2, _ptr(offsets), h_offsets.ctypes.data_as(C.c_void_p),
+                                               _ptr(pages), h_pages.ctypes.data_as(C.c_void_p), nb, _ptr(scores), _ptr(sums), _ptr(counts), _ptr(work),
+                                               work.numel(), self._stream()), "pt_op_det_poly_scores")
+        return scores[:nb]
+
     # ---- image-page straightening (csrc/page_pre.hip) ---------------------------------------------
     def page_line_mask(self, pages: torch.Tensor) -> torch.Tensor:
         """uint8 RGB [n, h, w, 3] -> the deskew's opened horizontal-line mask, bit-packed: int64 [n, h, (w + 63) // 64] (bit b of word q =
@@ -1800,6 +1835,39 @@ def db_candidates_batch(bitmaps: np.ndarray, max_candidates: int = 1000, min_siz
                                        boxes.ctypes.data_as(C.c_void_p), None, cap, counts.ctypes.data_as(C.c_void_p)),
             "pt_db_candidates_batch")
     return boxes, counts
+
+
+def db_contour_candidates_batch(bitmaps: np.ndarray, max_candidates: int = 1000, min_size: float = 3.0, n_threads: int = 0,
+                                points: Optional[np.ndarray] = None, alloc=None):
+    """db_candidates_batch that also returns the traced contour of every kept candidate (pt_db_contour_candidates_batch; what score_mode "slow"
+    scores).  -> (boxes f32 [n, cap, 8], counts int32 [n], points int32 [np, 2] (x, y), offsets int32 [sum(counts) + 1]): candidate j, counted over
+    the pages in order, owns points[offsets[j]:offsets[j + 1]].  points: a C-contiguous int32 [cap, 2] array to write into (DetStage passes a view
+    of pinned memory); alloc(np) -> such an array of at least np rows (default: numpy).  A buffer that is too small loses nothing but the call: the
+    library reports how many points there are, alloc gives a buffer that holds them and the call is made again; the result is a view of the buffer."""
+    lib = L.load()
+    bm = np.ascontiguousarray(bitmaps).view(np.uint32)
+    n, H, wpr = bm.shape
+    cap = max_candidates
+    boxes = np.empty((n, cap, 8), dtype=np.float32)
+    counts = np.zeros((n,), dtype=np.int32)
+    offsets = np.zeros((n * cap + 1,), dtype=np.int32)
+    alloc = alloc or (lambda k: np.empty((k, 2), dtype=np.int32))
+    if points is None:
+        points = alloc(max(1024, 64 * n))
+    need = C.c_longlong()
+    for _ in range(2):
+        if points.dtype != np.int32 or points.ndim != 2 or points.shape[1] != 2 or not points.flags.c_contiguous:
+            raise ValueError("db_contour_candidates_batch: points must be a C-contiguous int32 [cap, 2] array")
+        L.check(lib.pt_db_contour_candidates_batch(bm.ctypes.data_as(C.c_void_p), n, H, wpr * 32, max_candidates, float(min_size), int(n_threads),
+                                                   boxes.ctypes.data_as(C.c_void_p), None, cap, counts.ctypes.data_as(C.c_void_p),
+                                                   points.ctypes.data_as(C.c_void_p), points.shape[0], offsets.ctypes.data_as(C.c_void_p),
+                                                   C.byref(need)), "pt_db_contour_candidates_batch")
+        if need.value <= points.shape[0]:
+            break
+        points = alloc(int(need.value))
+    else:
+        raise L.PtError(f"pt_db_contour_candidates_batch: alloc returned {points.shape[0]} rows for {need.value} points")
+    return boxes, counts, points[:need.value], offsets[:int(counts.sum()) + 1]
 
 
 def db_finalize_batch(boxes: np.ndarray, scores: np.ndarray, counts: np.ndarray, net_hw, dest_hw, box_thresh: float = 0.6,

@@ -43,12 +43,13 @@ PT_TSR_MAX_CELLS = 3000
 PT_CENTERNET_MAX_CELLS = 1000
 PT_CELL_METRIC_MAX = 4096      # cells per table pt_op_cell_metric takes
 PT_DOCX_REC_FLOATS, PT_DOCX_MAX_K = 12, 128
+PT_DET_POLY_MAX_W, PT_DET_POLY_BANDS, PT_DET_POLY_WORK_BYTES = 4096, 16, 16 * 12      # pt_op_det_poly_scores: widest map, bands of a candidate, work bytes per candidate
 PT_ROTATE_90_CLOCKWISE, PT_ROTATE_180, PT_ROTATE_90_COUNTERCLOCKWISE = 0, 1, 2   # cv2.rotate codes (pt_page_quarter_turn)
 PT_REC_H, PT_REC_W, PT_REC_T, PT_REC_NCLS = 32, 640, 160, 7644
 PT_PROF_CLASSES = ("conv3x3", "conv1x1", "stem", "other")
 EXPECTED_ABI = 21         # pt_abi_version() of the library these prototypes were written against (include/pdftable_hip.h).  21: pt_op_lore_tok_prepare .. scatter4.  20: pt_op_mtl_*.  19: pt_op_cvit_*.  pt_op_affine_act /
 #                           pt_op_db_tail were ADDED under 18: no existing signature changed, and a library without them fails to bind by name (_proto);
-#                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large / pt_op_lore_hm_head / pt_op_ctc_greedy / pt_op_sla_* / pt_op_table_match / pt_op_pico_candidates under 19, pt_op_lore_match / pt_op_layout_decode under 20, pt_docx_preprocess / pt_docx_forward_net / pt_docx_decode / pt_op_teds_* / pt_op_cell_metric / pt_op_docx_order under 21
+#                           pt_op_dwconvt_up_add / pt_op_dcn_up_add likewise, and pt_op_conv2d_large / pt_op_lore_hm_head / pt_op_ctc_greedy / pt_op_sla_* / pt_op_table_match / pt_op_pico_candidates under 19, pt_op_lore_match / pt_op_layout_decode under 20, pt_docx_preprocess / pt_docx_forward_net / pt_docx_decode / pt_op_teds_* / pt_op_cell_metric / pt_op_docx_order / pt_db_contour_candidates_batch / pt_op_det_poly_scores under 21
 
 _lib = None
 
@@ -184,6 +185,8 @@ def _proto(lib):
         "pt_op_lore_match": (i, [vp, vp, vp, i, vp, vp, vp, vp, i, vp, vp]),      # added under ABI 20, bound by name
         "pt_op_layout_decode": (i, [vp, vp, i, i, i, i, ip, i, i, i, i, i, f, C.c_double, i, i, i, i, vp, vp, vp]),      # likewise
         "pt_op_docx_order": (i, [vp, vp, vp, i, i] + [C.c_double] * 6 + [f, i, i, i, i, vp, vp, vp, vp]),      # added under ABI 21, bound by name
+        "pt_db_contour_candidates_batch": (i, [vp, i, i, i, i, f, i, vp, vp, i, vp, vp, C.c_longlong, vp, C.POINTER(C.c_longlong)]),      # added under ABI 21, bound by name
+        "pt_op_det_poly_scores": (i, [vp, i, i, i, vp, i, vp, vp, vp, vp, i, vp, vp, vp, vp, C.c_longlong, vp]),      # likewise
         "pt_op_teds_scratch_bytes": (i, [i, i, C.POINTER(C.c_longlong)]),      # added under ABI 21, bound by name
         "pt_op_teds_cost": (i, [vp, C.c_longlong, vp, vp, i, vp, vp, i, vp, C.c_longlong, vp]),      # likewise
         "pt_op_teds_dist": (i, [vp, vp, i, vp, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, C.c_longlong, vp, vp]),      # likewise

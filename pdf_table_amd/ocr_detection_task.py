@@ -65,7 +65,7 @@ class OcrDetectionTask(BaseInferTask):
         self._engine = engine
         self._det_cfg = DetConfig(flavour=model, thresh=thresh,
                                   box_thresh=kwargs.get("box_thresh", 0.6), unclip_ratio=kwargs.get("unclip_ratio", 1.5),
-                                  use_dilation=kwargs.get("use_dilation", False))
+                                  use_dilation=kwargs.get("use_dilation", False), score_mode=kwargs.get("score_mode", "fast"))
         self._config.model_path = self.get_model_name_or_path()
         self._get_inference_model()
 
