@@ -26,7 +26,7 @@ CPP_SOURCES = ["db_post.cpp", "api_common.cpp"]
 # HIP compiled ONCE (as namespace pt_bf16): kernels on uint8 pages (page_pre) or fp32 / fp64 / int32 arrays (table_match, lore_match, layout_decode, docx_decode, docx_order, det_poly_score) or int32 / int64 / fp64 arrays (teds, cell_metric) only, no activation format; their
 # entry points take no engine, so the generated dispatchers call pt_bf16::api only
 ONCE_HIP_SOURCES = ["page_pre.hip", "table_match.hip", "lore_match.hip", "layout_decode.hip", "docx_decode.hip", "docx_order.hip", "teds.hip", "cell_metric.hip", "det_poly_score.hip"]
-HEADERS = ["common.h", "act16.h", "dla_net.h", "dla_up.h", "net_ctx.h", os.path.join("..", "..", "include", "pdftable_hip.h")]
+HEADERS = ["common.h", "act16.h", "conv_pick.h", "dla_net.h", "dla_up.h", "net_ctx.h", os.path.join("..", "..", "include", "pdftable_hip.h")]
 # Every HIP translation unit is compiled once per 16-bit activation format (csrc/act16.h): namespace pt_bf16, and namespace pt_f16 with -DPT_ACT_F16=1
 FORMATS = [("bf16", []), ("f16", ["-DPT_ACT_F16=1"])]
 

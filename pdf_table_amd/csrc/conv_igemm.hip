@@ -1,31 +1,36 @@
-// conv_igemm.hip -- implicit-GEMM convolution for gfx950 (MI355X), bf16 in / fp32 accumulate.
+// conv_igemm.hip -- the dense convolutions and GEMMs of every model graph on gfx950 (MI355X): 16-bit operands, fp32 accumulate.
 //
-// Covers every dense conv of the hot-path nets (reference layer lists: SURVEY.md appendix A):
-//   3x3 s1/s2 and 1x1 s1/s2 convolutions of ResNet-18 / SegDetector (db_net/dbnet.py:102-171,
-//   260-336, 513-539) and the CRNN conv stack (crnn/modeling_crnn.py:40-87), plus
-//   ConvTranspose2d(k=2,s=2) as a 1x1 GEMM with N = 4*Cout and a pixel-shuffle epilogue.
+// Activations are NHWC, weights pre-tiled [N/64][Cin/32][taps][64][32] with BN folded on the host; ConvTranspose2d(k=2,s=2) runs as a 1x1 GEMM with
+// N = 4*Cout and a pixel-shuffle epilogue.  Every kernel takes one ConvK; blockIdx -> tile is XCD-aware (xcd_remap).
 //
-// Design (DESIGN.md "conv kernel"):
-//   * activations NHWC bf16, weights pre-tiled [N/64][Cin/32][taps][64][32] bf16 (BN folded on host)
-//   * one workgroup = 4 waves = an 8x32 (stride 1) or 4x32 (stride 2) patch of output pixels x 64
-//     output channels; the input halo patch for a 32-channel slice is staged ONCE in LDS and all
-//     KSxKS taps read it from there (im2col never touches HBM/L2)
-//   * v_mfma_f32_32x32x16_bf16: the 32 MFMA rows are 32 consecutive output pixels of one image row,
-//     so an A fragment is one ds_read_b128 per lane at a fixed stride (80 B per pixel: 64 B of
-//     channels + 16 B pad => conflict-free across the 16-lane groups of ds_read_b128)
-//   * next K-slice is prefetched global->VGPR while the current one is multiplied (2 workgroups per
-//     CU cover the rest of the latency)
-//   * epilogue goes through LDS as fp32 so that bias + residual (+ fused nearest-x2 upsample of the
-//     residual) + ReLU + bf16 rounding + (replicated / pixel-shuffled / channel-offset) stores are
-//     all 16-byte, channel-contiguous accesses
-//   * blockIdx -> tile mapping is XCD-aware: consecutive logical tiles (all N-tiles of a patch, then
-//     the neighbouring patch) stay on one XCD so the halo and the weights hit that XCD's L2.
+// Map of the file, in its order:
+//   ConvK, the conversions, xcd_remap, tile_order          shared by all kernels
+//   epilogue_store (staged through LDS as fp32),           bias, residual, activation, pooling, fused heads; 16-byte channel-contiguous stores
+//   epilogue_direct_row (from the accumulators)
+//   conv_igemm_kernel<KS, STRIDE, GEOM, NHALF, DIRECT, F16>  "chunk" (v1): a 4 x 32 / 8 x 32 / 4 x 64 pixel patch x 64 channels, 32-channel slices
+//                                                          staged through registers; takes every layer no other family takes
+//   conv1x1_wide_kernel<KG, STAGED, GEN>                   "wide1": 1x1 stride 1, KG chunks per stage
+//   conv3x3_dma16_kernel<NT, NWV, S>                       "dma16" (v3): 16-channel slices DMA-fed into LDS, 16 x 32 or 32 x 32 pixels x 64 * NT channels
+//   conv3x3_pipe_kernel<NT, NWV, SKEW, BR, DIRECT, S, PHASE>  "pipe" (v4): the same tile with a software-pipelined tap loop; BR: blocks of 4 / 8 rows
+//   conv3x3_pipe_persist_kernel, ..._persist_hm_kernel     "pipe_persist" (v5): a run of tiles per workgroup; with Lore's 256 -> 2 heat-map layer fused
+//   gemm_pipe_kernel<LIST>                                 "gemm_pipe": 1x1 stride 1 with K >= 512 as a pipelined GEMM, 512 rows x 128 channels
+//   crnn_conv01_kernel                                     CRNN conv0 + pool + conv1 + pool            (pt_launch_crnn_conv01)
+//   dwpw_kernel<K, NB>                                     depthwise k x k + pointwise 1x1            (pt_launch_dwpw)
+//   conv3x3_ws64_kernel                                    "ws64": weight-stationary persistent 64 -> 64
+//   conv_stem7x7_kernel, ..._pool_kernel, ..._pool_ws_kernel, ..._thin_kernel   the 7x7 stems (pt_launch_stem7x7, pt_launch_stem7x7_pool)
+//   host side                                              pt_lds_attr, pt_zero_page, launch_conv: the launch code every family shares;
+//                                                          pt_launch_conv: validate, fill ConvK, conv_pick, switch over the instance
+//
+// Which family and instance a layer takes is decided in conv_pick.h (conv_pick: a pure function of the layer's shape, the CU count and the PT_*
+// switches; the rules and the measurements behind them are there), and nowhere else.  pt_launch_conv launches what it names: its switch is the
+// only place a dense-conv kernel is instantiated, one row per instance.  tools/conv_pick.cpp answers "which kernel does this layer take" on a CPU.
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "conv_pick.h"
 
 namespace PT_FMT_NS {
 
@@ -72,7 +77,7 @@ struct ConvK {
   const int* ylimit;      // device int: tiles whose first output row is >= *ylimit do nothing (data-dependent extents)
   const int* xlimit;      // device int [B]: tiles of image b whose first output column is >= xlimit[b] do nothing (ragged lines)
   const int* xlimit_rows; // device int [Ho]: the same per output ROW (sequence views [1, lines, T, C])
-  const int* xcols;       // host-side bookkeeping only (launch_cfg): ConvDesc.xlimit_cols
+  const int* xcols;       // host-side bookkeeping only (pt_prof_limit_slot): ConvDesc.xlimit_cols
   // 1x1 stride-1 only: K over nseg > 1 tensors (ConvDesc.in_more / seg_c); `in` is segment 0
   const bf16_t* in1;
   const bf16_t* in2;
@@ -3261,365 +3266,107 @@ __global__ __launch_bounds__(256, 2) void conv_stem7x7_thin_kernel(ConvK p) {
   }
 }
 
-static void launch_half(ConvK& k, unsigned nblk, hipStream_t s) {
-  using C = ConvCfg<3, 1, 0>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<3, 1, 0, 1>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv_igemm_kernel<3, 1, 0, 1>), dim3(nblk), dim3(256), C::SMEM, s, k);
-}
+// ---- host side ------------------------------------------------------------------------------------------------------------------------------
+// conv_pick.h counts tiles with the tile sizes written there, and one persistent workgroup per CU: they are these kernels' own
+static_assert(Dma16Cfg<1, 8, 1>::TH == conv_dma_tile_rows(1, 8, 1) && Dma16Cfg<2, 8, 1>::TH == conv_dma_tile_rows(2, 8, 1) &&
+              Dma16Cfg<1, 4, 1>::TH == conv_dma_tile_rows(1, 4, 1) && Dma16Cfg<2, 8, 2>::TH == conv_dma_tile_rows(2, 8, 2), "conv_pick.h: dma16 tile rows");
+static_assert(PipeCfg<1, 8, 0, 1>::TH == conv_dma_tile_rows(1, 8, 1) && PipeCfg<2, 8, 0, 1>::TH == conv_dma_tile_rows(2, 8, 1) &&
+              PipeCfg<1, 4, 0, 1>::TH == conv_dma_tile_rows(1, 4, 1) && PipeCfg<2, 8, 0, 2>::TH == conv_dma_tile_rows(2, 8, 2) &&
+              PipeCfg<2, 8, 4, 1>::NBLK == 4 && PipeCfg<2, 8, 8, 1>::NBLK == 2, "conv_pick.h: pipe tile rows and blocks");
+static_assert(2 * PipeCfg<1, 8, 0, 1>::BUF_BYTES > 80 * 1024 && 2 * PipeCfg<2, 8, 0, 1>::BUF_BYTES > 80 * 1024, "conv_pick.h: one persistent workgroup's LDS per CU");
+static_assert(ConvCfg<3, 1, 0>::TH == 8 && ConvCfg<3, 2, 0>::TH == 4 && ConvCfg<1, 1, 0>::TH == 4 && ConvCfg<3, 1, 1>::TH == 4 && ConvCfg<3, 1, 1>::TW == 64 &&
+              Ws64Cfg::TH == 16 && GemmPipeCfg::NG == 16 && GemmPipeCfg::NW == 128, "conv_pick.h: chunk / ws64 / gemm tiles");
 
-// layers with a plain epilogue: the register-epilogue instances of the kernel (1x1, stride-2 3x3, 3x3 at both widths)
-template <int KS, int STRIDE, int NHALF>
-static void launch_direct(const ConvK& k, unsigned nblk, hipStream_t s) {
-  using C = ConvCfg<KS, STRIDE, 0>;
+// the dynamic-LDS limit of a kernel instance, set before its first launch
+template <auto Kern>
+static int pt_lds_attr(int smem) {
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, STRIDE, 0, NHALF, true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM);
+    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
     attr_done = true;
   }
-  hipLaunchKernelGGL((conv_igemm_kernel<KS, STRIDE, 0, NHALF, true>), dim3(nblk), dim3(256), C::SMEM, s, k);
-}
-
-static bool conv1_wide() {      // PT_CONV1_WIDE=0: conv_igemm_kernel<1, 1> (one 32-channel chunk per stage) for every 1x1 stride-1 layer (A/B switch, read per call)
-  const char* ev = getenv("PT_CONV1_WIDE");
-  return !(ev && ev[0] == '0');
-}
-template <int KG, bool STAGED, bool GEN>
-static void launch_wide1_(const ConvK& k, unsigned nblk, hipStream_t s) {
-  using C = Conv1WideCfg<KG>;
-  constexpr int smem = STAGED ? C::SMEM_STAGED : C::SMEM;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv1x1_wide_kernel<KG, STAGED, GEN>), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((conv1x1_wide_kernel<KG, STAGED, GEN>), dim3(nblk), dim3(256), smem, s, k);
-}
-// KG = 4 where Cin is a multiple of 128, else 2 (zero-padded last stage where Cin is an odd number of 32-channel chunks)
-template <bool STAGED>
-static void launch_wide1(const ConvK& k, unsigned nblk, hipStream_t s) {
-  const bool kg4 = k.Cin % 128 == 0;
-  if (k.ylimit || k.Cin % 64 != 0) kg4 ? launch_wide1_<4, STAGED, true>(k, nblk, s) : launch_wide1_<2, STAGED, true>(k, nblk, s);
-  else kg4 ? launch_wide1_<4, STAGED, false>(k, nblk, s) : launch_wide1_<2, STAGED, false>(k, nblk, s);
-}
-
-template <int KS, int STRIDE, int GEOM = 0>
-static int launch_cfg(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = ConvCfg<KS, STRIDE, GEOM>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, STRIDE, GEOM>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<KS, STRIDE, GEOM, 2, false, true>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    attr_done = true;
-  }
-  k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
-  k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
-  k.n_tiles = k.N / 64;
-  long long nblk = (long long)k.B * k.tiles_x * k.tiles_y * k.n_tiles;
-  if (GEOM == 1 && k.blist) {      // pairs of live 32-column blocks: the worst case is every block of every image
-    k.tiles_x = (int)(((long long)k.B * (k.Wo / 32) + 1) / 2);
-    k.tiles_y = 1;
-    nblk = (long long)k.tiles_x * k.n_tiles;
-  }
-  PT_REQUIRE(nblk > 0 && nblk < (1ll << 31), "conv grid out of range (%lld blocks)", nblk);
-  if (k.ylimit) {      // mostly empty worst-case extents: 16 tiles per workgroup
-    k.reps = 16;
-    k.total_tiles = (int)nblk;
-    k.n_group = 0;
-    nblk = (nblk + 15) / 16;
-  }
-  char label[48];
-  snprintf(label, sizeof(label), "conv%dx%d s%d %d->%d @%dx%d%s", KS, KS, STRIDE, k.Cin, k.N, k.Ho, k.Wo, k.head_w ? " +head" : (k.split == 2 ? " h2" : (k.split ? " x3" : "")));
-  int lim_slot = -1;
-  {
-    PtProfScope prof(e, s, KS == 3 ? PT_PROF_CONV3X3 : PT_PROF_CONV1X1, flop, label);
-    static int direct1 = -1;      // PT_CONV1_DIRECT=0: the staged epilogue for every launch of this kernel (A/B switch)
-    if (direct1 < 0) { const char* ev = getenv("PT_CONV1_DIRECT"); direct1 = ev ? atoi(ev) : 1; }
-    const bool plain = direct1 && GEOM == 0 && !k.split && !k.pool && !k.head_w && !k.argmax_part && !k.res_f32 && !k.shuffle_cout;
-    const bool narrow = KS == 3 && STRIDE == 1 && GEOM == 0 && k.n_valid > 0 && k.n_valid <= 32 && k.N == 64 && !k.split && !k.pool &&
-                        !k.head_w && !k.argmax_part;      // <= 32 real output channels: half-width variant
-    // (Cin = 32 stays on the chunk kernel: one chunk is one stage either way, and the padded 2-chunk stage measured slower, 0.31 -> 0.37 ms @256x256)
-    const bool wide1 = KS == 1 && STRIDE == 1 && GEOM == 0 && !k.split && !k.pool && k.Cin >= 64 && conv1_wide();
-    if (narrow && plain)
-      launch_direct<3, 1, 1>(k, (unsigned)nblk, s);
-    else if (narrow)
-      launch_half(k, (unsigned)nblk, s);
-    // every 1x1 stride-1 layer but the split / pooled ones: row-limited, Cin % 64 != 0 and the staged epilogues included
-    else if (wide1)
-      plain ? launch_wide1<false>(k, (unsigned)nblk, s) : launch_wide1<true>(k, (unsigned)nblk, s);
-    else if (plain && KS == 1 && STRIDE == 1)
-      launch_direct<1, 1, 2>(k, (unsigned)nblk, s);
-    else if (plain && KS == 3 && STRIDE == 2)
-      launch_direct<3, 2, 2>(k, (unsigned)nblk, s);
-    else if (plain && KS == 1 && STRIDE == 2)
-      launch_direct<1, 2, 2>(k, (unsigned)nblk, s);
-    else if (plain && KS == 3 && STRIDE == 1)
-      launch_direct<3, 1, 2>(k, (unsigned)nblk, s);
-    else if (k.split == 2)
-      hipLaunchKernelGGL((conv_igemm_kernel<KS, STRIDE, GEOM, 2, false, true>), dim3((unsigned)nblk), dim3(256), C::SMEM, s, k);
-    else
-      hipLaunchKernelGGL((conv_igemm_kernel<KS, STRIDE, GEOM>), dim3((unsigned)nblk), dim3(256), C::SMEM, s, k);
-    if ((k.ylimit || k.xcols) && prof.idx >= 0 && e->prof.h_lims && e->prof.n_lims < PtProfile::MAX_LIMS) {
-      // the launch covers the worst case and stops at a device-side row limit (or per-image column limits): remember
-      // where the limit will land
-      auto& pd = e->prof.pending[prof.idx];
-      pd.lim_slot = lim_slot = e->prof.n_lims++;
-      pd.rows = k.ylimit ? k.Ho : (k.xlimit_rows ? k.Ho * k.Wo : k.B * k.Wo);
-    }
-  }
-  if (lim_slot >= 0)      // behind the launch (and outside its event pair): the limit the kernel saw, to pinned memory
-    (void)hipMemcpyAsync(e->prof.h_lims + lim_slot, k.ylimit ? k.ylimit : k.xcols, sizeof(int), hipMemcpyDeviceToHost, s);
-  PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }
 
-static bool use_dma_kernel() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("PT_CONV_DMA");
-    v = s ? atoi(s) : 1;
-  }
-  return v != 0;
-}
-
-template <int NT, int NWV, int S = 1>
-static int launch_dma16(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = Dma16Cfg<NT, NWV, S>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_dma16_kernel<NT, NWV, S>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    attr_done = true;
-  }
+// 8 KiB of zeros, made at the first launch that needs it: DMA source for halo pixels outside the image
+static int pt_zero_page(pt_engine* e) {
   if (!e->zero_page) {
     PT_HIP_CHECK(hipMalloc(&e->zero_page, 8192));
     PT_HIP_CHECK(hipMemset(e->zero_page, 0, 8192));
   }
-  k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
-  k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
-  k.n_tiles = k.N / C::NW;
-  const long long nblk = (long long)k.B * k.tiles_x * k.tiles_y * k.n_tiles;
-  PT_REQUIRE(nblk > 0 && nblk < (1ll << 31), "conv grid out of range (%lld blocks)", nblk);
-  char label[48];
-  snprintf(label, sizeof(label), "conv3x3 %s%s %d->%d @%dx%d%s", S == 2 ? "s2 v3" : "v3", NWV == 4 ? "h" : "", k.Cin, k.N, k.Ho, k.Wo, k.split ? " x3" : "");
-  PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, label);
-  hipLaunchKernelGGL((conv3x3_dma16_kernel<NT, NWV, S>), dim3((unsigned)nblk), dim3(C::NTHR), C::SMEM, s, k,
-                     reinterpret_cast<const bf16_t*>(e->zero_page));
-  PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }
 
-// v4: the software-pipelined tap loop (conv3x3_pipe_kernel); same tiling arithmetic and labels as launch_dma16
-template <int NT, int NWV, bool SKEW, int BR = 0, bool DIRECT = false, int S = 1, bool PHASE = false>
-static int launch_pipe(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = PipeCfg<NT, NWV, BR, S>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pipe_kernel<NT, NWV, SKEW, BR, DIRECT, S, PHASE>), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    attr_done = true;
-  }
-  k.n_tiles = k.N / C::NW;
-  long long nblk;
-  if (C::NBLK == 1) {
-    k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
-    k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
-    nblk = (long long)k.B * k.tiles_x * k.tiles_y * k.n_tiles;
-  } else if (k.blist) {      // NBLK live 32-column blocks per workgroup: the worst case is every block of every image
-    k.tiles_x = (int)(((long long)k.B * (k.Wo / 32) + C::NBLK - 1) / C::NBLK);
-    k.tiles_y = 1;
-    nblk = (long long)k.tiles_x * k.n_tiles;
-  } else {                   // NBLK consecutive column blocks of one image
-    k.tiles_x = (k.Wo + C::NBLK * 32 - 1) / (C::NBLK * 32);
-    k.tiles_y = 1;
-    nblk = (long long)k.B * k.tiles_x * k.n_tiles;
-  }
-  PT_REQUIRE(nblk > 0 && nblk < (1ll << 31), "conv grid out of range (%lld blocks)", nblk);
-  char label[48];
-  if (C::NBLK == 1) snprintf(label, sizeof(label), "conv3x3 %sv4%s%s %d->%d @%dx%d%s", S == 2 ? "s2 " : "", NWV == 4 ? "h" : "", PHASE ? "p" : "", k.Cin, k.N, k.Ho, k.Wo, k.split ? " x3" : "");
-  else snprintf(label, sizeof(label), "conv3x3 v4b %d->%d @%dx%d%s", k.Cin, k.N, k.Ho, k.Wo, k.split ? " x3" : "");
-  int lim_slot = -1;
+// A launch that covers the worst case and stops at a device-side row limit (or per-image / per-row column limits) is credited at read-out with
+// the rows the limit let through: pt_prof_limit_slot (inside the launch's PtProfScope) remembers where the limit will land, pt_prof_limit_copy
+// (behind the launch and outside its event pair) queues the copy of the limit the kernel saw to pinned memory
+static int pt_prof_limit_slot(pt_engine* e, const PtProfScope& prof, const ConvK& k) {
+  if (!(k.ylimit || k.xcols) || prof.idx < 0 || !e->prof.h_lims || e->prof.n_lims >= PtProfile::MAX_LIMS) return -1;
+  auto& pd = e->prof.pending[prof.idx];
+  pd.lim_slot = e->prof.n_lims++;
+  pd.rows = k.ylimit ? k.Ho : (k.xlimit_rows ? k.Ho * k.Wo : k.B * k.Wo);
+  return pd.lim_slot;
+}
+static void pt_prof_limit_copy(pt_engine* e, int lim_slot, const ConvK& k, hipStream_t s) {
+  if (lim_slot >= 0) (void)hipMemcpyAsync(e->prof.h_lims + lim_slot, k.ylimit ? k.ylimit : k.xcols, sizeof(int), hipMemcpyDeviceToHost, s);
+}
+
+// everything of a dense-conv launch but the instance
+struct ConvLaunch {
+  pt_engine* e;
+  ConvK& k;
+  unsigned nblk;      // workgroups
+  const char* label;
+  int prof_class;
+  double flop;
+  hipStream_t s;
+};
+
+template <auto Kern, class... Extra>
+static int launch_conv(const ConvLaunch& L, int nthr, int smem, Extra... extra) {
+  if (int rc = pt_lds_attr<Kern>(smem)) return rc;
+  int lim_slot;
   {
-    PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, label);
-    hipLaunchKernelGGL((conv3x3_pipe_kernel<NT, NWV, SKEW, BR, DIRECT, S, PHASE>), dim3((unsigned)nblk), dim3(C::NTHR), C::SMEM, s, k, reinterpret_cast<const bf16_t*>(e->zero_page));
-    if (k.xcols && prof.idx >= 0 && e->prof.h_lims && e->prof.n_lims < PtProfile::MAX_LIMS) {
-      // per-image column limits: the launch covers the worst case; remember where the limit will land (credited at read-out, like launch_cfg)
-      auto& pd = e->prof.pending[prof.idx];
-      pd.lim_slot = lim_slot = e->prof.n_lims++;
-      pd.rows = k.B * k.Wo;
-    }
+    PtProfScope prof(L.e, L.s, L.prof_class, L.flop, L.label);
+    hipLaunchKernelGGL(Kern, dim3(L.nblk), dim3(nthr), smem, L.s, L.k, extra...);
+    lim_slot = pt_prof_limit_slot(L.e, prof, L.k);
   }
-  if (lim_slot >= 0) (void)hipMemcpyAsync(e->prof.h_lims + lim_slot, k.xcols, sizeof(int), hipMemcpyDeviceToHost, s);
+  pt_prof_limit_copy(L.e, lim_slot, L.k, L.s);
   PT_HIP_CHECK(hipGetLastError());
   return PT_OK;
 }
 
-// the persistent form of launch_pipe<NT, NWV, true, 0, true, S> (conv3x3_pipe_persist_kernel): as many workgroups as fit the chip, a contiguous run of tiles each
-template <int NT, int NWV, int S>
-static int launch_pipe_persist(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = PipeCfg<NT, NWV, 0, S>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pipe_persist_kernel<NT, NWV, S>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * C::BUF_BYTES));
-    attr_done = true;
-  }
-  k.n_tiles = k.N / C::NW;
-  k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
-  k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
-  const long long total = (long long)k.B * k.tiles_x * k.tiles_y * k.n_tiles;
-  PT_REQUIRE(total > 0 && total < (1ll << 31), "conv grid out of range (%lld tiles)", total);
-  k.total_tiles = (int)total;
-  const int per_cu = 2 * C::BUF_BYTES <= 80 * 1024 ? 2 : 1;      // workgroups that fit a CU's LDS
-  long long grid = (long long)e->num_cu * per_cu;
-  if (const char* gv = getenv("PT_CONV_PERSIST_GRID")) {          // tests: fewer workgroups, longer runs
-    const int gg = atoi(gv);
-    if (gg > 0) grid = gg;
-  }
-  if (grid > total) grid = total;
-  char label[48];
-  snprintf(label, sizeof(label), "conv3x3 %sv5%s %d->%d @%dx%d", S == 2 ? "s2 " : "", NWV == 4 ? "h" : "", k.Cin, k.N, k.Ho, k.Wo);
-  {
-    PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, label);
-    hipLaunchKernelGGL((conv3x3_pipe_persist_kernel<NT, NWV, S>), dim3((unsigned)grid), dim3(C::NTHR), 2 * C::BUF_BYTES, s, k);
-  }
-  PT_HIP_CHECK(hipGetLastError());
-  return PT_OK;
+static ConvShape conv_shape_of(const ConvDesc& d) {
+  ConvShape c;
+  c.B = d.B; c.H = d.H; c.W = d.W; c.Cin = d.Cin; c.N = d.N; c.ks = d.ks; c.stride = d.stride;
+  c.rep = d.rep; c.shuffle_cout = d.shuffle_cout; c.res_mode = d.res_mode; c.relu = d.relu; c.pool = d.pool; c.split = d.split; c.nseg = d.nseg;
+  c.n_valid = d.n_valid; c.xp_store = d.xp_store; c.pick_B = d.pick_B; c.pick_Ho = d.pick_Ho;
+  for (int i = 0; i < 8; ++i) c.tap_mask[i] = d.tap_mask[i];
+  c.has_res = d.res; c.has_res_f32 = d.res_f32; c.has_out_f32 = d.out_f32; c.has_ylimit = d.ylimit; c.has_xlimit = d.xlimit; c.has_xlimit_rows = d.xlimit_rows;
+  c.has_block_list = d.block_list; c.has_head_w = d.head_w; c.has_argmax_part = d.argmax_part; c.has_hm_w2 = d.hm_w2;
+  return c;
 }
 
-// the heat-map head in one launch (conv3x3_pipe_persist_hm_kernel): always the persistent form, a workgroup's run is whole pixel tiles
-static int launch_pipe_persist_hm(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = PipeCfg<2, 8, 0, 1>;
-  using HM = PersistHm<2, 8, 1>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_pipe_persist_hm_kernel<2, 8, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, HM::SMEM));
-    attr_done = true;
-  }
-  k.n_tiles = k.N / C::NW;
-  k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
-  k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
-  const long long ptiles = (long long)k.B * k.tiles_x * k.tiles_y, total = ptiles * k.n_tiles;
-  PT_REQUIRE(k.n_tiles == 2 && total > 0 && total < (1ll << 31), "conv grid out of range (%lld tiles)", total);
-  k.total_tiles = (int)total;
-  long long grid = e->num_cu;      // (one workgroup's LDS per CU)
-  if (const char* gv = getenv("PT_CONV_PERSIST_GRID")) {          // tests: fewer workgroups, longer runs
-    const int gg = atoi(gv);
-    if (gg > 0) grid = gg;
-  }
-  if (grid > ptiles) grid = ptiles;
-  char label[48];
-  snprintf(label, sizeof(label), "conv3x3 v5+hm %d->%d->2 @%dx%d", k.Cin, k.N, k.Ho, k.Wo);
-  {
-    PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, label);
-    hipLaunchKernelGGL((conv3x3_pipe_persist_hm_kernel<2, 8, 1>), dim3((unsigned)grid), dim3(C::NTHR), HM::SMEM, s, k);
-  }
-  PT_HIP_CHECK(hipGetLastError());
-  return PT_OK;
-}
+bool pt_conv_fuses_hm(const pt_engine* e) { return conv_fuses_hm(ConvSwitches::read(), pt_split(e)); }
+bool pt_conv_takes_ws64(const pt_engine* e, int B, int Ho, int Wo) { return conv_takes_ws64(ConvSwitches::read(), e->num_cu, B, Ho, Wo); }
 
-// 1x1 stride-1 plain layers with K >= 256, N % 128 == 0, M % 32 == 0 in the single-pass modes: the pipelined GEMM (gemm_pipe_kernel)
-static int launch_gemm_pipe(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = GemmPipeCfg;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pipe_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pipe_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    attr_done = true;
-  }
-  const long long M = (long long)k.B * k.H * k.W, groups = M / 32;
-  {
-    const char* xv = getenv("PT_GEMM_XP");      // 0: 16-byte runs straight from the accumulators (A/B switch, read per call)
-    k.xp_store = !(xv && xv[0] == '0') && !k.out_f32;
-  }
-  k.n_tiles = k.N / C::NW;
-  k.tiles_x = (int)((groups + C::NG - 1) / C::NG);      // worst case with a list: every group live
-  k.tiles_y = 1;
-  const long long nblk = (long long)k.tiles_x * k.n_tiles;
-  PT_REQUIRE(nblk > 0 && nblk < (1ll << 31), "gemm grid out of range (%lld blocks)", nblk);
-  char label[48];
-  if (k.argmax_part) snprintf(label, sizeof(label), "classifier gemm+argmax");      // (the label bench.py's by_class files the CTC classifier under)
-  else snprintf(label, sizeof(label), "gemm %d->%d @%dx%d", k.Cin, k.N, k.Ho, k.Wo);
-  int lim_slot = -1;
-  {
-    PtProfScope prof(e, s, PT_PROF_CONV1X1, flop, label);
-    if (k.blist) hipLaunchKernelGGL((gemm_pipe_kernel<true>), dim3((unsigned)nblk), dim3(C::NTHR), C::SMEM, s, k);
-    else hipLaunchKernelGGL((gemm_pipe_kernel<false>), dim3((unsigned)nblk), dim3(C::NTHR), C::SMEM, s, k);
-    if (k.xcols && prof.idx >= 0 && e->prof.h_lims && e->prof.n_lims < PtProfile::MAX_LIMS) {      // ragged rows: credited at read-out, like launch_cfg
-      auto& pd = e->prof.pending[prof.idx];
-      pd.lim_slot = lim_slot = e->prof.n_lims++;
-      pd.rows = k.xlimit_rows ? k.Ho * k.Wo : k.B * k.Wo;
-    }
-  }
-  if (lim_slot >= 0) (void)hipMemcpyAsync(e->prof.h_lims + lim_slot, k.xcols, sizeof(int), hipMemcpyDeviceToHost, s);
-  PT_HIP_CHECK(hipGetLastError());
-  return PT_OK;
+// an instance as one switch value: the family and its template arguments (each below 16)
+constexpr unsigned conv_inst(ConvFamily f, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0, int g = 0, int h = 0) {
+  return (((((((unsigned)f * 16 + a) * 16 + b) * 16 + c) * 16 + d) * 16 + e) * 16 + g) * 16 + h;
 }
-
-// weight-stationary persistent kernel for plain 64 -> 64 layers (bf16 mode): one workgroup per CU walks total_tiles / grid tiles
-static int launch_ws64(pt_engine* e, ConvK& k, hipStream_t s, double flop) {
-  using C = Ws64Cfg;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_ws64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    attr_done = true;
+static unsigned conv_inst_of(const ConvPick& p) {
+  switch (p.family) {
+    case ConvFamily::chunk: return conv_inst(p.family, p.KS, p.STRIDE, p.GEOM, p.NHALF, p.DIRECT, p.F16);
+    case ConvFamily::wide1: return conv_inst(p.family, p.KG, p.STAGED, p.GEN);
+    case ConvFamily::pipe: return conv_inst(p.family, p.NT, p.NWV, p.SKEW, p.BR, p.DIRECT, p.S, p.PHASE);
+    case ConvFamily::gemm_pipe: return conv_inst(p.family, p.use_blist);
+    case ConvFamily::ws64: return conv_inst(p.family);
+    default: return conv_inst(p.family, p.NT, p.NWV, p.S);      // dma16, pipe_persist, pipe_persist_hm
   }
-  if (!e->zero_page) {
-    PT_HIP_CHECK(hipMalloc(&e->zero_page, 8192));
-    PT_HIP_CHECK(hipMemset(e->zero_page, 0, 8192));
-  }
-  k.tiles_x = (k.Wo + C::TW - 1) / C::TW;
-  k.tiles_y = (k.Ho + C::TH - 1) / C::TH;
-  k.n_tiles = 1;
-  const long long total = (long long)k.B * k.tiles_x * k.tiles_y;
-  PT_REQUIRE(total > 0 && total < (1ll << 30), "conv grid out of range (%lld tiles)", total);
-  k.total_tiles = (int)total;
-  unsigned nblk = (unsigned)(total < e->num_cu ? total : e->num_cu);
-  if (const char* gv = getenv("PT_CONV_WS64_GRID")) {      // tests: fewer workgroups, longer tile runs
-    const int g = atoi(gv);
-    if (g > 0 && (unsigned)g < nblk) nblk = (unsigned)g;
-  }
-  char label[48];
-  snprintf(label, sizeof(label), "conv3x3 ws %d->%d @%dx%d", k.Cin, k.N, k.Ho, k.Wo);
-  PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, label);
-  hipLaunchKernelGGL(conv3x3_ws64_kernel, dim3(nblk), dim3(C::NTHR), C::SMEM, s, k, reinterpret_cast<const bf16_t*>(e->zero_page));
-  PT_HIP_CHECK(hipGetLastError());
-  return PT_OK;
-}
-
-// PT_CONV_VARIANT: 0 = v1 only, 1 = micro-benchmark rule, 2 = v2 wherever it applies, 3 = v3 wherever it applies (default).
-// History: in the DB-ResNet18 graph at 8-page micro-batches v1-only measured fastest (det-only, no post: 3836 pages/s vs
-// 3764 with rule 1 and 3719 with v2) and was the default for most of round 1.  With 32-page det and 80-table Lore
-// micro-batches the 16-channel-slice DMA kernel wins where it applies (tools/ab_env.sh, two alternating runs each:
-// det-only 3503 / 3607 -> 3685 / 3647 pages/s, TSR-only 833 / 842 -> 845 / 859, four stages 354 / 358 -> 361 / 361).
-static int conv_variant() {
-  static int v = -1;
-  if (v < 0) {
-    const char* s = getenv("PT_CONV_VARIANT");
-    v = s ? atoi(s) : 3;
-  }
-  return v;
-}
-
-bool pt_conv_fuses_hm(const pt_engine* e) {
-  const char* ev = getenv("PT_LORE_HM_FUSE");      // 0: hm.0 and hm.2 as two launches (A/B switch, read per call)
-  const char* pv = getenv("PT_CONV_PIPE");         // below 4: the kernel families before the persistent tile, which the fused head is a form of
-  return !pt_split(e) && use_dma_kernel() && conv_variant() == 3 && !(pv && atoi(pv) < 4) && !(ev && atoi(ev) == 0);
-}
-
-// the tile-count rule of the weight-stationary 64 -> 64 kernel, apart from the layer's own properties (PT_CONV_WS64=0: never, 2: any tile count)
-bool pt_conv_takes_ws64(const pt_engine* e, int B, int Ho, int Wo) {
-  const char* ws_ev = getenv("PT_CONV_WS64");      // read per call (tests)
-  const int ws64 = ws_ev ? atoi(ws_ev) : 1;
-  return ws64 && (ws64 == 2 || (long long)B * ((Ho + 15) / 16) * ((Wo + 31) / 32) >= 4ll * e->num_cu);
 }
 
 int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
+  // 1. validate
   PT_REQUIRE(d.in && d.w && d.bias && (d.out || d.out_f32 || d.head_w || d.argmax_part || d.hm_w2), "conv: null pointer");
   PT_REQUIRE(d.Cin % 32 == 0 && d.Cin > 0, "conv: Cin=%d must be a positive multiple of 32", d.Cin);
   PT_REQUIRE(d.N % 64 == 0 && d.N > 0, "conv: N=%d must be a positive multiple of 64", d.N);
@@ -3628,14 +3375,9 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
   PT_REQUIRE(!(d.shuffle_cout && (d.rep != 1 || d.shuffle_cout % 64 != 0 || d.N != 4 * d.shuffle_cout)),
              "conv: bad pixel-shuffle configuration");
   PT_REQUIRE(d.rep >= 1 && d.out_cstride % 8 == 0 && d.out_coff % 8 == 0, "conv: bad output layout");
-  ConvK k;
-  memset(&k, 0, sizeof(k));
-  k.n_valid = d.n_valid; k.out_f32 = d.out_f32; k.res_f32 = d.res_f32;
   PT_REQUIRE(!d.res_f32 || d.out_f32, "conv: fp32 residual needs the fp32 output path");
   PT_REQUIRE(d.n_valid % 8 == 0 && d.n_valid <= d.N, "conv: n_valid=%d must be a multiple of 8 and <= N", d.n_valid);
   PT_REQUIRE(!(d.out_f32 && (d.rep != 1 || d.shuffle_cout)), "conv: fp32 output only on the plain store path");
-  k.in = d.in; k.w = d.w; k.bias = d.bias; k.out = d.out; k.res = d.res;
-  k.nseg = d.nseg;
   if (d.nseg > 1) {
     PT_REQUIRE(d.nseg <= 4 && d.ks == 1 && d.stride == 1, "conv: K over several tensors needs a 1x1 stride-1 layer and <= 4 segments");
     int sum = 0;
@@ -3644,45 +3386,56 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
       sum += d.seg_c[i];
     }
     PT_REQUIRE(sum == d.Cin, "conv: K segments sum to %d channels, Cin is %d", sum, d.Cin);
+  }
+  const ConvShape shape = conv_shape_of(d);
+  const int Ho = shape.Ho(), Wo = shape.Wo();
+  PT_REQUIRE(!d.xlimit_rows || (d.ks == 1 && d.stride == 1 && !d.ylimit && !d.xlimit), "conv: row-wise column limits need a 1x1 stride-1 layer");
+  PT_REQUIRE(!d.xlimit || (d.ks == 3 && d.stride == 1 && !d.ylimit), "conv: column limits need a 3x3 stride-1 layer");
+  PT_REQUIRE(!d.pool || (d.ks == 3 && d.stride == 1 && !d.res && !d.shuffle_cout && d.rep == 1 && !d.out_f32 && !d.argmax_part && !d.head_w && !d.n_valid && d.relu <= 1 && Ho % 2 == 0 && (d.pool != 1 || Wo % 2 == 0)),
+             "conv: fused pooling needs a plain 3x3 stride-1 layer with even output size");
+  PT_REQUIRE(d.relu != 3 || d.slope, "conv: PReLU needs the slope tensor");
+  if (d.head_w) PT_REQUIRE(d.shuffle_cout == 64 && d.head_b && (d.head_prob || d.head_logits), "conv: bad fused-head configuration");
+  if (d.res && d.res_mode == 2) PT_REQUIRE(Ho % 2 == 0 && Wo % 2 == 0, "conv: half-res residual needs even output size");
+  const ConvSwitches sw = ConvSwitches::read();
+  if (d.hm_w2) {
+    // hm.0 + hm.2 in one launch: the caller asked pt_conv_fuses_hm; anything but the plain 64 -> 256 + ReLU layer is a mistake, not a fall-back
+    PT_REQUIRE(conv_fuses_hm(sw, pt_split(e)) && d.ks == 3 && d.stride == 1 && d.Cin == 64 && d.N == 256 && d.relu == 1 && !d.res && !d.res_f32 && !d.split && d.nseg <= 1 &&
+                   !d.n_valid && !d.out_f32 && !d.head_w && !d.argmax_part && !d.ylimit && !d.xlimit && !d.xlimit_rows && !d.pool && d.rep == 1 && !d.shuffle_cout,
+               "conv: the fused heat-map head is the plain 3x3 64 -> 256 + ReLU layer in a single-pass mode");
+    PT_REQUIRE(d.hm_b2 && (d.hm_logits || d.hm_sig), "conv: fused heat-map head without bias or output");
+    for (int i = 0; i < 8; ++i) PT_REQUIRE(d.tap_mask[i] == 0, "conv: fused heat-map head with a tap mask");
+  }
+
+  // 2. the kernels' argument block; the launch's algorithmic FLOP and bytes for the profiler
+  ConvK k;
+  memset(&k, 0, sizeof(k));
+  k.in = d.in; k.w = d.w; k.bias = d.bias; k.out = d.out; k.res = d.res;
+  k.n_valid = d.n_valid; k.out_f32 = d.out_f32; k.res_f32 = d.res_f32;
+  k.nseg = d.nseg;
+  if (d.nseg > 1) {
     k.in1 = d.in_more[0]; k.in2 = d.in_more[1]; k.in3 = d.in_more[2];
     k.segc0 = d.seg_c[0]; k.segc1 = d.seg_c[1]; k.segc2 = d.seg_c[2]; k.segc3 = d.seg_c[3];
   }
-  k.B = d.B; k.H = d.H; k.W = d.W; k.Cin = d.Cin; k.N = d.N;
-  const int pad = d.ks / 2;
-  k.Ho = (d.H + 2 * pad - d.ks) / d.stride + 1;
-  k.Wo = (d.W + 2 * pad - d.ks) / d.stride + 1;
+  k.B = d.B; k.H = d.H; k.W = d.W; k.Cin = d.Cin; k.N = d.N; k.Ho = Ho; k.Wo = Wo;
   k.out_cstride = d.out_cstride; k.out_coff = d.out_coff; k.rep = d.rep; k.shuffle_cout = d.shuffle_cout;
   k.res_mode = d.res ? d.res_mode : 0; k.relu = d.relu; k.slope = d.slope; k.ylimit = d.ylimit; k.pool = d.pool;
   k.xlimit = d.xlimit; k.xlimit_rows = d.xlimit_rows; k.xcols = (d.xlimit || d.xlimit_rows) ? d.xlimit_cols : nullptr;
-  {
-    const char* bl = getenv("PT_CONV_BLOCK_LIST");      // PT_CONV_BLOCK_LIST=0: one image's 64 columns per workgroup (A/B switch, read per call)
-    k.blist = (d.xlimit && d.block_list && d.ks == 3 && d.stride == 1 && k.Ho <= 4 && k.Wo > 32 && k.Wo % 32 == 0 && !(bl && bl[0] == '0')) ? d.block_list : nullptr;
-  }
-  PT_REQUIRE(!d.xlimit_rows || (d.ks == 1 && d.stride == 1 && !d.ylimit && !d.xlimit), "conv: row-wise column limits need a 1x1 stride-1 layer");
-  PT_REQUIRE(!d.xlimit || (d.ks == 3 && d.stride == 1 && !d.ylimit), "conv: column limits need a 3x3 stride-1 layer");
-  PT_REQUIRE(!d.pool || (d.ks == 3 && d.stride == 1 && !d.res && !d.shuffle_cout && d.rep == 1 && !d.out_f32 && !d.argmax_part && !d.head_w && !d.n_valid && d.relu <= 1 && k.Ho % 2 == 0 && (d.pool != 1 || k.Wo % 2 == 0)),
-             "conv: fused pooling needs a plain 3x3 stride-1 layer with even output size");
-  PT_REQUIRE(d.relu != 3 || d.slope, "conv: PReLU needs the slope tensor");
   k.split = d.split; k.out_lo_off = d.out_lo_off;
-  // the extent the kernel choice below counts tiles over (ConvDesc.pick_B / pick_Ho)
-  const int pB = d.pick_B > 0 ? d.pick_B : k.B, pHo = d.pick_Ho > 0 ? d.pick_Ho : k.Ho;
   for (int i = 0; i < 8; ++i) k.tap_mask[i] = d.tap_mask[i];
-  {
-    // the layer asks for it (ConvDesc.xp_store: the detector's graph, +0.9 % det-only; the layout net's many small hardswish GEMMs lose
-    // 1.9 % to the extra barrier, the table nets are indifferent); PT_CONV_XP=0 / 1 forces it off / on everywhere (A/B switch, read per call)
-    const char* xv = getenv("PT_CONV_XP");
-    k.xp_store = (xv ? atoi(xv) : d.xp_store) && !d.out_f32;
-  }
   k.head_w = d.head_w; k.head_b = d.head_b; k.head_prob = d.head_prob; k.head_logits = d.head_logits;
   k.argmax_part = d.argmax_part;
-  if (d.head_w) PT_REQUIRE(d.shuffle_cout == 64 && d.head_b && (d.head_prob || d.head_logits), "conv: bad fused-head configuration");
-  if (k.res_mode == 2) PT_REQUIRE(k.Ho % 2 == 0 && k.Wo % 2 == 0, "conv: half-res residual needs even output size");
   // algorithmic FLOP (not x3 in split mode): the layer's real output channels, not the padded GEMM width; for a transposed
   // conv run as a pixel-shuffle GEMM N = 4 * Cout IS the work.  Row-limited launches are credited at read-out with the rows
-  // the device limit let through (launch_cfg)
+  // the device limit let through (pt_prof_limit_slot)
   const int n_alg = d.alg_n ? d.alg_n : (d.n_valid ? d.n_valid : d.N);
-  const double flop = 2.0 * k.B * k.Ho * k.Wo * (double)n_alg * d.Cin * d.ks * d.ks * d.alg_scale;
-  {
+  const double px = (double)k.B * Ho * Wo;
+  double flop = 2.0 * k.B * Ho * Wo * (double)n_alg * d.Cin * d.ks * d.ks * d.alg_scale;
+  if (d.hm_w2) {
+    k.head_w = d.hm_w2; k.head_b = d.hm_b2; k.head_logits = d.hm_logits; k.head_prob = d.hm_sig;
+    flop += 2.0 * px * d.N * 2.0;
+    // feat once, the stored map(s) once, both layers' weights once
+    e->prof.next_bytes = px * d.Cin * 2.0 + px * ((d.hm_logits ? 8 : 0) + (d.hm_sig ? 2 : 0)) * 4.0 + (double)d.N * d.Cin * 9 * 2.0 + 2.0 * d.N * 2.0;
+  } else {
     // algorithmic bytes of the launch (roofline.by_class of bench.py): every input pixel the layer samples once, every stored output once,
     // the residual once, the weights once; (hi | lo) tensors carry both halves
     const double mact = d.split ? 2.0 : 1.0, osz = d.out_f32 ? 4.0 : 2.0 * mact;
@@ -3693,155 +3446,107 @@ int pt_launch_conv(pt_engine* e, const ConvDesc& d, hipStream_t s) {
     by += (double)d.N * d.Cin * d.ks * d.ks * 2.0 * (d.split == 2 ? 2 : (d.split ? 3 : 1));
     e->prof.next_bytes = by;
   }
-  if (d.hm_w2) {
-    // hm.0 + hm.2 in one launch: the caller asked pt_conv_fuses_hm; anything but the plain 64 -> 256 + ReLU layer is a mistake, not a fall-back
-    PT_REQUIRE(pt_conv_fuses_hm(e) && d.ks == 3 && d.stride == 1 && d.Cin == 64 && d.N == 256 && d.relu == 1 && !d.res && !d.res_f32 && !d.split && d.nseg <= 1 &&
-                   !d.n_valid && !d.out_f32 && !d.head_w && !d.argmax_part && !d.ylimit && !d.xlimit && !d.xlimit_rows && !d.pool && d.rep == 1 && !d.shuffle_cout,
-               "conv: the fused heat-map head is the plain 3x3 64 -> 256 + ReLU layer in a single-pass mode");
-    PT_REQUIRE(d.hm_b2 && (d.hm_logits || d.hm_sig), "conv: fused heat-map head without bias or output");
-    for (int i = 0; i < 8; ++i) PT_REQUIRE(d.tap_mask[i] == 0, "conv: fused heat-map head with a tap mask");
-    k.head_w = d.hm_w2; k.head_b = d.hm_b2; k.head_logits = d.hm_logits; k.head_prob = d.hm_sig;
-    const double px = (double)k.B * k.Ho * k.Wo;
-    // feat once, the stored map(s) once, both layers' weights once
-    e->prof.next_bytes = px * d.Cin * 2.0 + px * ((d.hm_logits ? 8 : 0) + (d.hm_sig ? 2 : 0)) * 4.0 + (double)d.N * d.Cin * 9 * 2.0 + 2.0 * d.N * 2.0;
-    return launch_pipe_persist_hm(e, k, s, flop + 2.0 * px * d.N * 2.0);
+
+  // 3. the choice (conv_pick.h) and what it fixes in the argument block
+  const ConvPick p = conv_pick(shape, e->num_cu, sw);
+  const ConvGrid g = conv_pick_grid(shape, p, e->num_cu, sw);
+  {      // (the persistent families count tiles, the others the blocks they launch)
+    const bool walks = p.family == ConvFamily::pipe_persist || p.family == ConvFamily::pipe_persist_hm || p.family == ConvFamily::ws64;
+    PT_REQUIRE(g.count > 0 && g.count < g.limit, "%s grid out of range (%lld %s)", p.family == ConvFamily::gemm_pipe ? "gemm" : "conv", g.count, walks ? "tiles" : "blocks");
   }
-  // stride-2 3x3 layers with 128-wide output blocks (ResNet-18 / DLA-34 down-sampling convs): the 16-channel-slice DMA kernel on an 8 x 32 x 128 tile
-  // (PT_CONV_S2_DMA=0: the register-staged 4 x 32 x 64 tile, A/B switch)
-  if (d.ks == 3 && d.stride == 2 && !d.split && d.N % 128 == 0 && d.Cin % 32 == 0 && d.Cin >= 64 && pHo >= 8 && !d.head_w && !d.argmax_part && !d.n_valid &&
-      !d.out_f32 && !d.res_f32 && !d.res && d.relu < 2 && !d.ylimit && !d.xlimit && !d.xlimit_rows && !d.pool && d.rep == 1 && !d.shuffle_cout && use_dma_kernel()) {
-    static int s2 = -1;
-    if (s2 < 0) { const char* ev = getenv("PT_CONV_S2_DMA"); s2 = ev ? atoi(ev) : 1; }
-    bool masked = false;
-    for (int i = 0; i < 8; ++i) masked = masked || d.tap_mask[i] != 0;
-    const char* pv2 = getenv("PT_CONV_PIPE");      // 0: the v3 stride-2 tile (A/B switch, read per call)
-    if (s2 && !masked && !(pv2 && pv2[0] == '0')) return launch_pipe<2, 8, true, 0, true, 2>(e, k, s, flop);
-    if (s2 && !masked) return launch_dma16<2, 8, 2>(e, k, s, flop);
+  k.blist = p.use_blist ? d.block_list : nullptr;
+  k.n_group = p.n_group; k.xp_store = p.xp_store; k.reps = p.reps;
+  k.tiles_x = g.tiles_x; k.tiles_y = g.tiles_y; k.n_tiles = g.n_tiles; k.total_tiles = g.total_tiles;
+  char label[kConvLabelLen];
+  conv_pick_label(shape, p, label);
+  const ConvLaunch L{e, k, (unsigned)g.nblk, label, d.ks == 3 ? PT_PROF_CONV3X3 : PT_PROF_CONV1X1, flop, s};
+
+  // 4. the instance: runtime -> template, one row per instantiated kernel.  The switch value of a row (conv_inst) packs the family and the template
+  //    arguments that conv_pick_kernel_name prints for it; conv_inst_of packs the same fields of the pick, and a pick without a row is refused by name.
+  //    The ORDER of the rows is the order in which the launchers that this table replaced first used each instance: the compiler emits the kernels in that order, so
+  //    keeping it keeps the code object byte-identical.  Reordering or adding rows is harmless to behaviour; it only moves kernels in the object.
+  //    The dma16 kernel reads the zero page; the pipe kernel takes the engine's pointer as it is and the ws64 kernel ignores its own (neither reads it).
+#define PT_CHUNK(KS, ST, GEOM, NHALF, DIRECT, F16) \
+  case conv_inst(ConvFamily::chunk, KS, ST, GEOM, NHALF, DIRECT, F16): return launch_conv<&conv_igemm_kernel<KS, ST, GEOM, NHALF, DIRECT, F16>>(L, 256, ConvCfg<KS, ST, GEOM>::SMEM)
+#define PT_WIDE1(KG, STAGED, GEN) \
+  case conv_inst(ConvFamily::wide1, KG, STAGED, GEN): return launch_conv<&conv1x1_wide_kernel<KG, STAGED, GEN>>(L, 256, STAGED ? Conv1WideCfg<KG>::SMEM_STAGED : Conv1WideCfg<KG>::SMEM)
+#define PT_DMA16(NT, NWV, S)                                                          \
+  case conv_inst(ConvFamily::dma16, NT, NWV, S):                                      \
+    if (int rc = pt_zero_page(e)) return rc;                                          \
+    return launch_conv<&conv3x3_dma16_kernel<NT, NWV, S>>(L, Dma16Cfg<NT, NWV, S>::NTHR, Dma16Cfg<NT, NWV, S>::SMEM, reinterpret_cast<const bf16_t*>(e->zero_page))
+#define PT_PIPE(NT, NWV, SKEW, BR, DIRECT, S, PHASE)                 \
+  case conv_inst(ConvFamily::pipe, NT, NWV, SKEW, BR, DIRECT, S, PHASE): \
+    return launch_conv<&conv3x3_pipe_kernel<NT, NWV, SKEW, BR, DIRECT, S, PHASE>>(L, PipeCfg<NT, NWV, BR, S>::NTHR, PipeCfg<NT, NWV, BR, S>::SMEM, reinterpret_cast<const bf16_t*>(e->zero_page))
+#define PT_PERSIST(NT, NWV, S) \
+  case conv_inst(ConvFamily::pipe_persist, NT, NWV, S): return launch_conv<&conv3x3_pipe_persist_kernel<NT, NWV, S>>(L, PipeCfg<NT, NWV, 0, S>::NTHR, 2 * PipeCfg<NT, NWV, 0, S>::BUF_BYTES)
+  switch (conv_inst_of(p)) {
+    PT_CHUNK(3, 1, 0, 1, false, false);      // <= 32 real output channels, staged epilogue
+    case conv_inst(ConvFamily::pipe_persist_hm, 2, 8, 1): return launch_conv<&conv3x3_pipe_persist_hm_kernel<2, 8, 1>>(L, PipeCfg<2, 8, 0, 1>::NTHR, PersistHm<2, 8, 1>::SMEM);
+    case conv_inst(ConvFamily::gemm_pipe, false): return launch_conv<&gemm_pipe_kernel<false>>(L, GemmPipeCfg::NTHR, GemmPipeCfg::SMEM);
+    case conv_inst(ConvFamily::gemm_pipe, true): return launch_conv<&gemm_pipe_kernel<true>>(L, GemmPipeCfg::NTHR, GemmPipeCfg::SMEM);
+    PT_PIPE(2, 8, true, 0, true, 2, false);      // stride 2
+    PT_DMA16(2, 8, 2);
+    PT_PIPE(2, 8, true, 0, false, 1, true);      // phase convolutions
+    PT_PIPE(1, 4, false, 0, false, 1, false);    // PT_CONV_PIPE=1
+    PT_PIPE(2, 8, false, 0, false, 1, false);
+    PT_PIPE(1, 8, false, 0, false, 1, false);
+    PT_PERSIST(2, 8, 1);
+    PT_PERSIST(1, 8, 1);
+    PT_PIPE(1, 4, true, 0, true, 1, false);      // register epilogue
+    PT_PIPE(2, 8, true, 0, true, 1, false);
+    PT_PIPE(1, 8, true, 0, true, 1, false);
+    PT_PIPE(1, 4, true, 0, false, 1, false);     // staged epilogue
+    PT_PIPE(2, 8, true, 0, false, 1, false);
+    PT_PIPE(1, 8, true, 0, false, 1, false);
+    PT_DMA16(1, 4, 1);
+    PT_DMA16(2, 8, 1);
+    PT_DMA16(1, 8, 1);
+    PT_PIPE(2, 8, true, 4, true, 1, false);      // 4- and 8-row maps: blocks of 4 / 8 rows
+    PT_PIPE(2, 8, true, 8, true, 1, false);
+    PT_PIPE(2, 8, true, 4, false, 1, false);
+    PT_PIPE(2, 8, true, 8, false, 1, false);
+    PT_CHUNK(3, 1, 1, 2, false, false);          // the 4 x 64 patch
+    PT_CHUNK(3, 1, 1, 2, false, true);
+    PT_CHUNK(3, 1, 0, 1, true, false);           // <= 32 real output channels, register epilogue
+    PT_WIDE1(4, false, true);
+    PT_WIDE1(2, false, true);
+    PT_WIDE1(4, false, false);
+    PT_WIDE1(2, false, false);
+    PT_WIDE1(4, true, true);
+    PT_WIDE1(2, true, true);
+    PT_WIDE1(4, true, false);
+    PT_WIDE1(2, true, false);
+    PT_CHUNK(1, 1, 0, 2, true, false);           // register epilogue
+    PT_CHUNK(3, 2, 0, 2, true, false);
+    PT_CHUNK(1, 2, 0, 2, true, false);
+    PT_CHUNK(3, 1, 0, 2, true, false);
+    PT_CHUNK(3, 1, 0, 2, false, false);          // staged epilogue; F16: the two-pass fp16 variant of the (hi | lo) modes
+    PT_CHUNK(3, 1, 0, 2, false, true);
+    PT_CHUNK(3, 2, 0, 2, false, false);
+    PT_CHUNK(3, 2, 0, 2, false, true);
+    PT_CHUNK(1, 1, 0, 2, false, false);
+    PT_CHUNK(1, 1, 0, 2, false, true);
+    PT_CHUNK(1, 2, 0, 2, false, false);
+    PT_CHUNK(1, 2, 0, 2, false, true);
+    case conv_inst(ConvFamily::ws64):
+      if (int rc = pt_zero_page(e)) return rc;
+      return launch_conv<&conv3x3_ws64_kernel>(L, Ws64Cfg::NTHR, Ws64Cfg::SMEM, reinterpret_cast<const bf16_t*>(e->zero_page));
   }
-  if (d.ks == 3 && d.stride == 1 && !d.head_w && !d.argmax_part && !d.n_valid && !d.out_f32 && !d.res_f32 && d.relu < 2 && !d.ylimit && !d.xlimit && !d.pool && d.split != 2 && use_dma_kernel()) {
-    // steady-state A/B on MI355X (tools/ab3.sh, round 1): the 16-channel-slice DMA kernel (v3) wins on >= 120-row maps
-    // with K >= 128 channels, the 32-channel-slice DMA kernel (v2) on 60..119-row maps, the register-staged kernel
-    // (v1) on short-K layers and on small maps, where the big DMA tiles leave CUs idle
-    const int cv = conv_variant();
-    // plain 64 -> 64 layers with enough tiles to give every CU a run of them: the weight-stationary persistent kernel
-    // (PT_CONV_WS64=0: the v3 tiles, A/B switch)
-    bool masked = false;
-    for (int i = 0; i < 8; ++i) masked = masked || d.tap_mask[i] != 0;
-    if (cv == 3 && !d.split && d.Cin == 64 && d.N == 64 && d.rep == 1 && !d.shuffle_cout && d.res_mode <= 1 && !masked &&
-        pt_conv_takes_ws64(e, pB, pHo, k.Wo))
-      return launch_ws64(e, k, s, flop);
-    const bool v3ok = (d.N % 128 == 0) ? pHo >= 12 : pHo >= 24;
-    const bool wide = d.Cin >= 128;
-    int pick = 0;
-    if (cv == 3 && v3ok) pick = 3;
-    else if (cv == 1 && wide && k.Ho >= 120) pick = 3;
-    // 4-wave workgroups (16x32 pixels x 64 channels, 74 KB of LDS: two per CU) where the 8-wave tile is mostly prologue and
-    // epilogue: short K (Cin <= 128: +3..8 % on 64->64 @240^2 / @256^2, 128->128 @120^2 / @128^2, 64->256 @256^2), and grids
-    // that leave the 8-wave tiling with a ragged last round (512->512 @32^2 x 44: +12 %); K >= 2304 layers whose grid is whole
-    // rounds stay on the 8-wave tiles (512->512 @30^2 x 32: -3 % as 4-wave).  PT_CONV_HALF = 0 / 1 forces one of them.
-    static int half = -2;
-    if (half == -2) { const char* ev = getenv("PT_CONV_HALF"); half = ev ? atoi(ev) : -1; }
-    bool use_half = half == 1;
-    if (half < 0 && pick == 3) {
-      const bool nt2 = d.N % 128 == 0;
-      const long long full = (long long)pB * ((pHo + (nt2 ? 15 : 31)) / (nt2 ? 16 : 32)) * ((k.Wo + 31) / 32) * (d.N / (nt2 ? 128 : 64));
-      use_half = d.Cin <= 128 || (full < 2ll * e->num_cu && full % e->num_cu != 0);
-    }
-    // v4 (software-pipelined tap loop) for the unmasked layers; PT_CONV_PIPE=0: v3 everywhere (A/B switch, read per call)
-    const char* pv = getenv("PT_CONV_PIPE");
-    // the phase convolutions (db_model.hip phase_masks: four 64-channel tiles, taps (dy .. dy + 1) x (dx .. dx + 1)) have their own v4 variant
-    bool phase = masked && d.N == 256;
-    for (int i = 0; i < 8 && phase; ++i) {
-      unsigned mk = 0;
-      if (i < 4)
-        for (int r = i >> 1; r < (i >> 1) + 2; ++r)
-          for (int q = i & 1; q < (i & 1) + 2; ++q) mk |= 1u << (r * 3 + q);
-      phase = d.tap_mask[i] == mk;
-    }
-    if (phase && cv == 3 && v3ok && !(pv && atoi(pv) < 3)) return launch_pipe<2, 8, true, 0, false, 1, true>(e, k, s, flop);
-    const int pipe = masked ? 0 : (pv ? atoi(pv) : 4);      // 1: barrier behind tap 8, 2: in front of it (SKEW), 3: + register epilogue on plain layers, 4: + persistent workgroups
-    if (pick == 3 && pipe == 1) {
-      if (use_half) return launch_pipe<1, 4, false>(e, k, s, flop);
-      return d.N % 128 == 0 ? launch_pipe<2, 8, false>(e, k, s, flop) : launch_pipe<1, 8, false>(e, k, s, flop);
-    }
-    if (pick == 3 && pipe >= 2) {
-      // register epilogue for the plain layers (PT_CONV_PIPE=2: the staged fp32 epilogue everywhere, A/B switch)
-      const bool direct = pipe >= 3 && !k.split && !k.pool && !k.shuffle_cout;
-      // 4: the persistent form for the 8-wave tiles where a workgroup gets at least two tiles (interleaved A/B, tools/conv_ab.py: 256 -> 256 @64^2 1305 -> 1327
-      // TF/s, @60^2 1174 -> 1198, 512 -> 512 @32^2 1379 -> 1404, @30^2 1267 -> 1275; the 4-wave tile LOSES 14 % as a persistent kernel -- 128 -> 128 @128^2
-      // 1134 -> 975: two of its workgroups per CU already cover each other's prologues, and the run's bookkeeping costs it registers it does not have)
-      const bool nt2 = d.N % 128 == 0;
-      const long long tiles = (long long)pB * ((pHo + (nt2 ? 15 : 31)) / (nt2 ? 16 : 32)) * ((k.Wo + 31) / 32) * (d.N / (nt2 ? 128 : 64));
-      // (a four-slice layer without a residual is better off on the persistent 8-wave tile than on the 4-wave one: 64 -> 256 @256^2 900 -> 955 TF/s; with
-      // eight slices the two are level -- 128 -> 128 @128^2 1101 / 1120 -- and with a residual the 4-wave tile wins, 922 against 862)
-      if (use_half && half < 0 && direct && pipe >= 4 && d.Cin == 64 && nt2 && !d.res && tiles >= 2ll * e->num_cu) use_half = false;
-      if (direct && pipe >= 4 && (!use_half || pipe >= 5) && !k.xlimit && !k.xlimit_rows && !k.blist) {
-        if (tiles >= 2ll * e->num_cu || pipe >= 5)      // (5: whatever the tile count -- tests)
-          return nt2 ? launch_pipe_persist<2, 8, 1>(e, k, s, flop) : launch_pipe_persist<1, 8, 1>(e, k, s, flop);
-      }
-      if (direct) {
-        if (use_half) return launch_pipe<1, 4, true, 0, true>(e, k, s, flop);
-        return d.N % 128 == 0 ? launch_pipe<2, 8, true, 0, true>(e, k, s, flop) : launch_pipe<1, 8, true, 0, true>(e, k, s, flop);
-      }
-      if (use_half) return launch_pipe<1, 4, true>(e, k, s, flop);
-      return d.N % 128 == 0 ? launch_pipe<2, 8, true>(e, k, s, flop) : launch_pipe<1, 8, true>(e, k, s, flop);
-    }
-    if (pick == 3 && use_half) return launch_dma16<1, 4>(e, k, s, flop);
-    if (pick == 3) return d.N % 128 == 0 ? launch_dma16<2, 8>(e, k, s, flop) : launch_dma16<1, 8>(e, k, s, flop);
-  }
-  // maps that are exactly 4 or 8 rows high with K >= 1152 and 128-wide output blocks (the CRNN conv2.* / conv3.* layers): the pipelined DMA kernel on
-  // tiles of four 4 x 32 / two 8 x 32 blocks -- from the compacted list of live blocks when the layer has one (PT_CONV_PIPE_BLOCKS=0: the
-  // register-staged kernels, A/B switch read per call)
-  if (d.ks == 3 && d.stride == 1 && (k.Ho == 4 || k.Ho == 8) && k.H == k.Ho && k.Wo % 32 == 0 && k.Wo > 32 && d.N % 128 == 0 && d.Cin >= 128 && !d.head_w &&
-      !d.argmax_part && !d.n_valid && !d.out_f32 && !d.res_f32 && !d.res && d.relu < 2 && !d.ylimit && !d.xlimit_rows && d.rep == 1 && !d.shuffle_cout &&
-      d.split != 2 && use_dma_kernel()) {
-    const char* pb = getenv("PT_CONV_PIPE_BLOCKS");
-    const char* pv = getenv("PT_CONV_PIPE");
-    bool masked = false;
-    for (int i = 0; i < 8; ++i) masked = masked || d.tap_mask[i] != 0;
-    if (!masked && !(pb && pb[0] == '0') && !(pv && pv[0] == '0')) {
-      if (d.xlimit && d.block_list) k.blist = d.block_list;      // (8-row maps too: the GEOM 1 rule above only takes lists for <= 4 rows)
-      if (!k.split && !k.pool && !(pv && atoi(pv) < 3))           // plain layer: register epilogue
-        return k.Ho == 4 ? launch_pipe<2, 8, true, 4, true>(e, k, s, flop) : launch_pipe<2, 8, true, 8, true>(e, k, s, flop);
-      return k.Ho == 4 ? launch_pipe<2, 8, true, 4>(e, k, s, flop) : launch_pipe<2, 8, true, 8>(e, k, s, flop);
-    }
-  }
-  if (d.ks == 3 && d.stride == 1 && k.Ho <= 4 && k.Wo > 32) return launch_cfg<3, 1, 1>(e, k, s, flop);
-  if (d.ks == 3 && d.stride == 1) return launch_cfg<3, 1>(e, k, s, flop);
-  if (d.ks == 3 && d.stride == 2) return launch_cfg<3, 2>(e, k, s, flop);
-  // (K >= 512: at K = 256 a tile is four slices -- mostly prologue and epilogue of a workgroup that has the CU to itself -- and the 2048-wide
-  // projection measured 1.65 ms against the streaming row GEMM's 1.42; K = 512 ... 1024: 1.43 -> 1.35, 0.70 -> 0.60, 0.42 -> 0.34, 1.17 -> 0.63 ms)
-  if (d.ks == 1 && d.stride == 1 && !d.split && d.nseg <= 1 && d.Cin >= 512 && d.Cin % 64 == 0 && d.N % 128 == 0 && ((long long)d.B * d.H * d.W) % 32 == 0 &&
-      !d.head_w && (!d.argmax_part || (!d.res && !d.relu)) && !d.res_f32 && !d.shuffle_cout && !d.pool && !d.ylimit && !d.xlimit && d.rep == 1 && (!d.res || d.res_mode == 1) &&
-      (!d.xlimit_rows || (d.block_list && d.W % 32 == 0)) && use_dma_kernel()) {
-    const char* gv = getenv("PT_GEMM_PIPE");      // 0: the 4 x 32 x 64 tile kernels (A/B switch, read per call)
-    if (!(gv && gv[0] == '0')) {
-      k.blist = d.xlimit_rows ? d.block_list : nullptr;
-      return launch_gemm_pipe(e, k, s, flop);
-    }
-  }
-  if (d.ks == 1) {
-    // column tiles per group: ~2 MB of weights (half of an XCD's L2); PT_N_GROUP overrides (0 = off)
-    static int ng_env = -2;
-    if (ng_env == -2) { const char* s_ = getenv("PT_N_GROUP"); ng_env = s_ ? atoi(s_) : -1; }
-    const long long tile_bytes = 64ll * d.Cin * 2 * (d.split == 2 ? 2 : (d.split ? 3 : 1));
-    int g = ng_env >= 0 ? ng_env : (int)((2ll << 20) / tile_bytes);
-    if (g < 1) g = ng_env == 0 ? 0 : 1;
-    k.n_group = g;
-  }
-  if (d.ks == 1 && d.stride == 1) return launch_cfg<1, 1>(e, k, s, flop);
-  return launch_cfg<1, 2>(e, k, s, flop);
+#undef PT_CHUNK
+#undef PT_WIDE1
+#undef PT_DMA16
+#undef PT_PIPE
+#undef PT_PERSIST
+  char name[96];
+  conv_pick_kernel_name(p, name, sizeof(name));
+  pt_set_error("conv: %s is not an instance of this library", name);
+  return PT_ERR_INVALID;
 }
 
 // CRNN conv0 + pool + conv1 + pool in one launch (crnn_conv01_kernel): gray [n][32][640] -> p1 [n][8][160][128]; xlimit: conv1's per-line column limits
 int pt_launch_crnn_conv01(pt_engine* e, const bf16_t* gray, int n, const float* w64x9, const float* b0, const bf16_t* w1, const float* b1, bf16_t* p1,
                           const int* xlimit, const int* xlimit_cols, hipStream_t s) {
   using C = Conv01Cfg;
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&crnn_conv01_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::SMEM));
-    attr_done = true;
-  }
   ConvK k;
   memset(&k, 0, sizeof(k));
   k.in = gray; k.head_w = w64x9; k.head_b = b0; k.w = w1; k.bias = b1; k.out = p1;
@@ -3851,19 +3556,7 @@ int pt_launch_crnn_conv01(pt_engine* e, const bf16_t* gray, int n, const float* 
   k.tiles_x = 10; k.tiles_y = 1; k.n_tiles = 1;
   const double flop = 2.0 * n * 16 * 320 * 128.0 * 64 * 9;
   e->prof.next_bytes = 2.0 * n * (32.0 * 640 + 8.0 * 160 * 128);
-  int lim_slot = -1;
-  {
-    PtProfScope prof(e, s, PT_PROF_CONV3X3, flop, "conv0+pool+conv1+pool 1->64->128 @16x320");
-    hipLaunchKernelGGL(crnn_conv01_kernel, dim3((unsigned)(n * 10)), dim3(C::NTHR), C::SMEM, s, k);
-    if (k.xcols && prof.idx >= 0 && e->prof.h_lims && e->prof.n_lims < PtProfile::MAX_LIMS) {
-      auto& pd = e->prof.pending[prof.idx];
-      pd.lim_slot = lim_slot = e->prof.n_lims++;
-      pd.rows = k.B * k.Wo;
-    }
-  }
-  if (lim_slot >= 0) (void)hipMemcpyAsync(e->prof.h_lims + lim_slot, k.xcols, sizeof(int), hipMemcpyDeviceToHost, s);
-  PT_HIP_CHECK(hipGetLastError());
-  return PT_OK;
+  return launch_conv<&crnn_conv01_kernel>(ConvLaunch{e, k, (unsigned)(n * 10), "conv0+pool+conv1+pool 1->64->128 @16x320", PT_PROF_CONV3X3, flop, s}, C::NTHR, C::SMEM);
 }
 
 // depthwise k x k (stride 1 / 2) + pointwise 1x1 in one launch (dwpw_kernel); returns PT_ERR_INVALID when the pair is outside the kernel's
@@ -3901,12 +3594,7 @@ int pt_launch_dwpw(pt_engine* e, const bf16_t* in, int B, int H, int W, int C, c
 
 template <int S, int NH>
 static int launch_stem(pt_engine* e, ConvK& k, hipStream_t s) {
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem7x7_kernel<S, NH>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, StemCfg<S>::SMEM));
-    attr_done = true;
-  }
+  if (int rc = pt_lds_attr<&conv_stem7x7_kernel<S, NH>>(StemCfg<S>::SMEM)) return rc;
   k.tiles_x = (k.Wo + 31) / 32; k.tiles_y = (k.Ho + 7) / 8; k.n_tiles = 1;
   const long long nblk = (long long)k.B * k.tiles_x * k.tiles_y;
   PT_REQUIRE(nblk > 0 && nblk < (1ll << 31), "stem grid out of range");
@@ -3921,12 +3609,7 @@ int pt_launch_stem7x7_pool(pt_engine* e, const bf16_t* in, int B, int H, int W, 
                            hipStream_t s) {
   PT_REQUIRE(in && w && bias && out, "stem+pool: null pointer");
   PT_REQUIRE(H % 4 == 0 && W % 4 == 0 && H > 0 && W > 0, "stem+pool: H, W must be multiples of 4");
-  static bool attr_done = false;
-  if (!attr_done) {
-    PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem7x7_pool_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, StemPoolCfg::SMEM));
-    attr_done = true;
-  }
+  if (int rc = pt_lds_attr<&conv_stem7x7_pool_kernel>(StemPoolCfg::SMEM)) return rc;
   ConvK k;
   memset(&k, 0, sizeof(k));
   k.in = in; k.w = w; k.bias = bias; k.out = out;
@@ -3940,11 +3623,7 @@ int pt_launch_stem7x7_pool(pt_engine* e, const bf16_t* in, int B, int H, int W, 
   PtProfScope prof(e, s, PT_PROF_STEM, 2.0 * B * k.Ho * k.Wo * 64.0 * 147.0, "stem7x7 s2 + maxpool");
   const char* ws_ev = getenv("PT_STEM_POOL_WS");      // 0: one tile per workgroup (A/B switch, read per call)
   if (!(ws_ev && atoi(ws_ev) == 0)) {
-    static bool ws_attr = false;
-    if (!ws_attr) {
-      PT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_stem7x7_pool_ws_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, StemPoolCfg::SMEM));
-      ws_attr = true;
-    }
+    if (int rc = pt_lds_attr<&conv_stem7x7_pool_ws_kernel>(StemPoolCfg::SMEM)) return rc;
     k.total_tiles = (int)nblk;
     unsigned g = (unsigned)(nblk < e->num_cu ? nblk : e->num_cu);
     if (const char* gv = getenv("PT_STEM_POOL_WS_GRID")) {      // tests: fewer workgroups, longer tile runs
